@@ -24,6 +24,12 @@ metric value = matched rows / s, where matched rows = count(*) of the same MATCH
 CAPS's joins would emit.  It is computed once in closed form (sum_b in(b)*out(b) - self-loops) on the
 device outside the timed region; the query itself never enumerates bindings.
 Run: python bench.py [--gpus N --steps K --warmup W]  (torch.distributed.run for N > 1)
+
+A plain run does what the headline figure needs and no more: ingest, the warm-up and the timed steps of
+the first mode, the matched rows, the result line (and --dump-outputs DIR: what the last timed step
+returned, as DIR/<name>.npy).  --full adds everything else: the other modes, the per-kernel timers and
+the roofline (a few profiled steps of their own), the checks against the committed fixtures and the
+unsharded table, and the CPU baselines.
 """
 import argparse
 import ctypes
@@ -129,7 +135,35 @@ def parse():
     p.add_argument("--c5-upper", type=int, default=3, choices=(3, 4),
                    help="C5's upper bound: 3 (the BASELINE config) or 4 (the four-hop fused count, one GPU; a "
                         "diagnostic line without a fixture: its parity is the tests' against enumeration)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline figure: every mode of --modes (a plain run times the first alone), the "
+                        "per-kernel timers and the roofline, the checks against the fixtures / the unsharded table, "
+                        "the CPU baselines")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned to its caller as "
+                        "DIR/<name>.npy (float64; at most 64 MB in all: a larger table is a fixed, seeded sample of "
+                        "its sorted rows)")
+    args = p.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_BYTES = 64 << 20  # --dump-outputs: the files' arrays together stay under this
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array of `arrays` (name -> 1-D numpy array, all of one length: the columns of the
+    answer) as dirname/<name>.npy in float64.  More than DUMP_BYTES in all: the same seeded sample of rows of
+    every column (the generator's seed is fixed, so two runs of the same arguments keep the same rows)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    rows = len(next(iter(arrays.values())))
+    keep = DUMP_BYTES // (8 * len(arrays))
+    idx = np.sort(np.random.default_rng(42).integers(0, rows, keep)) if rows > keep else None
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        np.save(os.path.join(dirname, name + ".npy"), (a if idx is None else a[idx]).astype(np.float64))
 
 
 def cpu_baseline(scale, ef):
@@ -342,6 +376,9 @@ def main():
         modes = [m for m in modes if not m.startswith("count")] or ["cold"]
     elif distributed:  # the drop-in route on every rank (no explicit-kernel or atomic A/B forms)
         modes = [m for m in modes if m in ("cold", "warm", "count")] or ["cold"]
+    full = args.full
+    if not full:  # a plain run: the headline mode alone
+        modes = modes[:1]
 
     # ---- ingest (untimed): relationship table + Person node table ---------------------------------
     # N > 1: every rank generates the graph and keeps its shard -- the relationships whose target it
@@ -540,15 +577,18 @@ def main():
             res = step()
         # every timer over a few untimed steps: the per-kernel breakdown and the dominant kernel.  The timed
         # steps then bracket only the dominant launch (its events are the roofline's live measurement): each
-        # timer's two event records leave the device idle for a few microseconds
-        _lib.call("capsmi_session_set_profiling", sess.handle, 1)
-        kernel_times()  # reset
-        for _ in range(PROFILED_STEPS):
-            step()
-        kt_all = {k: v for k, v in kernel_times().items() if v[0] > 0}
-        dom_name = max(kt_all, key=lambda k: kt_all[k][1]) if kt_all else None
-        _lib.call("capsmi_session_set_profiling_names", sess.handle, dom_name.encode() if dom_name else None)
-        pre = mode in plans_of and shards == 1 and not args.plan_in_step
+        # timer's two event records leave the device idle for a few microseconds.  (--full; a plain run keeps
+        # every timer off and reports no per-kernel figure)
+        kt_all, dom_name = {}, None
+        if full:
+            _lib.call("capsmi_session_set_profiling", sess.handle, 1)
+            kernel_times()  # reset
+            for _ in range(PROFILED_STEPS):
+                step()
+            kt_all = {k: v for k, v in kernel_times().items() if v[0] > 0}
+            dom_name = max(kt_all, key=lambda k: kt_all[k][1]) if kt_all else None
+            _lib.call("capsmi_session_set_profiling_names", sess.handle, dom_name.encode() if dom_name else None)
+        pre =mode in plans_of and shards == 1 and not args.plan_in_step
         if pre:  # this mode's plans, one per timed step, built before the timed region (timed apart)
             tp = time.perf_counter()
             queue = [plans_of[mode]() for _ in range(args.steps)]
@@ -563,7 +603,8 @@ def main():
                         gate.release()
         if gate is not None:
             gate.busy = 0.0
-        kernel_times()  # reset
+        if full:
+            kernel_times()  # reset
         if distributed:
             dist.barrier()
         torch.cuda.synchronize()
@@ -579,9 +620,10 @@ def main():
         per_step = [b - a for a, b in zip([t0] + marks[:-1], marks)]
         medians[mode] = sorted(per_step)[len(per_step) // 2] * 1e3 if per_step else None
         kt = dict(kt_all)
-        kt.update({k: v for k, v in kernel_times().items() if v[0] > 0})  # the dominant launch, timed steps
-        _lib.call("capsmi_session_set_profiling", sess.handle, 0)
-        _lib.call("capsmi_session_set_profiling_names", sess.handle, None)
+        if full:
+            kt.update({k: v for k, v in kernel_times().items() if v[0] > 0})  # the dominant launch, timed steps
+            _lib.call("capsmi_session_set_profiling", sess.handle, 0)
+            _lib.call("capsmi_session_set_profiling_names", sess.handle, None)
         if distributed:
             tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
             dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -600,16 +642,18 @@ def main():
     matched = check = None
     fx = fixture(f"c3_s{scale}") if ef == 16 else None
     if rank == 0:
-        full = graph.rmat_rels(sess, scale, 0, m_total, graph.RMAT_GRAPH500, 42) if distributed else rels
+        whole = graph.rmat_rels(sess, scale, 0, m_total, graph.RMAT_GRAPH500, 42) if distributed else rels
         all_persons = graph.rmat_nodes(sess, scale, graph.NODES_ALL) if distributed else persons
         p = graph.NodeBitmap(sess, 0, n).add_scan(all_persons, "id")
-        matched = graph.two_hop_count(sess, [full], p, p, p)
+        matched = graph.two_hop_count(sess, [whole], p, p, p)
         # the undirected modes' bindings: the undirected count(*) (its own run's answer when und_count ran, else
         # the oracle fixture), so their value is undirected bindings / s, not the directed match's
         fxu0 = fixture(f"c3u_s{scale}") or {}
         und_matched = results["und_count"][1] if "und_count" in results else fxu0.get("count_star")
         answers = {m: r[1] for m, r in results.items()}
-        if shards != 1:
+        if not full:
+            check = "not checked (a plain run; --full checks every answer)"
+        elif shards != 1:
             check = f"not applicable (--shard-of {shards}: rank 0's shard alone)"
         elif fx is None:
             check = "no fixture for this scale"
@@ -621,7 +665,7 @@ def main():
             if matched != fx["count_star"]:
                 bad["count_star"] = matched
             check = "ok" if not bad else f"MISMATCH {bad} vs fixture {fx['count_distinct_c']} / {fx['count_star']}"
-        del full
+        del whole
 
     if rank == 0:
         head = modes[0]
@@ -642,10 +686,15 @@ def main():
                "degrees": m_local * 16 + n * 8}                  # read int64 pairs, inA + outC
         alg.update(kbytes)
         timed = {k: (c, ms) for k, (c, ms) in kt.items() if c > 0}
-        avg_ms = timed[dom][1] / timed[dom][0]  # the dominant launch over the timed steps
-        achieved = alg[dom] / (avg_ms * 1e-3) / 1e9
-        # committed PMC summaries are 1-GPU profiles of the whole table: they say nothing about a shard
-        traffic = pmc_traffic(KERNEL_SYMBOL[dom], "c3") if world == 1 and shards == 1 else None
+        roofline = None  # --full: the dominant kernel's timer
+        if dom is not None:
+            avg_ms = timed[dom][1] / timed[dom][0]  # the dominant launch over the timed steps
+            achieved = alg[dom] / (avg_ms * 1e-3) / 1e9
+            # committed PMC summaries are 1-GPU profiles of the whole table: they say nothing about a shard
+            traffic = pmc_traffic(KERNEL_SYMBOL[dom], "c3") if world == 1 and shards == 1 else None
+            roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                        "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel": KERNEL_SYMBOL[dom],
+                        "kernel_ms": avg_ms, "alg_bytes_per_launch": alg[dom]}
         query_alg = 2 * 24 * m_total + 3 * 8 * n  # SURVEY.md §8d C3 B_alg (whole query, all ranks)
         line = {
             "metric": METRIC,
@@ -669,9 +718,7 @@ def main():
                        "route": ("Planner(sg).run(query): lazy Table[T] plan -> fused two-hop kernels "
                                  f"({routed} plans routed on this rank)") if shards == 1 and
                        head in ("cold", "warm", "count") else "explicit phased kernel calls"},
-            "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "kernel": KERNEL_SYMBOL[dom],
-                         "kernel_ms": avg_ms, "alg_bytes_per_launch": alg[dom]},
+            "roofline": roofline,
             "query": {MODE_QUERY.get(head, (None, "count_distinct_c"))[1]: res, "matched_rows": rows_of(head),
                       "check_vs_fixture": check,  # tests/golden/rmat_full.json (oracle closed form)
                       "alg_bytes_query": query_alg,
@@ -679,7 +726,8 @@ def main():
                       "query_frac_of_peak": query_alg / sec / 1e9 / (HBM_PEAK_GBS * world),
                       "kernel_ms": {k: v[1] / v[0] for k, v in timed.items()},
                       "kernel_ms_from": (f"{dom}: the timed steps (its timer alone); the others: "
-                                         f"{PROFILED_STEPS} untimed steps with every timer"),
+                                         f"{PROFILED_STEPS} untimed steps with every timer") if dom is not None
+                      else "not measured (a plain run; --full times the kernels)",
                       "rels_local_rank0": m_local, "ingest_s": ingest_s},
         }
         if head in plan_ms:  # planning outside the timed region, reported beside it
@@ -724,7 +772,10 @@ def main():
                                          f"(CAPSMI_SERIAL_LOCK): a rank's busy ms per step is its share on a device of "
                                          f"its own, collectives excluded; ms_per_step is NOT a multi-GPU time",
                                  "busy_ms_per_rank": busy}
-        line["cpu_baseline"] = cpu_baseline(scale, ef) if (not args.no_cpu_baseline and world == 1) else None
+        if args.dump_outputs:  # the head mode's answer of its last timed step: the query's one-row result column
+            dump_outputs(args.dump_outputs, {MODE_QUERY.get(head, (None, "count_distinct_c"))[1]: [res]})
+        want_cpu = full and not args.no_cpu_baseline and world == 1
+        line["cpu_baseline"] = cpu_baseline(scale, ef) if want_cpu else None
         print(json.dumps(line), flush=True)
         if check is not None and check.startswith("MISMATCH"):
             sys.exit(f"bench: result differs from the oracle fixture: {check}")
@@ -934,15 +985,19 @@ def run_single(args):
                     b_[k] = b.value / c.value  # per launch
         return t, b_
     # every timer over a few untimed steps: the per-kernel breakdown and the dominant kernel; the timed steps
-    # then bracket only the dominant launch (each timer's two event records leave the device idle a few us)
-    _lib.call("capsmi_session_set_profiling", sess.handle, 1)
-    read_timers()  # reset
-    for _ in range(PROFILED_STEPS):
-        step()
-    kt, kbytes = read_timers()
-    ranked = [k for k in kt if k != "varlen_4"]  # (the four-hop phase: several kernels, no single roofline)
-    dom = max(ranked, key=lambda k: kt[k][1]) if ranked else None
-    _lib.call("capsmi_session_set_profiling_names", sess.handle, dom.encode() if dom else None)
+    # then bracket only the dominant launch (each timer's two event records leave the device idle a few us).
+    # (--full; a plain run keeps every timer off and reports no per-kernel figure)
+    full = args.full
+    kt, kbytes, dom = {}, {}, None
+    if full:
+        _lib.call("capsmi_session_set_profiling", sess.handle, 1)
+        read_timers()  # reset
+        for _ in range(PROFILED_STEPS):
+            step()
+        kt, kbytes = read_timers()
+        ranked = [k for k in kt if k != "varlen_4"]  # (the four-hop phase: several kernels, no single roofline)
+        dom = max(ranked, key=lambda k: kt[k][1]) if ranked else None
+        _lib.call("capsmi_session_set_profiling_names", sess.handle, dom.encode() if dom else None)
     plan_ms = None
     if route != "direct" and not args.plan_in_step:  # as the C3 modes: each timed step executes its own
         tp = time.perf_counter()                     # plan, built before the timed region (timed apart)
@@ -951,7 +1006,8 @@ def run_single(args):
         inner_step = lambda: run_plan(queue.pop(0))  # noqa: E731 (each plan executed once, then dropped)
     if gate is not None:
         gate.busy = 0.0
-    read_timers()  # reset
+    if full:
+        read_timers()  # reset
     if dw:
         dist.barrier()
     torch.cuda.synchronize()
@@ -966,12 +1022,13 @@ def run_single(args):
         tt = torch.tensor([sec], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         sec = float(tt.item())
-    kt_dom, kb_dom = read_timers()  # the dominant launch over the timed steps
+    kt_dom, kb_dom = read_timers() if full else ({}, {})  # the dominant launch over the timed steps
     kt.update(kt_dom)
     kbytes.update(kb_dom)
     steps_of = {k: (args.steps if k in kt_dom else PROFILED_STEPS) for k in kt}
-    _lib.call("capsmi_session_set_profiling", sess.handle, 0)
-    _lib.call("capsmi_session_set_profiling_names", sess.handle, None)
+    if full:
+        _lib.call("capsmi_session_set_profiling", sess.handle, 0)
+        _lib.call("capsmi_session_set_profiling_names", sess.handle, None)
     check = None
     if wl == "c5":
         cnt_col = cache.get("c5_cols", ["id", "count"])[1]
@@ -980,22 +1037,39 @@ def run_single(args):
             t = torch.tensor([res], dtype=torch.int64, device="cuda")
             dist.all_reduce(t)
             res = int(t.item())
-            if rank == 0:
-                full = graph.rmat_rels(sess, scale, 0, m, probs, 42)
+            if full and rank == 0:
+                whole = graph.rmat_rels(sess, scale, 0, m, probs, 42)
                 ok = graph.NodeBitmap(sess, 0, n).add_scan(graph.rmat_nodes(sess, scale, graph.NODES_ALL, 42), "id")
-                ref = int(graph.var_length_count(sess, [full], ok, ok, 1, 3).column("count").values.sum())
+                ref = int(graph.var_length_count(sess, [whole], ok, ok, 1, 3).column("count").values.sum())
                 check = "ok" if ref == res else f"MISMATCH {res} vs unsharded {ref}"
-                del full
-    if wl == "c2" and world > 1 and rank == 0:  # the whole table on one device gives the same row count
-        full = graph.rmat_rels(sess, scale, 0, m, probs, 42)
+                del whole
+    if full and wl == "c2" and world > 1 and rank == 0:  # the whole table on one device gives the same row count
+        whole = graph.rmat_rels(sess, scale, 0, m, probs, 42)
         a_ok = graph.NodeBitmap(sess, 0, n).add_scan(nodes, "id", pred)
         b_ok = graph.NodeBitmap(sess, 0, n).add_scan(nodes, "id")
-        ref = graph.expand_filter(sess, full, a_ok, b_ok, ["source", "target"], ["a", "b"]).size
+        ref = graph.expand_filter(sess, whole, a_ok, b_ok, ["source", "target"], ["a", "b"]).size
         check = "ok" if ref == res else f"MISMATCH {res} vs unsharded {ref}"
-        del full
-    # every line checks its answer against the committed oracle fixture (tests/golden/rmat_full.json)
+        del whole
+    if args.dump_outputs and rank == 0:  # what the last timed step returned (this rank's rows where they stay
+        cols = {"c2": cache.get("outs", ["a", "b"]), "c5": cache.get("c5_cols", ["id", "count"])}.get(wl)  # sharded)
+        if cols is None:  # C4: the one-row count(*)
+            dump_outputs(args.dump_outputs, {"count_star": [res]})
+        else:  # the result table, its rows (which the kernels append in no fixed order) sorted by (first, second);
+            c0, c1 = (out.column(c).values for c in cols)  # the files named after the query's return items
+            if len(c0) and min(c0.min(), c1.min()) >= 0 and max(c0.max(), c1.max()) < 1 << 31:
+                key = np.sort((c0 << 32) | c1)  # one sort of the packed pairs (C2's 7e7 rows: seconds, not tens)
+                c0, c1 = key >> 32, key & 0xFFFFFFFF
+            else:
+                order = np.lexsort((c1, c0))
+                c0, c1 = c0[order], c1[order]
+            names = ("a", "b") if wl == "c2" else ("id", "count")
+            dump_outputs(args.dump_outputs, {names[0]: c0, names[1]: c1})
+            del c0, c1
+    # --full: every line checks its answer against the committed oracle fixture (tests/golden/rmat_full.json)
     fx = fixture(f"{wl}_s{scale}" if up == 3 else f"{wl}u{up}_s{scale}")  # c5u4_*: the *1..4 answers
-    if fx is None or (world > 1 and wl == "c2"):
+    if not full:
+        fcheck = "not checked (a plain run; --full checks the answer)"
+    elif fx is None or (world > 1 and wl == "c2"):
         fcheck = "no fixture for this scale" if fx is None else "rows only (output stays partitioned)"
         if fx is not None and wl == "c2":
             fcheck = "ok" if res == fx["rows"] else f"MISMATCH rows {res} vs fixture {fx['rows']}"
@@ -1040,7 +1114,8 @@ def run_single(args):
                   "query_frac_of_peak": b_alg / sec / 1e9 / HBM_PEAK_GBS,
                   "kernel_ms": {k: v[1] / v[0] for k, v in kt.items()},
                   "kernel_ms_from": (f"{dom}: the timed steps (its timer alone); the others: {PROFILED_STEPS} "
-                                     "untimed steps with every timer")},
+                                     "untimed steps with every timer") if full
+                  else "not measured (a plain run; --full times the kernels)"},
     }
     if world > 1:  # every rank's timed phases (ms per step): the balance of the shares
         kr = torch.zeros(world, len(kernels), dtype=torch.float64, device="cuda")
@@ -1106,7 +1181,7 @@ def run_single(args):
     line["query"]["check_vs_fixture"] = fcheck
     if check is not None or (world > 1 and wl in ("c2", "c5")):
         line["query"]["check_vs_unsharded"] = check
-    line["cpu_baseline"] = None if (args.no_cpu_baseline or world > 1) else cpu_baseline_single(
+    line["cpu_baseline"] = None if (not full or args.no_cpu_baseline or world > 1) else cpu_baseline_single(
         wl, cpu_scale, ef, probs, scale, up)
     if rank == 0:
         print(json.dumps(line), flush=True)

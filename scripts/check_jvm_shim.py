@@ -1,21 +1,21 @@
 """Static check of the JVM shim against the reference's Table contract.
 
 jvm/src/main/scala/org/opencypher/capsmi/GpuTable.scala is never compiled here (no JVM in this image).  This
-test reads the reference's trait sources as text -- okapi-relational/.../api/table/Table.scala:43-176 and
+check reads the reference's trait sources as text -- okapi-relational/.../api/table/Table.scala:43-176 and
 okapi-api/.../api/table/CypherTable.scala:41-68 -- extracts every member's name, parameter lists (types,
 implicit-ness, varargs; parameter names and default values ignored) and result type with `T` read as
 GpuTable, and checks that GpuTable overrides every abstract member with the same lists and result, and that
-every member it does override matches the trait's.  It runs in the build container only: /root/reference is
-not on the GPU box (the test is then skipped)."""
+every member it does override matches the trait's.  The trait sources are the reference's and are not part
+of this repository, so this is a tool, not a test of the suite:
+
+    python scripts/check_jvm_shim.py REFERENCE_CHECKOUT   (exit 0: the shim matches)"""
 import os
 import re
-
-import pytest
+import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
-TABLE = os.path.join(REF, "okapi-relational/src/main/scala/org/opencypher/okapi/relational/api/table/Table.scala")
-CYPHER_TABLE = os.path.join(REF, "okapi-api/src/main/scala/org/opencypher/okapi/api/table/CypherTable.scala")
+TABLE = "okapi-relational/src/main/scala/org/opencypher/okapi/relational/api/table/Table.scala"
+CYPHER_TABLE = "okapi-api/src/main/scala/org/opencypher/okapi/api/table/CypherTable.scala"
 SHIM = os.path.join(ROOT, "jvm/src/main/scala/org/opencypher/capsmi/GpuTable.scala")
 
 
@@ -109,10 +109,9 @@ def members(path, trait=None, overrides_only=False, self_type=True):
     return out
 
 
-@pytest.mark.skipif(not os.path.exists(TABLE), reason="the reference is only in the build container")
-def test_gpu_table_overrides_every_table_member():
-    trait = members(TABLE, "Table")
-    trait.update(members(CYPHER_TABLE, "CypherTable"))
+def check_gpu_table_overrides_every_table_member(ref):
+    trait = members(os.path.join(ref, TABLE), "Table")
+    trait.update(members(os.path.join(ref, CYPHER_TABLE), "CypherTable"))
     shim = members(SHIM, overrides_only=True, self_type=False)
     assert ("join", ("GpuTable,JoinType,(String,String)*",)) in trait  # the parser read Table.scala:88
     missing = [k for k, (_, abstract) in trait.items() if abstract and k not in shim]
@@ -125,3 +124,10 @@ def test_gpu_table_overrides_every_table_member():
             continue  # not a Table / CypherTable member (e.g. a records-level override)
         assert k in trait, f"GpuTable.{k[0]}{k[1]} matches no parameter lists of {by_name[k[0]]}"
         assert res == trait[k][0], f"GpuTable.{k[0]} returns {res}, the trait {trait[k][0]}"
+    return len(shim)
+
+
+if __name__ == "__main__":
+    if len(sys.argv) != 2:
+        sys.exit(__doc__)
+    print(f"GpuTable.scala: {check_gpu_table_overrides_every_table_member(sys.argv[1])} overrides match the traits")

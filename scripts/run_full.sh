@@ -5,7 +5,8 @@ cd "$GRAFT_REPO_ROOT"
 export TMPDIR=/tmp
 T=${1:-full}
 W=${2:-c3}
-B="python3 bench.py --workload $W --steps 3 --warmup 1 --modes ${PMC_MODES:-cold} --no-cpu-baseline"
+B="python3 bench.py --full --workload $W --steps 3 --warmup 1 --modes ${PMC_MODES:-cold} --no-cpu-baseline"
+BENCH_MODES="--full ${BENCH_MODES:-}"  # the bench log below: every mode, the checks, the CPU baseline
 : > gpurun_out/${T}_status.txt
 timeout -k 10 400 python3 bench.py --workload $W --steps 5 --warmup 2 ${BENCH_MODES:-} > gpurun_out/${T}_bench.log 2>&1 || exit $?
 echo bench ok >> gpurun_out/${T}_status.txt

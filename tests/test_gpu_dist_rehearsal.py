@@ -26,7 +26,8 @@ def _run(wl, scale, n=2):
     env = dict(os.environ, CAPSMI_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",
            "--master-addr", "127.0.0.1", f"--master-port={_port()}", os.path.join(ROOT, "bench.py"), "--gpus", str(n),
-           "--workload", wl, "--scale", str(scale), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--workload", wl, "--scale", str(scale), "--steps", "2", "--warmup", "1", "--full",
+           "--no-cpu-baseline"]  # --full: every mode, the checks against the fixture and the unsharded table
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

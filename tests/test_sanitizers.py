@@ -25,10 +25,24 @@ def _build(cmd, tmp_path):
     assert p.returncode == 0, p.stderr[-3000:]
 
 
+def _fixed_layout():
+    """In the child, before exec: address-space randomisation off for that process (personality
+    ADDR_NO_RANDOMIZE, what `setarch -R` sets).  ThreadSanitizer's runtime maps its shadow at fixed addresses
+    and, on kernels that randomise mappings over more than 28 bits, now and then ends at start-up with
+    "FATAL: ThreadSanitizer: unexpected memory mapping" before any code under test has run (AddressSanitizer's
+    has the same weakness).  Where the call is refused the process runs with the default layout."""
+    import ctypes
+    libc = ctypes.CDLL(None, use_errno=True)
+    cur = libc.personality(0xFFFFFFFF)
+    if cur != -1:
+        libc.personality(cur | 0x0040000)
+
+
 def _run(exe, *args, timeout=240):
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1",
                TSAN_OPTIONS="halt_on_error=1", OMP_NUM_THREADS="4")
-    p = subprocess.run([exe, *args], capture_output=True, text=True, timeout=timeout, env=env)
+    p = subprocess.run([exe, *args], capture_output=True, text=True, timeout=timeout, env=env,
+                       preexec_fn=_fixed_layout)
     assert p.returncode == 0, (p.stdout[-2000:], p.stderr[-6000:])
     assert "ERROR: AddressSanitizer" not in p.stderr and "runtime error" not in p.stderr, p.stderr[-6000:]
     assert "WARNING: ThreadSanitizer" not in p.stderr, p.stderr[-6000:]
