@@ -497,6 +497,9 @@ bool apply(Config& c, const std::string& name, const char* v) {
     } else if (name == "CAPSMI_PAIRS") {
         if (!parse_choice(v, {"auto", "packed", "uint2"}, k)) return false;
         c.pairs = k;
+    } else if (name == "CAPSMI_HOP2") {
+        if (!parse_choice(v, {"auto", "pool", "cells"}, k)) return false;
+        c.hop2 = k;
     } else if (name == "CAPSMI_TRI_BUILD") {
         if (!parse_choice(v, {"direct", "sorted"}, k)) return false;
         c.tri_sorted_build = k == 1;
@@ -538,7 +541,8 @@ const std::pair<const char*, const char*> kKnobs[] = {
     {"CAPSMI_GROUPED", "sets"},      {"CAPSMI_PAIRS", "auto"},       {"CAPSMI_TRI_BUILD", "direct"},
     {"CAPSMI_TRI_DEG_SAMPLE", "0"},  {"CAPSMI_TRI_SPLIT", "1"},      {"CAPSMI_TRI_VMODE_T", "256"},
     {"CAPSMI_UND", "part"},          {"CAPSMI_VL_BITS", "8"},        {"CAPSMI_VL_SUBLOG", "-1"},
-    {"CAPSMI_VL_F2", "0"},           {"CAPSMI_COLL_CHUNK", "67108864"}, {"CAPSMI_INGEST_THREADS", "0"}};
+    {"CAPSMI_VL_F2", "0"},           {"CAPSMI_COLL_CHUNK", "67108864"}, {"CAPSMI_INGEST_THREADS", "0"},
+    {"CAPSMI_HOP2", "auto"}};
 }  // namespace
 
 Config config_from_env() {
@@ -1603,7 +1607,7 @@ static void build_part(capsmi_session* s, int32_t nrels, capsmi_table* const* re
 }
 
 // hop 1 on a partitioned layout into X1 (= M | S1) and X2 (= M | S2); S1 scratch
-static void part_mid(capsmi_session* s, const RelPart& rp, const capsmi_bitmap* a, const capsmi_bitmap* b, uint32_t* X1,
+static void part_mid(capsmi_session* s, RelPart& rp, const capsmi_bitmap* a, const capsmi_bitmap* b, uint32_t* X1,
                      uint32_t* X2, uint32_t* S1) {
     const int64_t nw = b->nwords;
     HIP_CHECK(hipMemsetAsync(X1, 0, sizeof(uint32_t) * nw, s->stream));
@@ -2009,7 +2013,7 @@ capsmi_status capsmi_relpart_digest(const capsmi_relpart* p, int64_t* ncells, in
         need(sums, "sums");
         need(misplaced, "misplaced");
         use_device(p->sess);
-        relpart_digest(p->sess, p->rp, counts, sums, misplaced);
+        relpart_digest(p->sess, const_cast<capsmi_relpart*>(p)->rp, counts, sums, misplaced);
     }
     API_END
 }
@@ -2033,7 +2037,7 @@ capsmi_status capsmi_two_hop_mark_mid_part(capsmi_session* s, const capsmi_relpa
     check_bitmap(a_ok, "a_ok");
     check_bitmap(b_ok, "b_ok");
     use_device(s);
-    part_mid(s, p->rp, a_ok, b_ok, mid_words, mid_words + b_ok->nwords, scratch_words);
+    part_mid(s, const_cast<capsmi_relpart*>(p)->rp, a_ok, b_ok, mid_words, mid_words + b_ok->nwords, scratch_words);
     API_END
 }
 
@@ -2049,7 +2053,7 @@ capsmi_status capsmi_two_hop_mark_dst_part(capsmi_session* s, const capsmi_relpa
     REQUIRE(b_ok->lo == c_ok->lo && b_ok->hi == c_ok->hi, CAPSMI_ERR_UNSUPPORTED, "b and c scans need one id domain");
     use_device(s);
     HIP_CHECK(hipMemsetAsync(dst_words, 0, sizeof(uint32_t) * c_ok->nwords, s->stream));
-    relpart_hop2(s, p->rp, c_ok, mid_words, mid_words + b_ok->nwords, dst_words);
+    relpart_hop2(s, const_cast<capsmi_relpart*>(p)->rp, c_ok, mid_words, mid_words + b_ok->nwords, dst_words);
     API_END
 }
 
@@ -2068,9 +2072,9 @@ capsmi_status capsmi_two_hop_count_distinct_part(capsmi_session* s, const capsmi
     const int64_t nw = b_ok->nwords > 0 ? b_ok->nwords : 1;
     Buf x = dev_alloc(sizeof(uint32_t) * nw * 4, s);
     uint32_t* X1 = P<uint32_t>(x);
-    part_mid(s, p->rp, a_ok, b_ok, X1, X1 + nw, X1 + 2 * nw);
+    part_mid(s, const_cast<capsmi_relpart*>(p)->rp, a_ok, b_ok, X1, X1 + nw, X1 + 2 * nw);
     HIP_CHECK(hipMemsetAsync(X1 + 3 * nw, 0, sizeof(uint32_t) * nw, s->stream));
-    relpart_hop2(s, p->rp, c_ok, X1, X1 + nw, X1 + 3 * nw);
+    relpart_hop2(s, const_cast<capsmi_relpart*>(p)->rp, c_ok, X1, X1 + nw, X1 + 3 * nw);
     *out_distinct = words_popcount(s, X1 + 3 * nw, 0, c_ok->nwords);
     API_END
 }

@@ -141,6 +141,8 @@ struct Config {
                                   //   for full node filters
     bool grouped_keys = false;    // CAPSMI_GROUPED = keys: grouped count(DISTINCT c) by the per-binding key sort
     int pairs = 0;                // CAPSMI_PAIRS = packed | uint2 (1 | 2): force the cached layout's pair form
+    int hop2 = 0;                 // CAPSMI_HOP2 = pool | cells (1 | 2): force the cold 2-hop's form for a full a_ok, both hops
+                                  //   over the pass-1 pool or pass 2 + the cell hops (auto: the pool up to 2^26 ids, k_part.hip)
     bool tri_sorted_build = false;  // CAPSMI_TRI_BUILD = sorted: the sort-oriented trigraph build (above 2^24 ids)
     int tri_deg_sample = 0;       // CAPSMI_TRI_DEG_SAMPLE: 1 in k relationships for the degree order (0: auto)
     bool tri_split = true;        // CAPSMI_TRI_SPLIT = 0: the combined (not direction-split) triangle walks
@@ -452,8 +454,28 @@ struct PartLayout {
     int tbits;       // target slice = 2^tbits ids (19 for the 2-hop layout)
     int packed = 0;  // 2-hop layout: 5-byte cell-relative pairs (sbits + tbits <= 40), else uint2
 };
+// Pass 1 of the partition plus chunk ordering and the block-balanced segment split (k_part.hip):
+// relationships grouped by bucket = (y >> L.tbits) of their packed (x, y) = (source - lo, target - lo)
+// pair, in chunks of kCh pairs; with `swap` the pair is (target, source) and buckets follow the
+// source.  Blocks of a consumer kernel launched with g2 blocks walk segments via part::seg_of.
+struct ChunkPart {
+    PartLayout L;
+    Buf pool, meta, chist, jbuf;
+    int64_t pool_chunks = 0, npool = 1, mtot = 0, g2 = 1;
+    int64_t* jst = nullptr;      // nt + 1 chunk offsets per bucket in `order`
+    int64_t* segbase = nullptr;  // g2 + 1
+    int* ja = nullptr;           // first bucket per block
+    uint32_t* order = nullptr;   // used chunks grouped by bucket
+};
 struct RelPart {
     PartLayout L;
+    // The build has two stages.  Stage 1 (pass 1) leaves the chunk partition `cp`: pairs grouped by target
+    // slice.  Stage 2 (relpart_cells: pass 2) turns it into the cells below and drops the pool.  A cold 2-hop
+    // with a full a_ok runs both hops over the pool and never needs stage 2 (k_pool_hop1 / k_pool_hop2);
+    // every reader of `pairs` / `boff` completes the cells first (relpart_cells is a no-op once built).
+    ChunkPart cp;
+    bool cells = false;
+    int sel = -1;   // hop-2 form: -1 none ran yet, 0 the pool (no cells built), 1 the cells
     // per kept relationship, grouped by cell: uint2 (source - lo, target - lo), or when L.packed the
     // cell-relative key k = (source low sbits) << tbits | (target low tbits) as two arrays, the low
     // word u32[cap] and the high byte u8[cap] behind it
@@ -464,7 +486,7 @@ struct RelPart {
     int64_t rows = 0;  // relationships offered to the build (>= kept)
 };
 int64_t relpart_kept(capsmi_session* s, RelPart& rp);
-void relpart_digest(capsmi_session* s, const RelPart& rp, int64_t* counts, uint64_t* sums, int64_t* misplaced);
+void relpart_digest(capsmi_session* s, RelPart& rp, int64_t* counts, uint64_t* sums, int64_t* misplaced);
 // hop 1 of a 2-hop run while the layout is built: M(t) |= a_ok(s) for s != t, a_ok self-loops ->
 // S1 (first) / S2 (second), target filter b_ok; outputs zeroed by the caller
 struct RelPartHop1 {
@@ -475,9 +497,11 @@ struct RelPartHop1 {
 // unpacked: keep 8-byte pairs whatever the domain (a layout walked by kernels that read uint2 pairs only)
 void relpart_build(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms, int nt,
                    int64_t lo, int64_t hi, RelPart& rp, const RelPartHop1* h1 = nullptr, bool unpacked = false);
-void relpart_hop1(capsmi_session* s, const RelPart& rp, const capsmi_bitmap* a, const capsmi_bitmap* b, uint32_t* M,
+// stage 2 of the build on a handle that kept its pool (no-op when the cells are there)
+void relpart_cells(capsmi_session* s, RelPart& rp);
+void relpart_hop1(capsmi_session* s, RelPart& rp, const capsmi_bitmap* a, const capsmi_bitmap* b, uint32_t* M,
                   uint32_t* S1, uint32_t* S2);
-void relpart_hop2(capsmi_session* s, const RelPart& rp, const capsmi_bitmap* c, const uint32_t* X1, const uint32_t* X2,
+void relpart_hop2(capsmi_session* s, RelPart& rp, const capsmi_bitmap* c, const uint32_t* X1, const uint32_t* X2,
                   uint32_t* C);
 
 // fused cyclic triangle count (k_tri.hip): the oriented simple graph with multiplicities

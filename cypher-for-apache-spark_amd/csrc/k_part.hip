@@ -16,7 +16,9 @@
 // Build: pass 0 counts cells (LDS histogram), pass 1 scatters (source, target) int64 pairs into
 // target slices as packed uint32 pairs, pass 2 scatters each target slice into its source cells.
 // Both scatters stage an 8192-relationship tile in LDS grouped by bucket, so the HBM writes are
-// runs of whole cache lines rather than 8-byte scatters.
+// runs of whole cache lines rather than 8-byte scatters.  A cold 2-hop with a full a_ok over at most
+// 2^26 ids stops after pass 1 and runs both hops over the pass-1 pool (k_pool_hop1 / k_pool_hop2);
+// pass 2 is then the second stage of the build (relpart_cells), run only when something reads the cells.
 #include <map>
 #include <mutex>
 #include "part_common.h"
@@ -1029,6 +1031,97 @@ __global__ void __launch_bounds__(kBlock) k_hop_2d(PairOut pairs, const int64_t*
     flush_slice(tl, out, cur_j, gwords, tmask);
 }
 
+// ---- both hops over the pass-1 pool (no pass 2) -------------------------------------------------------
+// The pool is grouped by target slice, so a block keeps the slice's target bitmap in LDS while it walks its
+// share of the slice's chunks (part::walk_chunks_n); several blocks may share a slice, so the flush ORs.
+constexpr int kPoolBlock = 1024;
+
+// move the LDS slice j out through `mask` and clear it
+__device__ __forceinline__ void pool_flush(uint32_t* tl, uint32_t* g, int j, int64_t gwords, BitV mask) {
+    const int64_t w0 = (int64_t)j * kSliceWords;
+    for (int i = threadIdx.x; i < kSliceWords; i += kPoolBlock) {
+        uint32_t v = tl[i];
+        tl[i] = 0;
+        const int64_t gw = w0 + i;
+        if (!v || gw >= gwords) continue;
+        if (!mask.full) v &= mask.w[gw];
+        if (v) atomicOr(&g[gw], v);
+    }
+}
+
+// Hop 1 for a full a_ok: M(t) for s != t in LDS, flushed through b_ok; self-loops -> S1 / S2 as in
+// k_scatter_s2<true>.
+__global__ void __launch_bounds__(kPoolBlock) k_pool_hop1(ChunkWalk cw, BitV tmask, uint32_t* __restrict__ M,
+                                                          uint32_t* __restrict__ S1, uint32_t* __restrict__ S2,
+                                                          int64_t gwords) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t tl[];
+    for (int k = threadIdx.x; k < kSliceWords; k += kPoolBlock) tl[k] = 0;
+    __syncthreads();
+    walk_chunks_n<kPoolBlock>(
+        cw,
+        [&](const uint2 (&pr)[kWalkItems], uint32_t valid, int j) {
+            const uint32_t tbase = (uint32_t)j << kSliceBits;
+#pragma unroll
+            for (int k = 0; k < kWalkItems; ++k) {
+                if (!((valid >> k) & 1u)) continue;
+                const uint32_t s = pr[k].x, t = pr[k].y;
+                if (s != t) {
+                    lds_set(tl, t - tbase);
+                } else if (tmask.full || gbit(tmask.w, t)) {  // rare: self-loops
+                    const uint32_t bit = 1u << (t & 31);
+                    const uint32_t old = atomicOr(&S1[t >> 5], bit);
+                    if (old & bit) atomicOr(&S2[t >> 5], bit);
+                }
+            }
+        },
+        [&](int j) { pool_flush(tl, M, j, gwords, tmask); });
+}
+
+// Hop 2: C(t) |= X1(s) for s != t, X2(s) for s == t, with the C slice in LDS.  A pair whose target bit is
+// already set needs no X read (the result is an OR, so skipping is exact in any order); targets outside c_ok
+// are preset so their pairs skip too, and the flush masks them off again.  A lane tests its step's targets
+// first, then issues the X1 gathers of the unset ones together (buffer loads: a lane that needs none gives an
+// offset past the bitmap, which reads as zero without a memory request) and only then sets bits.
+__global__ void __launch_bounds__(kPoolBlock, 8) k_pool_hop2(ChunkWalk cw, const uint32_t* __restrict__ X1,
+                                                             const uint32_t* __restrict__ X2, BitV cmask,
+                                                             uint32_t* __restrict__ C, int64_t gwords) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t tl[];
+    for (int k = threadIdx.x; k < kSliceWords; k += kPoolBlock) tl[k] = 0;
+    __syncthreads();
+    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<uint32_t*>(X1), (short)0, (int)(gwords * (int64_t)sizeof(uint32_t)), 0x00020000);
+    walk_chunks_n<kPoolBlock>(
+        cw,
+        [&](const uint2 (&pr)[kWalkItems], uint32_t valid, int j) {
+            const uint32_t tbase = (uint32_t)j << kSliceBits;
+            uint32_t need = 0;
+#pragma unroll
+            for (int k = 0; k < kWalkItems; ++k) {
+                const uint32_t r = (pr[k].y - tbase) & ((1u << kSliceBits) - 1u);
+                if (((valid >> k) & 1u) && !((tl[r >> 5] >> (r & 31)) & 1u)) need |= 1u << k;
+            }
+            uint32_t xw[kWalkItems];
+#pragma unroll
+            for (int k = 0; k < kWalkItems; ++k) {
+                const bool ld = ((need >> k) & 1u) && pr[k].x != pr[k].y;
+                xw[k] = __builtin_amdgcn_raw_buffer_load_b32(xr, ld ? (pr[k].x >> 5) * 4u : 0xFFFFFFF0u, 0, 0);
+            }
+#pragma unroll
+            for (int k = 0; k < kWalkItems; ++k) {
+                if (!((need >> k) & 1u)) continue;
+                const uint32_t s = pr[k].x, t = pr[k].y;
+                const bool ok = s != t ? ((xw[k] >> (s & 31)) & 1u) != 0 : gbit(X2, s);  // self-loops: rare
+                if (ok) lds_set(tl, t - tbase);
+            }
+        },
+        [&](int j) { pool_flush(tl, C, j, gwords, cmask); },
+        [&](int j) {
+            if (cmask.full) return;
+            const int64_t w0 = (int64_t)j * kSliceWords;
+            for (int i = threadIdx.x; i < kSliceWords; i += kPoolBlock)
+                tl[i] = w0 + i < gwords ? ~cmask.w[w0 + i] : 0xFFFFFFFFu;
+        });
+}
 
 }  // namespace part
 
@@ -1197,6 +1290,34 @@ void chunk_order(capsmi_session* s, int nt, int64_t pool_chunks, int64_t g2_want
     cp.order = order;
 }
 
+static part::ChunkWalk chunk_walk(const ChunkPart& cp) {
+    return part::ChunkWalk{P<uint2>(cp.pool), P<unsigned long long>(cp.meta), cp.order, cp.jst, cp.segbase, cp.ja, cp.L.nt};
+}
+
+// Grid of the pool hops: one 1024-lane block per CU (64 KiB of LDS), fewer for small tables so that a
+// block's share stays at 16 chunks or more.  More blocks would hide the X gathers' latency but cut the slices
+// into more shares, each of which meets a target for the first time once more (scripts/pool_reads_model.py:
+// 0.05 X reads per relationship at 256 shares of C3, 0.08 at 512), and every share pays a 64 KiB flush per
+// slice it touches.  Measured at C3 (plain bench, alternating libraries on one box): two blocks per CU 8.89 /
+// 8.99 ms per step, one 8.70 / 8.67 ms.
+constexpr int kPoolBlocksPerCU = 1;
+constexpr int64_t kPoolMinShare = 16 * (int64_t)part::kCh;  // pairs
+static unsigned pool_grid(const capsmi_session* s, const ChunkPart& cp) {
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((int64_t)s->num_cus * kPoolBlocksPerCU, cp.mtot / kPoolMinShare));
+}
+
+// Where the pool hops run (CAPSMI_HOP2=auto): domains of at most 2^26 ids (2^19-id source slices, X = 8 MiB).
+// Measured on tables of uniform in-degree d (profiles/r07_pool_sweep.json): there the pool's hops beat or tie
+// pass 2 + k_hop_2d at every d from 32 down to 1, where no pair finds its target set and hop 2 reads X once per
+// relationship (2^26 relationships: 0.80 against 0.82 ms after pass 1; d >= 4, 2^28 relationships: 1.36 against
+// 1.52 ms).  Over 2^28 ids (X = 32 MiB) the pool's hop 2 lost at d = 1, 2 and 4 (4.38 / 3.35 / 3.09 ms against
+// 3.03 ms for pass 2 + k_hop_2d), so larger domains keep the cells path.  A choice per build from a count of
+// hop 1's first encounters (one X read each) was built and removed: below 2^26 ids it never chose the cells
+// rightly, above it never the pool.
+static bool pool_domain(const part::Layout& L) { return L.sbits == part::kSliceBits; }
+
+static void cells_build(capsmi_session* s, RelPart& rp, const RelPartHop1* h1);
+
 void relpart_build(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms, int nt,
                    int64_t lo, int64_t hi, RelPart& rp, const RelPartHop1* h1, bool unpacked) {
     REQUIRE(hi > lo && (uint64_t)(hi - lo) <= (uint64_t(1) << 30), CAPSMI_ERR_UNSUPPORTED,
@@ -1215,11 +1336,45 @@ void relpart_build(capsmi_session* s, const int64_t* const* srcs, const int64_t*
         REQUIRE(h1->a->lo == lo && h1->a->hi == hi && h1->b->lo == lo && h1->b->hi == hi, CAPSMI_ERR_UNSUPPORTED,
                 "partitioned 2-hop needs node scans over the layout's id domain");
 
-    const bool fuse = h1 && h1->a->full;
-    ChunkPart cp;
+    int64_t rows = 0;
+    for (int i = 0; i < nt; ++i) rows += std::max<int64_t>(ms[i], 0);
+    // a full a_ok: hop 1 needs no source test.  It then runs over the pool (k_pool_hop1) and the cells wait
+    // until something needs them; with CAPSMI_HOP2=cells it rides on pass 2 as before.
+    const bool full_a = h1 && h1->a->full;
+    const bool pool_hop = full_a && rows > 0 && (s->cfg.hop2 == 1 || (s->cfg.hop2 == 0 && pool_domain(L)));
+    const bool fuse = full_a && !pool_hop;
+    ChunkPart& cp = rp.cp;
     // (measured and removed in round 6: a 6-byte pass-1 pool, u32 + u16 arrays per chunk -- pass 1 5.26 ->
     // 5.58 ms, pass 2 + hop 1 3.76 -> 4.45 ms at C3; both passes are bound by their LDS / VALU phases)
     chunk_partition(s, srcs, dsts, ms, nt, false, L, (int64_t)s->num_cus * (fuse ? 1 : 2), cp);
+    rp.cells = false;
+    rp.sel = -1;
+    rp.kept = -1;  // known on the device (boff[ncells]); read only when asked (relpart_kept)
+    rp.rows = cp.mtot;
+    if (pool_hop) {
+        const size_t lds = sizeof(uint32_t) * kSliceWords;
+        allow_lds(k_pool_hop1, lds);
+        KernelTimer kt(s, "hop1");
+        hipLaunchKernelGGL(k_pool_hop1, dim3(pool_grid(s, cp)), dim3(kPoolBlock), lds, st, chunk_walk(cp),
+                           BitV{P<uint32_t>(h1->b->words), h1->b->full ? 1 : 0}, h1->M, h1->S1, h1->S2, h1->b->nwords);
+        HIP_CHECK(hipGetLastError());
+        return;
+    }
+    cells_build(s, rp, fuse ? h1 : nullptr);
+    if (h1 && !fuse) relpart_hop1(s, rp, h1->a, h1->b, h1->M, h1->S1, h1->S2);
+}
+
+void relpart_cells(capsmi_session* s, RelPart& rp) {
+    if (!rp.cells) cells_build(s, rp, nullptr);
+}
+
+// stage 2: the kept pool -> cells (pass 2; with h1, hop 1 for a full a_ok fused into it); the pool is dropped
+static void cells_build(capsmi_session* s, RelPart& rp, const RelPartHop1* h1) {
+    using namespace part;
+    hipStream_t st = s->stream;
+    const Layout& L = rp.L;
+    const bool fuse = h1 != nullptr;
+    ChunkPart& cp = rp.cp;
     const int64_t g2 = cp.g2, mtot = cp.mtot;
     const int64_t maxg = g2 + L.nt;  // segments <= blocks + slices
     int64_t* jst = cp.jst;
@@ -1255,9 +1410,9 @@ void relpart_build(capsmi_session* s, const int64_t* const* srcs, const int64_t*
                            order, jst, segbase, ja, psum, P<int64_t>(rp.boff), L, pair_out(rp), mtot, ho);
     }
     HIP_CHECK(hipGetLastError());
-    rp.kept = -1;  // known on the device (boff[ncells]); read only when asked (relpart_kept)
-    rp.rows = mtot;
-    if (h1 && !fuse) relpart_hop1(s, rp, h1->a, h1->b, h1->M, h1->S1, h1->S2);
+    rp.cells = true;
+    rp.sel = 1;
+    rp.cp = ChunkPart();  // the pool and its bookkeeping go back to the allocator (stream-ordered)
 }
 
 template <bool HOP1, bool SRC_FULL>
@@ -1278,11 +1433,12 @@ static void launch_hop(capsmi_session* s, const RelPart& rp, part::BitV sb, cons
     HIP_CHECK(hipGetLastError());
 }
 
-void relpart_hop1(capsmi_session* s, const RelPart& rp, const capsmi_bitmap* a, const capsmi_bitmap* b, uint32_t* M,
+void relpart_hop1(capsmi_session* s, RelPart& rp, const capsmi_bitmap* a, const capsmi_bitmap* b, uint32_t* M,
                   uint32_t* S1, uint32_t* S2) {
     REQUIRE(a->lo == rp.L.lo && a->hi == rp.L.hi && b->lo == rp.L.lo && b->hi == rp.L.hi, CAPSMI_ERR_UNSUPPORTED,
             "partitioned 2-hop needs node scans over the layout's id domain");
     if (rp.rows == 0) return;
+    relpart_cells(s, rp);
     const part::BitV av{P<uint32_t>(a->words), a->full ? 1 : 0}, bv{P<uint32_t>(b->words), b->full ? 1 : 0};
     KernelTimer kt(s, "hop1");
     if (a->full)
@@ -1291,12 +1447,29 @@ void relpart_hop1(capsmi_session* s, const RelPart& rp, const capsmi_bitmap* a, 
         launch_hop<true, false>(s, rp, av, nullptr, bv, M, S1, S2, b->nwords);
 }
 
-void relpart_hop2(capsmi_session* s, const RelPart& rp, const capsmi_bitmap* c, const uint32_t* X1, const uint32_t* X2,
+void relpart_hop2(capsmi_session* s, RelPart& rp, const capsmi_bitmap* c, const uint32_t* X1, const uint32_t* X2,
                   uint32_t* C) {
     REQUIRE(c->lo == rp.L.lo && c->hi == rp.L.hi, CAPSMI_ERR_UNSUPPORTED,
             "partitioned 2-hop needs node scans over the layout's id domain");
     if (rp.rows == 0) return;
     const part::BitV xv{X1, 0}, cv{P<uint32_t>(c->words), c->full ? 1 : 0};
+    if (!rp.cells) {
+        // a handle that ran hop 1 over its pool and has built no cells since: hop 2 walks the pool too
+        if (rp.sel < 0) rp.sel = 0;
+        if (rp.sel == 0) {
+            using namespace part;
+            const size_t lds = sizeof(uint32_t) * kSliceWords;
+            allow_lds(k_pool_hop2, lds);
+            KernelTimer kt(s, "hop2");
+            hipLaunchKernelGGL(k_pool_hop2, dim3(pool_grid(s, rp.cp)), dim3(kPoolBlock), lds, s->stream, chunk_walk(rp.cp),
+                               X1, X2, cv, C, c->nwords);
+            HIP_CHECK(hipGetLastError());
+            s->routes["hop2_pool"] += 1;
+            return;
+        }
+        relpart_cells(s, rp);
+    }
+    s->routes["hop2_cells"] += 1;
     KernelTimer kt(s, "hop2");
     launch_hop<false, false>(s, rp, xv, X2, cv, C, nullptr, nullptr, c->nwords);
 }
@@ -1325,7 +1498,8 @@ __global__ void __launch_bounds__(256) k_cell_digest(part::PairOut pairs, const 
     if (nb) atomicAdd(bad, nb);
 }
 
-void relpart_digest(capsmi_session* s, const RelPart& rp, int64_t* counts, uint64_t* sums, int64_t* misplaced) {
+void relpart_digest(capsmi_session* s, RelPart& rp, int64_t* counts, uint64_t* sums, int64_t* misplaced) {
+    relpart_cells(s, rp);
     hipStream_t st = s->stream;
     const int nc = rp.L.ncells;
     std::vector<int64_t> off(nc + 1, 0);
@@ -1348,6 +1522,7 @@ void relpart_digest(capsmi_session* s, const RelPart& rp, int64_t* counts, uint6
 }
 
 int64_t relpart_kept(capsmi_session* s, RelPart& rp) {
+    relpart_cells(s, rp);
     if (rp.kept < 0) rp.kept = rp.rows > 0 ? read_scalar(s, P<int64_t>(rp.boff) + rp.L.ncells) : 0;
     return rp.kept;
 }

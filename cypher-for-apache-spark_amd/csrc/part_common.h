@@ -338,19 +338,7 @@ __device__ __forceinline__ bool owns_slice(const ChunkWalk& cw, int j) {
 
 }  // namespace part
 
-// Pass 1 of the partition plus chunk ordering and the block-balanced segment split (k_part.hip):
-// relationships grouped by bucket = (y >> L.tbits) of their packed (x, y) = (source - lo, target - lo)
-// pair, in chunks of kCh pairs; with `swap` the pair is (target, source) and buckets follow the
-// source.  Blocks of a consumer kernel launched with g2 blocks walk segments via part::seg_of.
-struct ChunkPart {
-    part::Layout L;
-    Buf pool, meta, chist, jbuf;
-    int64_t pool_chunks = 0, npool = 1, mtot = 0, g2 = 1;
-    int64_t* jst = nullptr;      // nt + 1 chunk offsets per bucket in `order`
-    int64_t* segbase = nullptr;  // g2 + 1
-    int* ja = nullptr;           // first bucket per block
-    uint32_t* order = nullptr;   // used chunks grouped by bucket
-};
+// ChunkPart (capsmi_impl.h): pass 1 of the partition, the chunk ordering and the segment split
 void chunk_partition(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
                      int nt, bool swap, const part::Layout& L, int64_t g2, ChunkPart& cp);
 // the ordering half of chunk_partition for a pool another kernel filled (cp.meta: bucket | fill << 32)

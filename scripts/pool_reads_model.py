@@ -1,0 +1,81 @@
+"""CPU model of the X reads of the pool's hop 2 (csrc/k_part.hip k_pool_hop2) on the oracle's R-MAT graph.
+
+The pairs of one 2^19-id target slice are taken in ingest order and cut into block shares of `--share` pairs.
+A share starts with an empty C slice; its pairs go by in steps of `--step` pairs (512 = one wave step, 8192 =
+every wave of a block at once), and every pair of a step that finds its target unset at the start of the step
+reads X(source); the ones whose source passes set the target.  Printed per share size and step: X reads per
+relationship, the first encounters per relationship (distinct targets per share: what k_pool_hop1 counts as
+R_est, the reads' lower bound) and the model's count(DISTINCT c) against the oracle's closed form.
+
+The share of the GPU's grid at scale 26 (2^30 relationships): 4 Mi pairs at 256 blocks, 2 Mi at 512 (the grid
+chosen, two blocks per CU).  The model keeps the share size, not the block count, when run at a smaller scale.
+
+    python scripts/pool_reads_model.py --scale 22
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SLICE_BITS = 19
+
+
+def frontier(n, src, dst):
+    """X1 = M | (>= 1 self-loop), X2 = M | (>= 2 self-loops) with every node filter full"""
+    loop = src == dst
+    M = np.zeros(n, bool)
+    M[dst[~loop]] = True
+    selfc = np.bincount(dst[loop], minlength=n)
+    return M | (selfc >= 1), M | (selfc >= 2)
+
+
+def model(n, src, dst, share, step):
+    X1, X2 = frontier(n, src, dst)
+    ok = np.where(src == dst, X2[src], X1[src])
+    j = dst >> SLICE_BITS
+    order = np.argsort(j, kind="stable")  # ingest order within a slice
+    bounds = np.searchsorted(j[order], np.arange((n >> SLICE_BITS) + 2))
+    reads = first = 0
+    C_all = np.zeros(n, bool)
+    for a, b in zip(bounds[:-1], bounds[1:]):
+        for s0 in range(a, b, share):
+            idx = order[s0:min(s0 + share, b)]
+            t, p = dst[idx], ok[idx]
+            C = np.zeros(n, bool)  # only this slice's ids are touched
+            for k in range(0, len(t), step):
+                tt = t[k:k + step]
+                unset = ~C[tt]
+                reads += int(unset.sum())
+                C[tt[unset & p[k:k + step]]] = True
+            first += len(np.unique(t))
+            C_all |= C
+    return reads, first, int(C_all.sum())
+
+
+def main():
+    from oracle import cpu
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scale", type=int, default=22)
+    ap.add_argument("--edge-factor", type=int, default=16)
+    ap.add_argument("--shares", default="4194304,2097152")
+    ap.add_argument("--steps", default="512,8192")
+    args = ap.parse_args()
+    n, m = 1 << args.scale, args.edge_factor << args.scale
+    src, dst = cpu.rmat_edges(args.scale, 0, m)
+    X1, _ = frontier(n, src, dst)
+    _, want = cpu.two_hop_closed_form_mt(n, src, dst)
+    print(f"scale {args.scale}: {m} relationships, sources with X1: {X1[src].mean():.4f} of the relationships, "
+          f"oracle distinct {want}")
+    for share in (int(x) for x in args.shares.split(",")):
+        for step in (int(x) for x in args.steps.split(",")):
+            reads, first, got = model(n, src, dst, share, step)
+            print(f"share {share} step {step}: X reads / rel {reads / m:.4f}, first encounters / rel {first / m:.4f}, "
+                  f"distinct {got} ({'ok' if got == want else 'MISMATCH'})")
+
+
+if __name__ == "__main__":
+    main()
