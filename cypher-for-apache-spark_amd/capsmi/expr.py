@@ -7,7 +7,8 @@ column references (a Var / Property / HasLabel / HasType resolves to a physical 
 RecordHeader, :97-105), literals and parameters (:86-92, :111-117), Equals (:120), Not (:121),
 IsNull / IsNotNull (:122-123), Ands / Ors (:132-136), In (:138-145), < <= > >= (:147-150),
 Add / Subtract / Multiply, and the id-tag vocabulary BitwiseAnd / BitwiseOr / ShiftLeft /
-ShiftRightUnsigned (:264-274) and CaseExpr (:283-298).
+ShiftRightUnsigned (:264-274), CaseExpr (:283-298), and Explode of a list column, ListLit or list
+parameter (:237-241), which ``GpuTable.withColumns`` runs as the UNWIND operator.
 
 ``compile_program`` lowers a tree to the postfix ``capsmi_expr`` program of include/capsmi.h.
 """
@@ -133,6 +134,35 @@ class Param(Expr):
     SparkSQLExprMapper.scala:86-92 turns it into ``functions.lit``.  A list parameter may only be an
     element of ``In``, where it stands for its values."""
     index: int
+
+
+@dataclass(frozen=True, eq=False)
+class ListLit(Expr):
+    """ListLit (okapi-ir Expr.scala; SparkSQLExprMapper.scala:111-112, functions.array of the literals):
+    Python scalars (int, float, bool, str, None) of one type.  On the device path it is the operand of
+    ``Explode`` only."""
+    values: Tuple[object, ...]
+
+
+@dataclass(frozen=True, eq=False)
+class Explode(Expr):
+    """Explode(list) (okapi-ir Expr.scala; SparkSQLExprMapper.scala:237-241, functions.explode): what
+    RelationalPlanner.scala:94-96 adds for UNWIND.  ``arg`` is a list column (``Col``), a ``ListLit`` or a
+    list ``Param``.  Only the whole expression of one ``withColumns`` column may be an Explode, and one per
+    call (Spark allows one generator per select)."""
+    arg: Expr
+
+
+def contains_explode(e: Expr) -> bool:
+    """Whether an Explode occurs anywhere in ``e``."""
+    if isinstance(e, Explode):
+        return True
+    for v in e.__dict__.values():
+        for x in (v if isinstance(v, tuple) else (v,)):
+            for y in (x if isinstance(x, tuple) else (x,)):  # Case alternatives are pairs
+                if isinstance(y, Expr) and contains_explode(y):
+                    return True
+    return False
 
 
 TRUE = Lit(True)

@@ -27,7 +27,8 @@ from typing import Dict, FrozenSet, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .expr import (BOOL, F64, I64, STR, Ands, BinOp, Col, Expr, In, IsNotNull, IsNull, Lit, Not, Ors, ands, eq)
+from .expr import (BOOL, F64, I64, LIST, STR, Ands, BinOp, Col, Explode, Expr, In, IsNotNull, IsNull, ListLit, Lit, Not, Ors,
+                   ands, eq)
 from .table import ColumnData, decode_value
 
 
@@ -63,14 +64,33 @@ class PropertyGraph:
         out = set()
         for n in self.nodes:
             out |= set(n.labels)
-            out |= {v for v in n.props.values() if isinstance(v, str)}
+            out |= _strings_of(n.props.values())
         for r in self.rels:
             out.add(r.type)
-            out |= {v for v in r.props.values() if isinstance(v, str)}
+            out |= _strings_of(r.props.values())
         return sorted(out)
 
 
+def _strings_of(values) -> set:
+    out = set()
+    for v in values:
+        if isinstance(v, str):
+            out.add(v)
+        elif isinstance(v, (list, tuple)):
+            out |= {x for x in v if isinstance(x, str)}
+    return out
+
+
 def _value_type(v) -> int:
+    if isinstance(v, (list, tuple)):  # CTList(elem): the element type of a non-empty list, else Long
+        elems = {_value_type(x) for x in v if x is not None}
+        if any(t >= LIST for t in elems):
+            raise PlanningError(f"nested list property {v!r}")
+        if elems == {I64, F64}:
+            elems = {F64}
+        if len(elems) > 1:
+            raise PlanningError(f"list property {v!r} mixes element types")
+        return LIST + (elems.pop() if elems else I64)
     if isinstance(v, bool):
         return BOOL
     if isinstance(v, int):
@@ -86,14 +106,27 @@ def _prop_types(entities) -> Dict[str, int]:
     """Property key -> physical type; Int/Float mixes widen to Float, other conflicts are errors
     (schema conflict, MatchBehaviour 'type conflicts on expressions')."""
     out: Dict[str, int] = {}
+    untyped = set()  # list properties seen only as empty lists so far: the element type is still open
     for e in entities:
         for k, v in e.props.items():
             if v is None:
                 continue
             t = _value_type(v)
+            if isinstance(v, (list, tuple)) and not any(x is not None for x in v):
+                if k not in out:
+                    out[k] = t
+                    untyped.add(k)
+                elif out[k] < LIST:
+                    raise PlanningError(f"property '{k}' has conflicting types")
+                continue
+            if k in untyped and t >= LIST:
+                untyped.discard(k)
+                out[k] = t
             if k in out and out[k] != t:
                 if {out[k], t} == {I64, F64}:
                     t = F64
+                elif {out[k], t} == {LIST + I64, LIST + F64}:
+                    t = LIST + F64
                 else:
                     raise PlanningError(f"property '{k}' has conflicting types")
             out[k] = t
@@ -103,6 +136,12 @@ def _prop_types(entities) -> Dict[str, int]:
 def _column(name: str, ty: int, values: Sequence, encode) -> ColumnData:
     n = len(values)
     valid = np.array([v is not None for v in values], dtype=bool)
+    if ty >= LIST:  # one array of element words per row (ColumnData's list form); a null row is empty
+        elem = ty - LIST
+        rows = np.empty(n, dtype=object)
+        for i, v in enumerate(values):
+            rows[i] = _column("", elem, list(v) if v is not None else [], encode).values
+        return ColumnData(name, ty, rows, None if valid.all() else valid)
     if ty == F64:
         arr = np.array([float(v) if v is not None else 0.0 for v in values], dtype=np.float64)
     elif ty == STR:
@@ -191,8 +230,8 @@ class ScanGraph:
         for t in sel:
             cols = [(Col(t.id_col), var)]
             cols += [(Lit(l in t.labels), f"{var}:{l}") for l in all_labels]
-            cols += [(Col(k) if k in t.props else Lit(None, props[k]), f"{var}.{k}") for k in sorted(props)]
-            ops.append(t.table.withColumns(*cols).select(*header))
+            cols += [(Col(k) if k in t.props or props[k] >= LIST else Lit(None, props[k]), f"{var}.{k}") for k in sorted(props)]
+            ops.append(_with_null_lists(t, props).withColumns(*cols).select(*header))
         out = ops[0]
         for o in ops[1:]:
             out = out.unionAll(o)
@@ -215,8 +254,8 @@ class ScanGraph:
             (ty_name,) = tuple(t.labels)
             cols = [(Col(t.id_col), var), (Col(t.src_col), f"{var}.__src"), (Col(t.dst_col), f"{var}.__dst"),
                     (Lit(ty_name), f"{var}.__type")]
-            cols += [(Col(k) if k in t.props else Lit(None, props[k]), f"{var}.{k}") for k in sorted(props)]
-            ops.append(t.table.withColumns(*cols).select(*header))
+            cols += [(Col(k) if k in t.props or props[k] >= LIST else Lit(None, props[k]), f"{var}.{k}") for k in sorted(props)]
+            ops.append(_with_null_lists(t, props).withColumns(*cols).select(*header))
         out = ops[0]
         for o in ops[1:]:
             out = out.unionAll(o)
@@ -225,6 +264,20 @@ class ScanGraph:
     def _empty(self, schema):
         return self.backend.table([ColumnData(n, ty, np.zeros(0, dtype=np.float64 if ty == F64 else np.int64))
                                    for n, ty in schema])
+
+
+def _with_null_lists(t: EntityTable, props: Dict[str, int]):
+    """t's table; with an all-null list column for every list property of the scan that t lacks (a null
+    literal carries no list store), under the property's name -- the scan's ``Lit(None, ty)`` for it is
+    then replaced by the column."""
+    missing = [k for k in sorted(props) if props[k] >= LIST and k not in t.props]
+    if not missing:
+        return t.table
+    tab, n = t.table, t.table.size
+    for k in missing:
+        tab = tab.add_list_column_csr(k, props[k] - LIST, np.zeros(n + 1, dtype=np.int64), np.zeros(0, dtype=np.int64),
+                                      np.zeros(n, dtype=np.uint8))
+    return tab
 
 
 class UnionGraph:
@@ -430,11 +483,12 @@ DISTINCT_AGGS = ("count_distinct", "collect_distinct")
 class _Op:
     """A backend table plus its header bookkeeping."""
 
-    def __init__(self, table, header: List[str], node_vars: set, rel_vars: List[str]):
+    def __init__(self, table, header: List[str], node_vars: set, rel_vars: List[str], null_cols=()):
         self.table = table
         self.header = header
         self.node_vars = node_vars
         self.rel_vars = rel_vars      # relationship id columns in the header (incl. var-length hops)
+        self.null_cols = set(null_cols)  # value columns that are a missing property (a null of no type)
 
 
 class Planner:
@@ -445,7 +499,10 @@ class Planner:
     # ---- query ------------------------------------------------------------------------------
     def run(self, query: dict):
         """Execute ``{"clauses": [{"match": str, "where": expr?}], "return": {...}}``; returns
-        (table, output spec) ready for :func:`result_rows`."""
+        (table, output spec) ready for :func:`result_rows`.  Further clause kinds:
+        ``{"unwind": spec, "as": name}`` with spec ``["listlit", [...]]``, ``["param", name]`` (a list of the
+        query's ``"params"`` map), ``["var", column]`` or ``["prop", var, key]``, and
+        ``{"with": {"items": ...}, "where": expr?}`` (the items of a RETURN)."""
         cur: Optional[_Op] = None
         varlen: Dict[str, int] = {}
         if query.get("driving"):  # driving table: its columns are value variables (planStartWithDrivingTable)
@@ -462,11 +519,78 @@ class Planner:
                 cols.append(_column(name, ty, values, dictionary.encode))
             cur = _Op(self.g.backend.table(cols), list(d), set(), [])
         for clause in query["clauses"]:
-            if "optional_match" in clause:
+            if "unwind" in clause:
+                cur = self._unwind(cur, clause["unwind"], clause["as"], query.get("params", {}))
+            elif "with" in clause:
+                cur = self._with(cur, clause["with"], clause.get("where"), varlen)
+            elif "optional_match" in clause:
                 cur = self._optional(cur, clause["optional_match"], clause.get("where"), varlen)
             else:
                 cur = self._match(cur, clause["match"], clause.get("where"), varlen)
         return self._return(cur, query["return"], varlen)
+
+    # Unwind: RelationalPlanner.scala:94-96 -- in.add(Explode(list) as item), a Table.withColumns
+    def _unwind(self, cur: Optional[_Op], spec, name: str, params: dict) -> _Op:
+        unit = None
+        if cur is None:  # a standalone UNWIND starts from the unit table (one row; the helper column is dropped)
+            unit = self.names.fresh("unit")
+            cur = _Op(self.g.backend.table([ColumnData(unit, I64, np.zeros(1, dtype=np.int64))]), [unit], set(), [])
+        if name in cur.header:
+            raise PlanningError(f"variable {name} is already bound")
+        kind = spec[0]
+        if kind == "listlit":
+            lst = ListLit(tuple(spec[1]))
+        elif kind == "param":
+            if not isinstance(params.get(spec[1]), (list, tuple)):
+                raise PlanningError(f"UNWIND needs a list parameter ${spec[1]}")
+            lst = ListLit(tuple(params[spec[1]]))
+        elif kind in ("var", "prop"):
+            col = spec[1] if kind == "var" else f"{spec[1]}.{spec[2]}"
+            if col not in cur.header or col in cur.null_cols:
+                if kind == "var" and col not in cur.header:
+                    raise PlanningError(f"unknown variable {col}")
+                lst = ListLit(())  # a missing property is a null list: no rows
+            else:
+                lst = Col(col)
+        else:
+            raise PlanningError(f"cannot UNWIND {spec!r}")
+        t = cur.table.withColumns((Explode(lst), name))
+        header = cur.header + [name]
+        if unit is not None:
+            t = t.drop(unit)
+            header = [name]
+        return _Op(t, header, set(cur.node_vars), list(cur.rel_vars), cur.null_cols)
+
+    def _with(self, cur: _Op, ret: dict, where, varlen: Dict[str, int]) -> _Op:
+        """WITH items [WHERE pred]: the projection / aggregation of a RETURN; its aliases become the
+        variables of what follows -- value columns, or for an entity item the columns it owns."""
+        if cur is None:
+            raise PlanningError("WITH needs an input")
+        null_cols = {alias for alias, spec in ret["items"]
+                     if spec[0] == "prop" and f"{spec[1]}.{spec[2]}" not in cur.header}
+        t, outs = self._return(cur, ret, varlen)
+        renames, header, node_vars, rel_vars = [], [], set(), []
+        for kind, alias, spec in outs:
+            if kind == "col":
+                renames.append((Col(spec), alias))
+                header.append(alias)
+            elif kind == "entity":
+                is_rel, parts = spec
+                for suffix, col in parts:
+                    renames.append((Col(col), alias + suffix))
+                    header.append(alias + suffix)
+                if is_rel:
+                    rel_vars.append(alias)
+                else:
+                    node_vars.add(alias)
+            else:
+                raise PlanningError("a var-length relationship list cannot pass through WITH")
+        if len(set(header)) != len(header):
+            raise PlanningError("WITH aliases collide")
+        t = t.withColumns(*renames).select(*header)
+        if where is not None:
+            t = t.filter(to_expr(where, header))
+        return _Op(t, header, node_vars, rel_vars, null_cols)
 
     def _optional(self, cur: Optional[_Op], pattern: str, where, varlen: Dict[str, int]) -> _Op:
         """OPTIONAL MATCH: the pattern is planned on top of the input (LogicalPlanner.scala:115-128);

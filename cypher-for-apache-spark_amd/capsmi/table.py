@@ -19,7 +19,8 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .expr import BOOL, F64, I64, LIST, STR, CapsmiExpr, Col, Expr, Lit, compile_program, to_ctypes
+from .expr import (BOOL, F64, I64, LIST, STR, CapsmiExpr, Col, Explode, Expr, ListLit, Lit, Param, compile_program,
+                   contains_explode, to_ctypes)
 
 _TLS = threading.local()
 
@@ -41,10 +42,56 @@ class ColumnData:
     valid: Optional[np.ndarray] = None
 
     def words(self) -> np.ndarray:
+        if self.type >= LIST:
+            raise _lib.IllegalArgumentException(f"list column {self.name} has no row words; see csr()")
         v = np.asarray(self.values)
         if self.type == F64:
             return np.ascontiguousarray(v.astype(np.float64)).view(np.int64)
         return np.ascontiguousarray(v.astype(np.int64))
+
+
+def _element_words(ty: int, v) -> np.ndarray:
+    a = np.asarray(v)
+    if ty == F64:
+        return np.ascontiguousarray(a.astype(np.float64)).view(np.int64).reshape(-1)
+    return np.ascontiguousarray(a.astype(np.int64)).reshape(-1)
+
+
+def list_csr(c: ColumnData) -> Tuple[np.ndarray, np.ndarray]:
+    """(offsets int64[n + 1], element words int64) of a list ColumnData; a null or None row is empty."""
+    elem = c.type - LIST
+    rows = [np.empty(0, dtype=np.int64) if (r is None or (c.valid is not None and not c.valid[i]))
+            else _element_words(elem, r) for i, r in enumerate(c.values)]
+    offs = np.zeros(len(rows) + 1, dtype=np.int64)
+    if rows:
+        np.cumsum([len(r) for r in rows], out=offs[1:])
+    vals = np.concatenate(rows) if rows else np.empty(0, dtype=np.int64)
+    return offs, np.ascontiguousarray(vals, dtype=np.int64)
+
+
+def typed_values(items: Sequence[object], encode_str, what: str):
+    """(element type, capsmi_value array) of Python scalars of one type (None = null); an int list with a
+    float is Double; an empty or all-null list is Long."""
+    from .expr import _lit_bits
+
+    def type_of(v):
+        return BOOL if isinstance(v, (bool, np.bool_)) else I64 if isinstance(v, (int, np.integer)) \
+            else F64 if isinstance(v, (float, np.floating)) else STR if isinstance(v, str) else None
+
+    for x in items:
+        if x is not None and type_of(x) is None:
+            raise _lib.NotImplementedException(f"{what}: value {x!r} (nested lists and maps are not supported)")
+    tys = {type_of(x) for x in items} - {None}
+    if tys == {I64, F64}:
+        tys = {F64}
+    if len(tys) > 1:
+        raise _lib.IllegalArgumentException(f"{what}: mixed value types")
+    ty = tys.pop() if tys else I64
+    vals = (_lib.Value * max(1, len(items)))()
+    for k, x in enumerate(items):
+        vals[k].is_null = 1 if x is None else 0
+        vals[k].ival = 0 if x is None else _lit_bits(x, ty, encode_str)
+    return ty, vals
 
 
 def decode_value(ty: int, v, dictionary):
@@ -129,6 +176,7 @@ class Session:
         _lib.call("capsmi_session_create", device, ctypes.byref(self._h))
         self.device = device
         self.dictionary = dictionary or StringDictionary()
+        self.params: List[object] = []  # the values of set_params (Explode of a list Param reads them)
 
     @property
     def handle(self):
@@ -171,11 +219,18 @@ class Session:
     def table(self, columns: Sequence[ColumnData]) -> "GpuTable":
         """CAPSNodeTable / CAPSRelationshipTable ingest: copies host columns to the device."""
         n = len(columns[0].values) if columns else 0
+        for c in columns:
+            if len(c.values) != n:
+                raise _lib.IllegalArgumentException(f"column {c.name} has {len(c.values)} rows, expected {n}")
+        lists = [c for c in columns if c.type >= LIST]
+        if lists:  # array columns: the plain columns first, each list column appended, then the given order
+            t = self.table([c for c in columns if c.type < LIST]) if len(lists) < len(columns) else self._rows_only(n)
+            for c in lists:
+                t = t.add_list_column(c)
+            return t.select(*[c.name for c in columns])
         descs = (_lib.ColDesc * max(1, len(columns)))()
         keep = []
         for i, c in enumerate(columns):
-            if len(c.values) != n:
-                raise _lib.IllegalArgumentException(f"column {c.name} has {len(c.values)} rows, expected {n}")
             w = c.words()
             keep.append(w)
             descs[i].name = c.name.encode()
@@ -189,6 +244,12 @@ class Session:
                 descs[i].valid = None
         out = ctypes.c_void_p()
         _lib.call("capsmi_table_from_host", self._h, len(columns), descs, n, ctypes.byref(out))
+        return GpuTable(self, out)
+
+    def _rows_only(self, n: int) -> "GpuTable":
+        """A table of n rows and no column (the carrier of list columns given alone)."""
+        out = ctypes.c_void_p()
+        _lib.call("capsmi_table_from_host", self._h, 0, (_lib.ColDesc * 1)(), n, ctypes.byref(out))
         return GpuTable(self, out)
 
     def encode_str(self, s: str) -> int:
@@ -240,6 +301,7 @@ class Session:
             return BOOL if isinstance(v, bool) else I64 if isinstance(v, int) else F64 if isinstance(v, float) \
                 else STR if isinstance(v, str) else None
 
+        self.params = list(values)
         keep, arr = [], (_lib.Param * max(1, len(values)))()
         for i, v in enumerate(values):
             items = list(v) if isinstance(v, (list, tuple)) else [v]
@@ -585,7 +647,71 @@ class GpuTable:
         _lib.call("capsmi_group", self._h, len(by), _lib.strs(by), len(aggregations), aggs, ctypes.byref(out))
         return self._wrap(out)
 
+    def explode(self, list_col: str, item: str) -> "GpuTable":
+        """UNWIND of a list column: one row per element, none for a null or empty list; the input columns
+        plus `item` (include/capsmi.h capsmi_explode).  Rows come in (input row, element position) order."""
+        out = ctypes.c_void_p()
+        _lib.call("capsmi_explode", self._h, list_col.encode(), item.encode(), ctypes.byref(out))
+        return self._wrap(out)
+
+    def explodeValues(self, values: Sequence[object], item: str) -> "GpuTable":
+        """UNWIND of a literal list or list parameter: every row once per value (include/capsmi.h
+        capsmi_explode_values).  Values are Python scalars of one type, None for null."""
+        ty, vals = typed_values(list(values), self.session.encode_str, "explodeValues")
+        out = ctypes.c_void_p()
+        _lib.call("capsmi_explode_values", self._h, ty, len(values), ctypes.cast(vals, ctypes.c_void_p), item.encode(),
+                  ctypes.byref(out))
+        return self._wrap(out)
+
+    def add_list_column(self, c: ColumnData) -> "GpuTable":
+        """This table plus the list column `c` (type LIST + element type; one array of elements per row;
+        include/capsmi.h capsmi_table_add_list_column)."""
+        if c.type < LIST:
+            raise _lib.IllegalArgumentException(f"column {c.name} is not a list column")
+        offs, vals = list_csr(c)
+        return self.add_list_column_csr(c.name, c.type - LIST, offs, vals, c.valid)
+
+    def add_list_column_csr(self, name: str, elem_type: int, offsets, values, valid=None) -> "GpuTable":
+        """The same from CSR arrays: `offsets` int64[rows + 1], `values` the element words."""
+        offs = np.ascontiguousarray(offsets, dtype=np.int64)
+        if len(offs) != self.size + 1:
+            raise _lib.IllegalArgumentException(f"list column {name}: {len(offs)} offsets for {self.size} rows")
+        vals = np.ascontiguousarray(values)
+        vals = vals.view(np.int64) if vals.dtype == np.float64 else np.ascontiguousarray(vals, dtype=np.int64)
+        if len(vals) < int(offs[-1]):
+            raise _lib.IllegalArgumentException(f"list column {name}: offsets end at {int(offs[-1])}, {len(vals)} values")
+        vb = None if valid is None else np.ascontiguousarray(np.asarray(valid, dtype=np.uint8))
+        out = ctypes.c_void_p()
+        _lib.call("capsmi_table_add_list_column", self._h, name.encode(), elem_type, offs.ctypes.data,
+                  vals.ctypes.data if len(vals) else None, None if vb is None or not len(vb) else vb.ctypes.data,
+                  ctypes.byref(out))
+        return self._wrap(out)
+
+    def _explode_column(self, e: Explode, name: str) -> "GpuTable":
+        a = e.arg
+        if isinstance(a, Col):
+            return self.explode(a.name, name)
+        if isinstance(a, ListLit):
+            return self.explodeValues(a.values, name)
+        if isinstance(a, Param):
+            params = self.session.params
+            if not 0 <= a.index < len(params) or not isinstance(params[a.index], (list, tuple)):
+                raise _lib.IllegalArgumentException(f"Explode: parameter {a.index} is not a list parameter")
+            return self.explodeValues(params[a.index], name)
+        raise _lib.NotImplementedException(f"Explode of {a!r}: a list column, ListLit or list Param")
+
     def withColumns(self, *columns: Tuple[Expr, str]) -> "GpuTable":
+        gen = [i for i, (e, _) in enumerate(columns) if contains_explode(e)]
+        if gen:  # UNWIND: Explode(list) AS item (RelationalPlanner.scala:94-96); one generator per call
+            if len(gen) > 1:
+                raise _lib.NotImplementedException("more than one Explode in one withColumns")
+            e, name = columns[gen[0]]
+            if not isinstance(e, Explode) or contains_explode(e.arg):
+                raise _lib.NotImplementedException("Explode nested in another expression")
+            t = self.withColumns(*columns[:gen[0]]) if gen[0] else self
+            t = t._explode_column(e, name)
+            rest = columns[gen[0] + 1:]
+            return t.withColumns(*rest) if rest else t
         # the scans' projections (columns and label / null literals) repeat on the same entity tables
         # query after query: their argument arrays are kept per table, keyed by their structure
         key = []

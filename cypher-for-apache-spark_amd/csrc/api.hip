@@ -1385,9 +1385,149 @@ capsmi_status eager_group(capsmi_table* t, int32_t nby, const char* const* by, i
     API_END
 }
 
+// ---- UNWIND (RelationalPlanner.scala:94-96, SparkSQLExprMapper.scala:237-241) ------------------------
+namespace {
+
+// the exploded table: t's columns of `keep` (null: all) gathered at `src` (null: the rows as they are, shared),
+// with the item column in the place of a column of its name, else appended (the capsmi_with_columns rule)
+capsmi_table* exploded(capsmi_table* t, int64_t m, const Buf& src, Column item, const std::vector<std::string>* keep) {
+    capsmi_session* s = t->sess;
+    auto wanted = [&](const std::string& n) { return !keep || std::find(keep->begin(), keep->end(), n) != keep->end(); };
+    capsmi_table kept;
+    kept.sess = s;
+    kept.nrows = t->nrows;
+    int at = -1;  // the item's position among the produced columns
+    for (const Column& c : t->cols) {
+        if (c.name == item.name) at = (int)kept.cols.size();
+        else if (wanted(c.name)) kept.cols.push_back(c);
+    }
+    std::unique_ptr<capsmi_table> o(new_table(s, m));
+    if (src) {
+        // per output row and gathered column: 8 B index + 8 B word read, 8 B written
+        KernelTimer kt(s, "explode_gather", 24.0 * (double)m * (double)kept.cols.size());
+        gather_into(o.get(), &kept, src, m, false);
+    } else {
+        o->cols = kept.cols;
+    }
+    if (wanted(item.name)) o->cols.insert(at < 0 ? o->cols.end() : o->cols.begin() + at, std::move(item));
+    return o.release();
+}
+
+}  // namespace
+
+capsmi_status eager_explode(capsmi_table* t, const char* list_col, const char* item_name,
+                            const std::vector<std::string>* keep, capsmi_table** out) {
+    API_BEGIN
+    need(t, "table");
+    need(out, "out");
+    need(item_name, "item name");
+    capsmi_session* s = t->sess;
+    use_device(s);
+    const Column& lc = t->cols[col_index(t, list_col)];
+    REQUIRE(is_list_type(lc.type), CAPSMI_ERR_ILLEGAL_ARGUMENT, "column '" + lc.name + "' is not a list column");
+    REQUIRE(lc.list, CAPSMI_ERR_INTERNAL, "list column without a store");
+    Column item;
+    item.name = item_name;
+    item.type = lc.list->elem;
+    Buf src;
+    const int64_t m = explode_lists(s, lc.d(), lc.v(), t->nrows, *lc.list, item.data, src);
+    if (m == 0) item.data = src = dev_alloc(sizeof(int64_t), s);
+    *out = exploded(t, m, src, std::move(item), keep);
+    API_END
+}
+
+capsmi_status eager_explode_values(capsmi_table* t, int32_t elem_type, int32_t count, const capsmi_value* values,
+                                   const char* item_name, const std::vector<std::string>* keep, capsmi_table** out) {
+    API_BEGIN
+    need(t, "table");
+    need(out, "out");
+    need(item_name, "item name");
+    REQUIRE(elem_type >= CAPSMI_I64 && elem_type <= CAPSMI_STR, CAPSMI_ERR_ILLEGAL_ARGUMENT, "bad element type");
+    REQUIRE(count >= 0 && (count == 0 || values), CAPSMI_ERR_ILLEGAL_ARGUMENT, "bad value list");
+    capsmi_session* s = t->sess;
+    use_device(s);
+    const int64_t n = t->nrows, m = n * count;
+    bool any_null = false;
+    std::vector<int64_t> words(count > 0 ? count : 1, 0);
+    std::vector<uint8_t> ok(count > 0 ? count : 1, 1);
+    for (int32_t j = 0; j < count; ++j) {
+        words[j] = values[j].is_null ? 0 : values[j].ival;
+        ok[j] = values[j].is_null ? 0 : 1;
+        any_null |= values[j].is_null != 0;
+    }
+    Column item;
+    item.name = item_name;
+    item.type = elem_type;
+    item.data = dev_alloc(sizeof(int64_t) * (m > 0 ? m : 1), s);
+    if (any_null) item.valid = dev_alloc(m > 0 ? m : 1, s);
+    Buf src;
+    if (m > 0) {
+        Buf dv = dev_alloc(sizeof(int64_t) * count, s), dk = dev_alloc(count, s);
+        HIP_CHECK(hipMemcpyAsync(P<void>(dv), words.data(), sizeof(int64_t) * count, hipMemcpyHostToDevice, s->stream));
+        HIP_CHECK(hipMemcpyAsync(P<void>(dk), ok.data(), count, hipMemcpyHostToDevice, s->stream));
+        src = dev_alloc(sizeof(int64_t) * m, s);
+        explode_values(s, n, count, P<int64_t>(dv), any_null ? P<uint8_t>(dk) : nullptr, P<int64_t>(item.data),
+                       P<uint8_t>(item.valid), P<int64_t>(src));
+        HIP_CHECK(hipStreamSynchronize(s->stream));  // the host words go away
+        if (count == 1) src = nullptr;  // every row once, in order: the payload columns are shared, not gathered
+    } else {
+        src = dev_alloc(sizeof(int64_t), s);
+    }
+    *out = exploded(t, m, src, std::move(item), keep);
+    API_END
+}
+
 }  // namespace capsmi
 
 extern "C" {
+
+// CAPSNodeTable / CAPSRelationshipTable ingest of an array property column (CAPSTable.scala:47-214): a list
+// column from host CSR arrays, appended to `t`
+capsmi_status capsmi_table_add_list_column(capsmi_table* t, const char* name, int32_t elem_type, const int64_t* host_offsets,
+                                           const void* host_values, const uint8_t* host_valid, capsmi_table** out) {
+    API_BEGIN
+    need(t, "table");
+    need(out, "out");
+    need(name, "column name");
+    need(host_offsets, "host_offsets");
+    REQUIRE(elem_type >= CAPSMI_I64 && elem_type <= CAPSMI_STR, CAPSMI_ERR_ILLEGAL_ARGUMENT, "bad element type");
+    M(t);
+    REQUIRE(t->find(name) < 0, CAPSMI_ERR_ILLEGAL_ARGUMENT, std::string("duplicate column '") + name + "'");
+    const int64_t n = t->nrows;
+    REQUIRE(host_offsets[0] == 0, CAPSMI_ERR_ILLEGAL_ARGUMENT, "list offsets must start at 0");
+    for (int64_t i = 0; i < n; ++i)
+        REQUIRE(host_offsets[i + 1] >= host_offsets[i], CAPSMI_ERR_ILLEGAL_ARGUMENT, "list offsets must not decrease");
+    const int64_t nv = host_offsets[n];
+    REQUIRE(nv == 0 || host_values, CAPSMI_ERR_ILLEGAL_ARGUMENT, "null list values");
+    capsmi_session* s = t->sess;
+    use_device(s);
+    hipStream_t st = s->stream;
+    auto L = std::make_shared<ListStore>();
+    L->elem = elem_type;
+    L->nlists = n;
+    L->nvalues = nv;
+    L->offsets = dev_alloc(sizeof(int64_t) * (n + 1), s);
+    L->values = dev_alloc(sizeof(int64_t) * (nv > 0 ? nv : 1), s);
+    HIP_CHECK(hipMemcpyAsync(P<void>(L->offsets), host_offsets, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, st));
+    if (nv) HIP_CHECK(hipMemcpyAsync(P<void>(L->values), host_values, sizeof(int64_t) * nv, hipMemcpyHostToDevice, st));
+    Column c;
+    c.name = name;
+    c.type = CAPSMI_LIST + elem_type;
+    c.list = L;
+    c.data = dev_alloc(sizeof(int64_t) * (n > 0 ? n : 1), s);
+    iota_i64(P<int64_t>(c.data), 0, n, st);  // row i is list i of the store
+    if (host_valid) {
+        c.valid = dev_alloc(n > 0 ? n : 1, s);
+        if (n) HIP_CHECK(hipMemcpyAsync(P<void>(c.valid), host_valid, n, hipMemcpyHostToDevice, st));
+    }
+    HIP_CHECK(hipStreamSynchronize(st));  // host buffers may go away
+    std::unique_ptr<capsmi_table> o(new_table(s, n));
+    o->cols = t->cols;
+    o->cols.push_back(std::move(c));
+    o->partitioned = t->partitioned;
+    *out = o.release();
+    API_END
+}
 
 // ---- graph fast path ------------------------------------------------------------------------------
 capsmi_status capsmi_bitmap_create(capsmi_session* s, int64_t id_lo, int64_t id_hi, capsmi_bitmap** out) {

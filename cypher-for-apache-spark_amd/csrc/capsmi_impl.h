@@ -356,6 +356,16 @@ std::shared_ptr<ListStore> collect_lists(capsmi_session* s, const int64_t* gid, 
                                          const uint8_t* valid, int type, int64_t n, bool distinct);
 // one store holding a's lists, then b's (b's list k becomes a.nlists + k)
 std::shared_ptr<ListStore> concat_lists(capsmi_session* s, const ListStore& a, const ListStore& b);
+// UNWIND (k_explode.hip).  Column form: rows (word, valid) of n rows over store L -> the element words `item`
+// and the input row `src` of every output row, in (input row, element position) order; returns their number
+// (synchronises; item / src stay null when it is 0).  Expansion tiles hold kExplodeTile output rows.
+constexpr int kExplodeTile = 2048;
+int64_t explode_lists(capsmi_session* s, const int64_t* word, const uint8_t* valid, int64_t n, const ListStore& L,
+                      Buf& item, Buf& src);
+// constant form: output row j = input row j / count with item vals[j % count] (device words; vvalid and
+// item_valid both null when no value is null); item / src hold n * count entries
+void explode_values(capsmi_session* s, int64_t n, int64_t count, const int64_t* vals, const uint8_t* vvalid, int64_t* item,
+                    uint8_t* item_valid, int64_t* src);
 // multi-GPU (k_dist.hip): the session's collective, stream-ordered (capsmi_collective_fn)
 void collective(capsmi_session* s, int op, const void* send, void* recv, int64_t count, int dtype);
 // calls of the host collective move at most coll_chunk() elements (CAPSMI_COLL_CHUNK); collective() and
@@ -633,6 +643,11 @@ capsmi_status eager_distinct(capsmi_table* t, capsmi_table** out);
 capsmi_status eager_distinct_on(capsmi_table* t, int32_t ncols, const char* const* cols, capsmi_table** out);
 capsmi_status eager_group(capsmi_table* t, int32_t nby, const char* const* by, int32_t naggs, const capsmi_agg* aggs,
                           capsmi_table** out);
+// keep: the output columns to produce (null: all) -- payload columns outside it are not gathered
+capsmi_status eager_explode(capsmi_table* t, const char* list_col, const char* item_name,
+                            const std::vector<std::string>* keep, capsmi_table** out);
+capsmi_status eager_explode_values(capsmi_table* t, int32_t elem_type, int32_t count, const capsmi_value* values,
+                                   const char* item_name, const std::vector<std::string>* keep, capsmi_table** out);
 
 // CSV ingest (ingest.hip)
 capsmi_table* read_csv(capsmi_session* s, const std::vector<std::string>& paths, char delim, char comment,

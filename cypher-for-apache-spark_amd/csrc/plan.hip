@@ -36,7 +36,8 @@ struct AggSpec {
 };
 
 struct PlanNode {
-    enum Kind { SELECT, DROP, RENAME, FILTER, WITH_COLUMNS, JOIN, UNION, DISTINCT, DISTINCT_ON, GROUP, ORDER, SKIP, LIMIT };
+    enum Kind { SELECT, DROP, RENAME, FILTER, WITH_COLUMNS, JOIN, UNION, DISTINCT, DISTINCT_ON, GROUP, ORDER, SKIP, LIMIT,
+                EXPLODE };
     Kind kind = SELECT;
     std::vector<capsmi_table*> in;            // retained inputs
     std::vector<std::string> a, b;            // column names (see builders)
@@ -45,6 +46,9 @@ struct PlanNode {
     std::vector<AggSpec> aggs;
     int32_t jt = 0;
     int64_t n = 0;
+    // EXPLODE: b[0] the item column; a[0] the list column, or a empty for the constant form with its
+    // `n` values `vals` of element type `jt`
+    std::vector<capsmi_value> vals;
     ~PlanNode() {
         for (capsmi_table* t : in) capsmi_table_release(t);
     }
@@ -175,6 +179,10 @@ capsmi_table* exec_node(const PlanNode& p) {
         case PlanNode::ORDER: { auto c = cstrs(p.a); check(eager_order_by(x, (int)c.size(), c.data(), p.flags.data(), &r)); break; }
         case PlanNode::SKIP: check(eager_skip(x, p.n, &r)); break;
         case PlanNode::LIMIT: check(eager_limit(x, p.n, &r)); break;
+        case PlanNode::EXPLODE:
+            if (p.a.empty()) check(eager_explode_values(x, p.jt, (int32_t)p.n, p.vals.data(), p.b[0].c_str(), nullptr, &r));
+            else check(eager_explode(x, p.a[0].c_str(), p.b[0].c_str(), nullptr, &r));
+            break;
     }
     return r;
 }
@@ -2183,6 +2191,30 @@ Res exec(capsmi_table* t, const Names& need, std::vector<Pred> preds, const Pare
             b.reset();
             return finish(owned(o), need, stay);
         }
+        case PlanNode::EXPLODE: {
+            // row-local: a conjunct that reads the item stays above, the others run on the input rows (fewer
+            // rows to expand); only the payload columns somebody above reads are gathered
+            const std::string& item = p.b[0];
+            std::vector<Pred> down, stay;
+            for (Pred& pr : preds) (has(pr.names, item) ? stay : down).push_back(std::move(pr));
+            Names out = need;
+            for (const Pred& pr : stay)
+                for (const std::string& n : pr.names) add(out, n);
+            Names nin;
+            if (!p.a.empty()) add(nin, p.a[0]);
+            for (const std::string& n : out)
+                if (n != item) add(nin, n);
+            if (nin.empty() && !x->cols.empty()) add(nin, x->cols[0].name);  // the row count travels with a column
+            Res r = exec(x, nin, std::move(down), par);
+            capsmi_table* o = nullptr;
+            if (p.a.empty())
+                check(eager_explode_values(r.t, p.jt, (int32_t)p.n, p.vals.data(), item.c_str(), &out, &o));
+            else
+                check(eager_explode(r.t, p.a[0].c_str(), item.c_str(), &out, &o));
+            o->partitioned = r.t->partitioned;  // no exchange: a rank's rows explode where they are
+            r.reset();
+            return finish(owned(o), need, stay);
+        }
         default: {  // union, distinct, grouping, ordering, skip / limit: conjuncts stay above
             std::vector<Names> nin(p.in.size());
             for (size_t i = 0; i < p.in.size(); ++i) nin[i] = all_names(p.in[i]);
@@ -2395,6 +2427,49 @@ capsmi_status capsmi_with_columns(capsmi_table* t, int32_t ncols, const capsmi_e
             else sch.push_back(c);
         }
         return lazy_table(t->sess, p, sch);
+    });
+}
+
+// the schema of an exploded table: the input's columns, the item replacing a column of its name, else appended
+static std::vector<Column> explode_schema(const capsmi_table* t, const Column& item) {
+    std::vector<Column> sch;
+    for (auto& c : t->cols) sch.push_back(schema_of(c));
+    const int j = find_col(t, item.name);
+    if (j >= 0) sch[j] = item;
+    else sch.push_back(item);
+    return sch;
+}
+
+capsmi_status capsmi_explode(capsmi_table* t, const char* list_col, const char* item_name, capsmi_table** out) {
+    return build(t, out, [&] {
+        need(item_name, "item name");
+        const Column& lc = t->cols[col_of(t, list_col)];
+        REQUIRE(is_list_type(lc.type), CAPSMI_ERR_ILLEGAL_ARGUMENT, "column '" + lc.name + "' is not a list column");
+        auto p = std::make_shared<PlanNode>();
+        p->kind = PlanNode::EXPLODE;
+        hold(*p, t);
+        p->a = {lc.name};
+        p->b = {item_name};
+        return lazy_table(t->sess, p, explode_schema(t, schema_col(item_name, lc.type - CAPSMI_LIST, false)));
+    });
+}
+
+capsmi_status capsmi_explode_values(capsmi_table* t, int32_t elem_type, int32_t count, const capsmi_value* values,
+                                    const char* item_name, capsmi_table** out) {
+    return build(t, out, [&] {
+        need(item_name, "item name");
+        REQUIRE(elem_type >= CAPSMI_I64 && elem_type <= CAPSMI_STR, CAPSMI_ERR_ILLEGAL_ARGUMENT, "bad element type");
+        REQUIRE(count >= 0 && (count == 0 || values), CAPSMI_ERR_ILLEGAL_ARGUMENT, "bad value list");
+        auto p = std::make_shared<PlanNode>();
+        p->kind = PlanNode::EXPLODE;
+        hold(*p, t);
+        p->b = {item_name};
+        p->jt = elem_type;
+        p->n = count;
+        p->vals.assign(values, values + count);
+        bool any_null = false;
+        for (const capsmi_value& v : p->vals) any_null |= v.is_null != 0;
+        return lazy_table(t->sess, p, explode_schema(t, schema_col(item_name, elem_type, any_null)));
     });
 }
 

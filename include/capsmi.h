@@ -66,7 +66,8 @@ enum {
 
 /* List columns (CTList(elem)): the result of a Collect aggregator (SparkTable.scala:169-177,
  * functions.sort_array(collect_list / collect_set)).  The column type is CAPSMI_LIST + element type
- * (CAPSMI_LIST_I64 ... CAPSMI_LIST_STR); rows are read with capsmi_table_export_list.  List columns
+ * (CAPSMI_LIST_I64 ... CAPSMI_LIST_STR); rows are read with capsmi_table_export_list, opened again into
+ * rows by capsmi_explode, and ingested from the host by capsmi_table_add_list_column.  List columns
  * travel through select / drop / rename / filter / join payloads / union all / order-by payloads /
  * skip / limit; using one as a join, grouping, distinct or sort key, or inside an expression, is
  * CAPSMI_ERR_NOT_IMPLEMENTED. */
@@ -215,7 +216,11 @@ capsmi_status capsmi_session_set_profiling_names(capsmi_session* s, const char* 
 capsmi_status capsmi_session_kernel_time(capsmi_session* s, const char* name, int64_t* launches, double* total_ms);
 /* summed algorithmic bytes (inputs read once, outputs written once) of the timed launches of `name`,
  * for kernels that declare them (the join kernels: "direct_join_probe", "radix_join_count",
- * "radix_join_write"); 0 otherwise; then the counter resets. */
+ * "radix_join_write"; UNWIND's "explode": 8 B x (n starts + n row words read, m values read, m items + m source
+ * rows written) for n input rows and m output rows, its payload gathers timed apart as "explode_gather" (24 B per
+ * output row and gathered column) and its
+ * lengths / scan / compaction as "explode_starts"; "explode_values": 16 B per output row); 0 otherwise; then the
+ * counter resets. */
 capsmi_status capsmi_session_kernel_bytes(capsmi_session* s, const char* name, double* bytes);
 /* fused-path routing of lazy plans: enable / disable (default on; off = operator by operator, for
  * A/B checks), and the number of plans routed to fused entry point `name` ("expand", "expand_count",
@@ -281,6 +286,16 @@ capsmi_status capsmi_table_export(const capsmi_table* t, int32_t col, void* host
 capsmi_status capsmi_table_export_list(const capsmi_table* t, int32_t col, int64_t offset, int64_t n,
                                        int64_t* host_offsets, uint8_t* host_valid, void* host_values,
                                        int64_t values_cap, int64_t* nvalues);
+/* List-property ingest, as CAPSNodeTable / CAPSRelationshipTable take array columns of their DataFrame
+ * (CAPSTable.scala:47-214): `t` (materialised by the call) plus a list column `name` of type CAPSMI_LIST +
+ * elem_type built from host CSR arrays.  Row i's elements are host_values[host_offsets[i] .. host_offsets[i+1]):
+ * 8-byte words of the element type, no element nulls (as in Collect's stores).  host_offsets has nrows + 1
+ * int64 entries, non-decreasing, starting at 0; its last entry is the value count.  host_valid (nrows bytes,
+ * 1 = non-null list) may be NULL.  Malformed offsets, a bad element type or an existing column `name` are
+ * CAPSMI_ERR_ILLEGAL_ARGUMENT.  Copies; the result is a plain table (no entity registration). */
+capsmi_status capsmi_table_add_list_column(capsmi_table* t, const char* name, int32_t elem_type,
+                                           const int64_t* host_offsets, const void* host_values,
+                                           const uint8_t* host_valid, capsmi_table** out);
 /* zero-copy device view of a column (valid pointer NULL when the column has no nulls) */
 capsmi_status capsmi_table_column_device_ptr(const capsmi_table* t, int32_t col, const void** data,
                                              const uint8_t** valid);
@@ -348,6 +363,26 @@ capsmi_status capsmi_with_columns(capsmi_table* t, int32_t ncols, const capsmi_e
                                   capsmi_table** out);                                  /* Table.scala:159 */
 capsmi_status capsmi_with_column_renamed(capsmi_table* t, const char* old_name, const char* new_name,
                                          capsmi_table** out);                           /* Table.scala:168 */
+/* UNWIND.  RelationalPlanner lowers logical.Unwind(list, item, in) to in.add(Explode(list) as item)
+ * (RelationalPlanner.scala:94-96), i.e. Table.withColumns (Table.scala:159) of an Explode expression, which
+ * SparkSQLExprMapper maps to functions.explode (SparkSQLExprMapper.scala:237-241).  Row i of `t`, whose list in
+ * the CAPSMI_LIST_* column `list_col` has L_i elements, becomes L_i output rows; a null or an empty list yields
+ * no row (explode, not explode_outer).  The result holds every input column, `list_col` included (withColumn
+ * keeps it), and a non-nullable column `item_name` of the element type, which replaces a column of that name if
+ * there is one and is appended otherwise (the capsmi_with_columns rule).  Output rows are ordered by (input row,
+ * element position).  A `list_col` that is no list column is CAPSMI_ERR_ILLEGAL_ARGUMENT.  Lazy like every
+ * operator: a filter that reads the item stays above the explode, filters on other columns run below it, and
+ * only the payload columns that something above reads are gathered; the node matches no fused shape, and the
+ * plan under it is routed as usual.  Row-local: the result of a partitioned table is partitioned, and no
+ * collective is called. */
+capsmi_status capsmi_explode(capsmi_table* t, const char* list_col, const char* item_name, capsmi_table** out);
+/* The same for a list that is not a column: explode(array(lit...)) of a ListLit or a list Param
+ * (SparkSQLExprMapper.scala:86-89, 111-112, 237-241).  Every input row is repeated `count` times, with
+ * item = values[j] (ival as capsmi_expr.ival, of type elem_type = CAPSMI_I64 ... CAPSMI_STR) in its j-th copy;
+ * order (input row, j).  The item column is nullable exactly when some value has is_null set.  count == 0
+ * gives zero rows.  Values are copied. */
+capsmi_status capsmi_explode_values(capsmi_table* t, int32_t elem_type, int32_t count, const capsmi_value* values,
+                                    const char* item_name, capsmi_table** out);
 
 /* ---- graph fast path ------------------------------------------------------------------
  * The relational planner lowers Expand into `join(relScan, source = start)` then

@@ -238,6 +238,13 @@ trait CapsmiLib extends Library {
   def capsmi_group(t: Pointer, nby: Int, by: Array[String], naggs: Int, aggs: CapsmiAgg, out: PointerByReference): Int
   def capsmi_with_columns(t: Pointer, ncols: Int, cols: CapsmiExprColumn, out: PointerByReference): Int
   def capsmi_with_column_renamed(t: Pointer, oldName: String, newName: String, out: PointerByReference): Int
+  // UNWIND: Explode(list) AS item (RelationalPlanner.scala:94-96) of a list column / of literal values
+  def capsmi_explode(t: Pointer, listCol: String, itemName: String, out: PointerByReference): Int
+  def capsmi_explode_values(t: Pointer, elemType: Int, count: Int, values: CapsmiValue, itemName: String,
+                            out: PointerByReference): Int
+  // list-property ingest from host CSR arrays (CAPSTable's array columns)
+  def capsmi_table_add_list_column(t: Pointer, name: String, elemType: Int, hostOffsets: Pointer, hostValues: Pointer,
+                                   hostValid: Pointer, out: PointerByReference): Int
 
   // explicit graph entry points (the lazy plans reach the same kernels through the recogniser)
   def capsmi_bitmap_create(s: Pointer, idLo: Long, idHi: Long, out: PointerByReference): Int

@@ -81,6 +81,31 @@ final class GpuSession(device: Int = 0) extends RelationalCypherSession[GpuTable
   private[opencypher] override val graphs: GpuGraphFactory = GpuGraphFactory()
 
   /** Query parameters for CAPSMI_X_PARAM (ExprCompiler binds the ones a program references). */
+  /** Scalars of one type as (element type, capsmi_value array): the values of a parameter, or the list of
+    * capsmi_explode_values.  An Integer list with a Float is Double; no typed value at all is Long. */
+  def typedValues(items: Seq[CypherValue]): (Int, Array[CapsmiValue]) = {
+    val ty = items.collectFirst {
+      case _: CypherFloat => Capsmi.F64
+      case _: CypherInteger => Capsmi.I64
+      case _: CypherBoolean => Capsmi.BOOL
+      case _: CypherString => Capsmi.STR
+    }.getOrElse(Capsmi.I64)
+    val vals = new CapsmiValue().toArray(math.max(1, items.size)).asInstanceOf[Array[CapsmiValue]]
+    items.zipWithIndex.foreach { case (x, k) =>
+      x match {
+        case CypherNull => vals(k).is_null = 1
+        case CypherInteger(l) if ty == Capsmi.F64 => vals(k).ival = java.lang.Double.doubleToRawLongBits(l.toDouble)
+        case CypherInteger(l) => vals(k).ival = l
+        case CypherFloat(d) => vals(k).ival = java.lang.Double.doubleToRawLongBits(d)
+        case CypherBoolean(b) => vals(k).ival = if (b) 1L else 0L
+        case CypherString(s) => vals(k).ival = dictionary.encode(s)
+        case other => throw UnsupportedOperationException(s"parameter value $other on the device path")
+      }
+      vals(k).write()
+    }
+    (ty, vals)
+  }
+
   def setParams(values: Seq[CypherValue]): Unit = {
     val ps = new CapsmiParam().toArray(math.max(1, values.size)).asInstanceOf[Array[CapsmiParam]]
     values.zipWithIndex.foreach { case (v, i) =>
@@ -88,25 +113,7 @@ final class GpuSession(device: Int = 0) extends RelationalCypherSession[GpuTable
         case CypherList(xs) => (xs, true)
         case x => (List(x), false)
       }
-      val ty = items.collectFirst {
-        case _: CypherFloat => Capsmi.F64
-        case _: CypherInteger => Capsmi.I64
-        case _: CypherBoolean => Capsmi.BOOL
-        case _: CypherString => Capsmi.STR
-      }.getOrElse(Capsmi.I64)
-      val vals = new CapsmiValue().toArray(math.max(1, items.size)).asInstanceOf[Array[CapsmiValue]]
-      items.zipWithIndex.foreach { case (x, k) =>
-        x match {
-          case CypherNull => vals(k).is_null = 1
-          case CypherInteger(l) if ty == Capsmi.F64 => vals(k).ival = java.lang.Double.doubleToRawLongBits(l.toDouble)
-          case CypherInteger(l) => vals(k).ival = l
-          case CypherFloat(d) => vals(k).ival = java.lang.Double.doubleToRawLongBits(d)
-          case CypherBoolean(b) => vals(k).ival = if (b) 1L else 0L
-          case CypherString(s) => vals(k).ival = dictionary.encode(s)
-          case other => throw UnsupportedOperationException(s"parameter value $other on the device path")
-        }
-        vals(k).write()
-      }
+      val (ty, vals) = typedValues(items)
       ps(i).`type` = ty; ps(i).is_list = if (isList) 1 else 0; ps(i).count = items.size
       ps(i).values = vals(0).getPointer; ps(i).write()
     }

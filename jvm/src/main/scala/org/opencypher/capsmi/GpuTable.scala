@@ -17,7 +17,8 @@ import com.sun.jna.Pointer
 import com.sun.jna.ptr.{IntByReference, LongByReference}
 import org.opencypher.okapi.api.types._
 import org.opencypher.okapi.api.value.CypherValue
-import org.opencypher.okapi.api.value.CypherValue.{CypherList, CypherMap, CypherValue}
+import org.opencypher.okapi.api.value.CypherValue.{CypherBoolean, CypherInteger, CypherList, CypherMap, CypherNull, CypherString,
+  CypherValue}
 import org.opencypher.okapi.impl.exception.{IllegalArgumentException, NotImplementedException}
 import org.opencypher.okapi.ir.api.expr._
 import org.opencypher.okapi.relational.api.table.Table
@@ -207,9 +208,51 @@ final class GpuTable private (val handle: Pointer)(implicit val session: GpuSess
   /** SparkTable.scala:69-88: every expression is evaluated against this table; a name that exists
     * is replaced in place. */
   override def withColumns(columns: (Expr, String)*)(implicit header: RecordHeader, parameters: CypherMap): GpuTable = {
+    // UNWIND arrives here as Explode(list) AS item (RelationalPlanner.scala:94-96): one generator per call, as
+    // the whole expression of its column; the columns before and after it are added around it, in order
+    def hasExplode(e: Expr): Boolean = e match {
+      case _: Explode => true
+      case other => other.children.exists(hasExplode)
+    }
+    val at = columns.indexWhere { case (e, _) => hasExplode(e) }
+    if (at >= 0) {
+      if (columns.count { case (e, _) => hasExplode(e) } > 1)
+        throw NotImplementedException("more than one Explode in one withColumns")
+      val (before, rest) = columns.splitAt(at)
+      val exploded = (if (before.isEmpty) this else withColumns(before: _*)).explodeColumn(rest.head._1, rest.head._2)
+      return if (rest.tail.isEmpty) exploded else exploded.withColumns(rest.tail: _*)
+    }
     val compiler = ExprCompiler(this, header, parameters)
     val progs = columns.map { case (e, name) => name -> compiler.compile(e) }
     wrap(I.capsmi_with_columns(handle, progs.size, CapsmiLib.exprColumns(progs), _))
+  }
+
+  /** functions.explode (SparkSQLExprMapper.scala:237-241) of a list column (capsmi_explode), or of a ListLit /
+    * list parameter (functions.array of the literals, :86-89, 111-112; capsmi_explode_values). */
+  private def explodeColumn(e: Expr, item: String)(implicit header: RecordHeader, parameters: CypherMap): GpuTable = {
+    def values(items: Seq[CypherValue]): GpuTable = {
+      val (ty, vals) = session.typedValues(items)
+      wrap(I.capsmi_explode_values(handle, ty, items.size, vals(0), item, _))
+    }
+    def literal(x: Expr): CypherValue = x match {
+      case IntegerLit(v) => CypherInteger(v)
+      case StringLit(v) => CypherString(v)
+      case b: BoolLit => CypherBoolean(b.v)
+      case _: NullLit => CypherNull
+      case other => throw NotImplementedException(s"list element $other on the device path")
+    }
+    e match {
+      case Explode(ListLit(vs)) => values(vs.map(literal))
+      case Explode(p: Param) if !header.contains(p) =>
+        parameters.getOrElse(p.name, throw IllegalArgumentException(s"a value for parameter $$${p.name}", "none")) match {
+          case CypherList(xs) => values(xs)
+          case other => throw IllegalArgumentException("a list parameter", other)
+        }
+      case Explode(list) if header.contains(list) && physicalColumns.contains(header.column(list)) =>
+        wrap(I.capsmi_explode(handle, header.column(list), item, _))
+      case Explode(p: Property) if !header.contains(p) => values(Seq.empty) // a missing property: a null list, no rows
+      case other => throw NotImplementedException(s"$other on the device path: Explode of a list column, ListLit or list parameter")
+    }
   }
 
   override def withColumnRenamed(oldColumn: String, newColumn: String): GpuTable =
