@@ -471,6 +471,7 @@ struct PartLayout {
 struct ChunkPart {
     PartLayout L;
     Buf pool, meta, chist, jbuf;
+    bool has_hist = false;       // chist holds the chunks' cell-count rows (pass 1 with want_hist, or k_chunk_hist)
     int64_t pool_chunks = 0, npool = 1, mtot = 0, g2 = 1;
     int64_t* jst = nullptr;      // nt + 1 chunk offsets per bucket in `order`
     int64_t* segbase = nullptr;  // g2 + 1

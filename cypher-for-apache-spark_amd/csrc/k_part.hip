@@ -37,15 +37,18 @@ namespace part {
 // its tiles' runs to it; a full chunk is retired and the next one taken from the workgroup's own
 // range of the pool (a block with T tiles fills at most T chunks and leaves at most one open per
 // slice, so T + nt chunks suffice and no global atomic sits in the tile loop).  Chunk metadata
-// records (slice, fill); fill 0 = unused.  Each open chunk also counts its pairs per source slice
-// (16-bit LDS counters, nt x ns of them = one per 2-D cell), written out as the chunk's cell
-// histogram when it is retired; pass 2 derives exact output offsets from those.  The next tile's
-// loads are issued before this tile is regrouped and written.
+// records (slice, fill); fill 0 = unused.  With HIST each open chunk also counts its pairs per source
+// slice (16-bit LDS counters, nt x ns of them = one per 2-D cell), written out as the chunk's cell
+// histogram when it is retired; pass 2 derives exact output offsets from those.  Callers whose
+// consumers walk the pool (the cold 2-hop's pool hops, C5's partitions) run HIST = false, and a pool
+// that comes to need the rows after all gets them from k_chunk_hist.  The next tile's loads are
+// issued before this tile is regrouped and written.
 
 
 
-__host__ __device__ constexpr size_t scatter1_lds(int nb, int ns, int block = kP1Block, int tile = kP1Tile) {
-    return sizeof(uint2) * tile + sizeof(uint32_t) * ((size_t)nb * hist_words(ns) + 7 * (size_t)nb + block / 64 + 4);
+__host__ __device__ constexpr size_t scatter1_lds(int nb, int ns, bool hist, int block = kP1Block, int tile = kP1Tile) {
+    return sizeof(uint2) * tile +
+           sizeof(uint32_t) * ((hist ? (size_t)nb * hist_words(ns) : 0) + 7 * (size_t)nb + block / 64 + 4);
 }
 
 // chunks per pass-1 block: tiles of the busiest block + one open chunk per slice
@@ -57,7 +60,8 @@ __device__ __forceinline__ void hist_add(uint32_t* H, int hw, int b, uint32_t i)
     atomicAdd(&H[b * hw + (int)(i >> 1)], 1u << ((i & 1u) * 16u));
 }
 
-template <int B, int IT, int MINW, bool NTS>  // MINW: waves per SIMD to fit
+// HIST = false: no cell counts (no H, no chist rows); k_chunk_hist makes the rows when something asks for them
+template <int B, int IT, int MINW, bool NTS, bool HIST>  // MINW: waves per SIMD to fit
 __global__ void __launch_bounds__(B, MINW) k_scatter_c(const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
                                                        int64_t m, Layout L, int swap, int64_t chunk0, size_t trash,
                                                        uint2* __restrict__ pool, unsigned long long* __restrict__ cmeta,
@@ -68,7 +72,7 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_c(const int64_t* __restrict
     const int nb = L.nt, hw = hist_words(L.ns);
     uint2* stage = reinterpret_cast<uint2*>(smem);
     uint32_t* H = reinterpret_cast<uint32_t*>(stage + T);  // nb rows of hw words: open chunks' cell counts
-    uint32_t* cnt = H + (size_t)nb * hw;  // this tile's run length per slice
+    uint32_t* cnt = H + (HIST ? (size_t)nb * hw : 0);  // this tile's run length per slice
     uint32_t* loc = cnt + nb;             // run start in the stage
     uint32_t* ph = loc + nb;              // open chunk per slice (kNone: none yet) ...
     uint32_t* fl = ph + nb;               // ... and its fill, both as of the start of the tile
@@ -76,7 +80,8 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_c(const int64_t* __restrict
     uint32_t* opened = p1 + nb;           // slices that opened a chunk in this tile
     uint32_t* wtot = opened + nb;
     uint32_t* misc = wtot + B / 64;  // [0] chunks opened this tile, [1] next free chunk
-    for (int i = threadIdx.x; i < nb * hw; i += B) H[i] = 0;
+    if (HIST)
+        for (int i = threadIdx.x; i < nb * hw; i += B) H[i] = 0;
     for (int i = threadIdx.x; i < nb; i += B) {
         ph[i] = kNone;
         fl[i] = 0;
@@ -135,7 +140,7 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_c(const int64_t* __restrict
             const int b = min((int)(p.y >> L.tbits), nb - 1);  // stale stage entries past `total`
             const uint32_t r = idx - loc[b], o = ph[b], room = o == kNone ? 0u : (uint32_t)kCh - fl[b];
             const bool first = r < room;
-            if (idx < total && first) hist_add(H, hw, b, p.x >> L.sbits);
+            if (HIST && idx < total && first) hist_add(H, hw, b, p.x >> L.sbits);
             const size_t at = idx >= total ? trash + threadIdx.x
                             : first       ? (size_t)o * kCh + fl[b] + r
                                           : (size_t)p1[b] * kCh + (r - room);
@@ -146,7 +151,7 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_c(const int64_t* __restrict
                 pool[at] = p;
         }
         const uint32_t nop = misc[0];
-        if (nop) {  // block-uniform: retire the filled chunks (histogram row out), count the runs' tails
+        if (HIST && nop) {  // block-uniform: retire the filled chunks (histogram row out), count the runs' tails
             __syncthreads();
             for (uint32_t x = threadIdx.x; x < nop * (uint32_t)hw; x += B) {
                 const int b = (int)opened[x / hw], w = (int)(x % hw);
@@ -183,10 +188,11 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_c(const int64_t* __restrict
     __syncthreads();
     for (int i = threadIdx.x; i < nb; i += B)
         if (ph[i] != kNone) cmeta[ph[i]] = chunk_meta(i, fl[i]);
-    for (int x = threadIdx.x; x < nb * hw; x += B) {
-        const uint32_t p = ph[x / hw];
-        if (p != kNone) chist[(size_t)p * hw + x % hw] = H[x];
-    }
+    if (HIST)
+        for (int x = threadIdx.x; x < nb * hw; x += B) {
+            const uint32_t p = ph[x / hw];
+            if (p != kNone) chist[(size_t)p * hw + x % hw] = H[x];
+        }
 }
 
 // ---- pass 1, whole-line variant (used when its LDS fits: <= 128 target slices at 2^19 ids) -------
@@ -221,28 +227,31 @@ constexpr int kLine = 16;  // pairs per 128-byte line
 __device__ __forceinline__ uint32_t held(uint32_t o, uint32_t f) { return o == kNone ? 0u : (f & (kLine - 1)); }
 
 // wave 0: retire the chunks the previous tile filled, add its runs' tails to the opened chunks'
-// histogram rows, advance the open chunks and clear the previous run lengths `cp`
+// histogram rows (HIST), advance the open chunks and clear the previous run lengths `cp`
+template <bool HIST>
 __device__ __forceinline__ void p1l_settle(const Layout& L, int hw, const uint2* stage, uint32_t* H, uint32_t* cp,
                                            const uint32_t* loc, uint32_t* ph, uint32_t* fl, const uint32_t* p1,
                                            const uint32_t* opened, uint32_t* misc, unsigned long long* cmeta,
                                            uint32_t* chist) {
     const int nb = L.nt, lane = threadIdx.x & 63;
     const uint32_t nop = misc[0];
-    for (uint32_t x = lane; x < nop * (uint32_t)hw; x += 64) {
-        const int b = (int)opened[x / hw], w = (int)(x % hw);
-        if (ph[b] != kNone) {
-            chist[(size_t)ph[b] * hw + w] = H[b * hw + w];
-            H[b * hw + w] = 0;
+    if (HIST) {
+        for (uint32_t x = lane; x < nop * (uint32_t)hw; x += 64) {
+            const int b = (int)opened[x / hw], w = (int)(x % hw);
+            if (ph[b] != kNone) {
+                chist[(size_t)ph[b] * hw + w] = H[b * hw + w];
+                H[b * hw + w] = 0;
+            }
         }
+        wave_lds_order();
+        for (uint32_t k = 0; k < nop; ++k) {  // items past the old chunk's room belong to the opened one
+            const int b = (int)opened[k];
+            const uint32_t h = held(ph[b], fl[b]);
+            const uint32_t room = ph[b] == kNone ? 0u : (uint32_t)kCh - (fl[b] - h);
+            for (uint32_t r = room + lane; r < h + cp[b]; r += 64) hist_add(H, hw, b, stage[loc[b] + r].x >> L.sbits);
+        }
+        wave_lds_order();
     }
-    wave_lds_order();
-    for (uint32_t k = 0; k < nop; ++k) {  // items past the old chunk's room belong to the opened one
-        const int b = (int)opened[k];
-        const uint32_t h = held(ph[b], fl[b]);
-        const uint32_t room = ph[b] == kNone ? 0u : (uint32_t)kCh - (fl[b] - h);
-        for (uint32_t r = room + lane; r < h + cp[b]; r += 64) hist_add(H, hw, b, stage[loc[b] + r].x >> L.sbits);
-    }
-    wave_lds_order();
     for (int i = lane; i < nb; i += 64) {
         const uint32_t c = cp[i];
         if (!c) continue;
@@ -262,10 +271,25 @@ __device__ __forceinline__ void p1l_settle(const Layout& L, int hw, const uint2*
     wave_lds_order();
 }
 
+// What the regroup and the store loop need per slice, worked out once per tile by wave 0 instead of per item
+// from loc / ph / fl / cn / p1.  Staged item r of slice b (r = index - loc) goes to logical position w + r of
+// the open chunk (w = its written prefix) while r < room, else to position r - room of the opened chunk;
+// positions below the landing chunk's last complete line (cut) are stored, the rest held back.
+//   x: loc | room << 16        y: w / kLine | cut(open) / kLine << 10 | cut(opened) / kLine << 20
+//   z: the open chunk          w: the chunk this tile's run opens
+__device__ __forceinline__ uint4 p1l_pack(uint32_t loc, uint32_t c, uint32_t o, uint32_t f, uint32_t np) {
+    const uint32_t h = held(o, f), w = f - h, room = o == kNone ? 0u : (uint32_t)kCh - w;
+    const uint32_t cut0 = min(w + h + c, (uint32_t)kCh) / kLine, cut1 = h + c > room ? (h + c - room) / kLine : 0u;
+    return make_uint4(loc | room << 16, w / kLine | cut0 << 10 | cut1 << 20, o, np);
+}
+static_assert(kCh / kLine < 1024 && kCh < 65536, "p1l_pack fields");
+
 // wave 0: run starts `loc` of this tile (exclusive scan over each slice's staged sequence = held
-// items + run), the chunks its runs open (p1, opened, misc[0]) and the staged total (misc[2])
+// items + run), where each run itself starts (base = loc + held), the chunks its runs open (p1, opened,
+// misc[0]), the store loop's per-slice words (Q) and the staged total (misc[2])
 __device__ __forceinline__ void p1l_plan(int nb, const uint32_t* cn, uint32_t* loc, const uint32_t* ph,
-                                         const uint32_t* fl, uint32_t* p1, uint32_t* opened, uint32_t* misc) {
+                                         const uint32_t* fl, uint32_t* p1, uint32_t* opened, uint32_t* misc,
+                                         uint32_t* base, uint4* Q) {
     const int lane = threadIdx.x & 63;
     const int per = (nb + 63) / 64, b0 = lane * per, b1 = min(b0 + per, nb);
     uint32_t sum = 0, need = 0;
@@ -278,15 +302,17 @@ __device__ __forceinline__ void p1l_plan(int nb, const uint32_t* cn, uint32_t* l
     uint32_t pre = is - sum, k = in - need;
     const uint32_t nf = misc[1];
     for (int i = b0; i < b1; ++i) {
-        const uint32_t c = cn[i];
+        const uint32_t c = cn[i], o = ph[i], f = fl[i];
         loc[i] = pre;
-        pre += c + held(ph[i], fl[i]);
+        base[i] = pre + held(o, f);
         uint32_t np = kNone;
-        if (c && (ph[i] == kNone || fl[i] + c > (uint32_t)kCh)) {
+        if (c && (o == kNone || f + c > (uint32_t)kCh)) {
             np = nf + k;
             opened[k++] = (uint32_t)i;
         }
         p1[i] = np;
+        Q[i] = p1l_pack(pre, c, o, f, np);
+        pre += c + held(o, f);
     }
     if (lane == 63) {
         misc[0] = in;
@@ -295,12 +321,12 @@ __device__ __forceinline__ void p1l_plan(int nb, const uint32_t* cn, uint32_t* l
     wave_lds_order();
 }
 
-__host__ __device__ constexpr size_t scatter1l_lds(int nb, int ns, int block, int tile) {
+__host__ __device__ constexpr size_t scatter1l_lds(int nb, int ns, bool hist, int block, int tile) {
     return sizeof(uint2) * ((size_t)tile + (size_t)nb * (2 * kLine)) +
-           sizeof(uint32_t) * ((size_t)nb * hist_words(ns) + 7 * (size_t)nb + block / 64 + 4);
+           sizeof(uint32_t) * ((hist ? (size_t)nb * hist_words(ns) : 0) + 12 * (size_t)nb + block / 64 + 4);
 }
 
-template <int B, int IT, int MINW, bool NTL = false, bool NTS = false>
+template <int B, int IT, int MINW, bool HIST, bool NTL = false, bool NTS = false>
 __global__ void __launch_bounds__(B, MINW) k_scatter_l(const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
                                                       int64_t m, Layout L, int swap, int64_t chunk0, size_t trash,
                                                       uint2* __restrict__ pool, unsigned long long* __restrict__ cmeta,
@@ -311,15 +337,18 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_l(const int64_t* __restrict
     const int nb = L.nt, hw = hist_words(L.ns);
     uint2* stage = reinterpret_cast<uint2*>(smem);    // T + nb * kLine: runs behind their held items
     uint2* hold = stage + T + (size_t)nb * kLine;      // nb x kLine held items
-    uint32_t* H = reinterpret_cast<uint32_t*>(hold + (size_t)nb * kLine);
-    uint32_t* cnt = H + (size_t)nb * hw;
-    uint32_t* loc = cnt + 2 * nb;
+    uint4* Q = reinterpret_cast<uint4*>(hold + (size_t)nb * kLine);  // p1l_pack, 16-byte aligned
+    uint32_t* H = reinterpret_cast<uint32_t*>(Q + nb);
+    uint32_t* cnt = H + (HIST ? (size_t)nb * hw : 0);
+    uint32_t* base = cnt + 2 * nb;
+    uint32_t* loc = base + nb;
     uint32_t* ph = loc + nb;
     uint32_t* fl = ph + nb;  // logical fill of the open chunk (held items included)
     uint32_t* p1 = fl + nb;
     uint32_t* opened = p1 + nb;
     uint32_t* misc = opened + nb;
-    for (int i = threadIdx.x; i < nb * hw; i += B) H[i] = 0;
+    if (HIST)
+        for (int i = threadIdx.x; i < nb * hw; i += B) H[i] = 0;
     for (int i = threadIdx.x; i < nb; i += B) {
         cnt[i] = 0;
         cnt[nb + i] = 0;
@@ -359,41 +388,34 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_l(const int64_t* __restrict
             if ((valid >> u) & 1u) rk[u] = atomicAdd(&cn[pr[u].y >> L.tbits], 1u);
         __syncthreads();
         if (threadIdx.x < 64) {
-            if (pending) p1l_settle(L, hw, stage, H, cnt + (par ^ 1) * nb, loc, ph, fl, p1, opened, misc, cmeta, chist);
-            p1l_plan(nb, cn, loc, ph, fl, p1, opened, misc);
+            if (pending) p1l_settle<HIST>(L, hw, stage, H, cnt + (par ^ 1) * nb, loc, ph, fl, p1, opened, misc, cmeta, chist);
+            p1l_plan(nb, cn, loc, ph, fl, p1, opened, misc, base, Q);
         }
         __syncthreads();
         pending = true;
         const uint32_t total = misc[2];
         for (int x = threadIdx.x; x < nb * kLine; x += B) {  // held items first
             const int b = x / kLine, k = x % kLine;
-            if ((uint32_t)k < held(ph[b], fl[b])) stage[loc[b] + k] = hold[x];
+            if ((uint32_t)k < base[b] - loc[b]) stage[loc[b] + k] = hold[x];
         }
 #pragma unroll
         for (int u = 0; u < IT; ++u)
-            if ((valid >> u) & 1u) {
-                const int b = pr[u].y >> L.tbits;
-                stage[loc[b] + held(ph[b], fl[b]) + rk[u]] = pr[u];
-            }
+            if ((valid >> u) & 1u) stage[base[pr[u].y >> L.tbits] + rk[u]] = pr[u];
         __syncthreads();
-        // staged item r of slice b: logical position w + r of chunk ph[b] (w = written prefix) while
-        // it fits, else position r - room of the opened chunk p1[b]; positions below the chunk's
-        // last complete line are stored, the rest held back
+        // staged item r of slice b lands as p1l_pack lays out; one 16-byte LDS read per item
         for (uint32_t idx = threadIdx.x; idx < (uint32_t)(T + nb * kLine); idx += B) {
             const uint2 p = stage[idx];
             const int b = min((int)(p.y >> L.tbits), nb - 1);
-            const uint32_t r = idx - loc[b], o = ph[b], f = fl[b], h = held(o, f), c = cn[b];
-            const uint32_t w = f - h, room = o == kNone ? 0u : (uint32_t)kCh - w;
+            const uint4 q = Q[b];
+            const uint32_t r = idx - (q.x & 0xFFFFu), room = q.x >> 16, w = (q.y & 1023u) * kLine;
             const bool first = r < room;
-            if (idx < total && first && r >= h) hist_add(H, hw, b, p.x >> L.sbits);
-            // end of the sequence in the chunk it lands in, and that chunk's stored prefix
-            const uint32_t end = first ? min(w + h + c, (uint32_t)kCh) : h + c - room;
+            if (HIST && idx < total && first && r >= base[b] - loc[b]) hist_add(H, hw, b, p.x >> L.sbits);
             const uint32_t pos = first ? w + r : r - room;
-            const uint32_t cut = end & ~(uint32_t)(kLine - 1);
+            const uint32_t cut = ((first ? q.y >> 10 : q.y >> 20) & 1023u) * kLine;
             if (idx >= total) {
                 break;  // idx only grows
             } else if (pos < cut) {
-                uint2* d = pool + (size_t)(first ? o : p1[b]) * kCh + pos;
+                uint2* d = pool + (size_t)(first ? q.z : q.w) * kCh + pos;
                 if (NTS)
                     __builtin_nontemporal_store(*reinterpret_cast<const unsigned long long*>(&p),
                                                 reinterpret_cast<unsigned long long*>(d));
@@ -406,7 +428,7 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_l(const int64_t* __restrict
     }
     __syncthreads();
     if (pending && threadIdx.x < 64)
-        p1l_settle(L, hw, stage, H, cnt + (par ^ 1) * nb, loc, ph, fl, p1, opened, misc, cmeta, chist);
+        p1l_settle<HIST>(L, hw, stage, H, cnt + (par ^ 1) * nb, loc, ph, fl, p1, opened, misc, cmeta, chist);
     __syncthreads();
     for (int x = threadIdx.x; x < nb * kLine; x += B) {  // held tails
         const int b = x / kLine, k = x % kLine;
@@ -414,9 +436,42 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_l(const int64_t* __restrict
     }
     for (int i = threadIdx.x; i < nb; i += B)
         if (ph[i] != kNone) cmeta[ph[i]] = chunk_meta(i, fl[i]);
-    for (int x = threadIdx.x; x < nb * hw; x += B) {
-        const uint32_t p = ph[x / hw];
-        if (p != kNone) chist[(size_t)p * hw + x % hw] = H[x];
+    if (HIST)
+        for (int x = threadIdx.x; x < nb * hw; x += B) {
+            const uint32_t p = ph[x / hw];
+            if (p != kNone) chist[(size_t)p * hw + x % hw] = H[x];
+        }
+}
+
+// The cell-count rows of a pool whose pass 1 ran without them (HIST = false): one wave per used chunk counts
+// the chunk's pairs per source slice (16-bit LDS counters) and writes the row pass 1 would have written.
+constexpr int kHistBlock = 256;
+
+__global__ void __launch_bounds__(kHistBlock) k_chunk_hist(const uint2* __restrict__ pool,
+                                                           const unsigned long long* __restrict__ cmeta,
+                                                           int64_t nchunks, int ns, int sbits,
+                                                           uint32_t* __restrict__ chist) {
+    constexpr int W = kHistBlock / 64;
+    __shared__ uint32_t rows[W][64];  // hist_words(ns) <= 64
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, hw = hist_words(ns);
+    uint32_t* h = rows[wave];
+    for (int64_t q = (int64_t)blockIdx.x * W + wave; q < nchunks; q += (int64_t)gridDim.x * W) {  // wave-uniform
+        const uint32_t fill = (uint32_t)(cmeta[q] >> 32);
+        if (!fill) continue;
+        h[lane] = 0;
+        wave_lds_order();
+        const uint2* __restrict__ c = pool + (size_t)q * kCh;
+        for (uint32_t i0 = 0; i0 < fill; i0 += 256) {  // four loads in flight per lane
+            uint32_t x[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) x[k] = c[min(i0 + (uint32_t)(k * 64 + lane), fill - 1)].x;
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (i0 + (uint32_t)(k * 64 + lane) < fill) hist_add(h, hw, 0, x[k] >> sbits);
+        }
+        wave_lds_order();
+        if (lane < hw) chist[(size_t)q * hw + lane] = h[lane];
+        wave_lds_order();
     }
 }
 
@@ -1178,10 +1233,13 @@ static void allow_lds(K kernel, size_t bytes) {
 }
 
 void chunk_partition(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
-                     int nt, bool swap, const part::Layout& L, int64_t g2_want, ChunkPart& cp) {
+                     int nt, bool swap, const part::Layout& L, int64_t g2_want, ChunkPart& cp, bool want_hist) {
     using namespace part;
     hipStream_t st = s->stream;
     cp.L = L;
+    // the whole-line variant where its LDS fits with the cell counts (the choice does not follow want_hist:
+    // the pool of a layout is the same whoever asks for it)
+    const bool lines = scatter1l_lds(L.nt, L.ns, true, kP1Block, kP1Tile) <= (size_t)160 * 1024;
     // pass 1 grid: one 1024-lane block per CU, fewer for small inputs so the open chunks
     // (blocks x slices) stay within a few times the filled ones
     std::vector<int> g1(nt, 0);
@@ -1211,27 +1269,21 @@ void chunk_partition(capsmi_session* s, const int64_t* const* srcs, const int64_
     const int hw = hist_words(L.ns);
     cp.pool = dev_alloc(sizeof(uint2) * kCh * (size_t)(npool + 1), s);  // + a trash chunk
     cp.meta = dev_alloc(sizeof(unsigned long long) * npool, s);
-    cp.chist = dev_alloc(sizeof(uint32_t) * hw * (size_t)npool, s);
+    cp.has_hist = want_hist;
+    if (want_hist) cp.chist = dev_alloc(sizeof(uint32_t) * hw * (size_t)npool, s);
     // (clearing each block's metadata range inside pass 1 instead measured 5.25 -> 5.39 ms at C3: the fill stays)
     HIP_CHECK(hipMemsetAsync(P<void>(cp.meta), 0, sizeof(unsigned long long) * npool, st));
-    const size_t lds1l = scatter1l_lds(L.nt, L.ns, kP1Block, kP1Tile);
-    const bool lines = lds1l <= (size_t)160 * 1024;
-    const size_t lds1 = lines ? lds1l : scatter1_lds(L.nt, L.ns);
-    if (lines)
-        allow_lds(k_scatter_l<kP1Block, kItems, 4>, lds1);
-    else
-        allow_lds(k_scatter_c<kP1Block, kItems, 4, kP1NT>, lds1);
+    const size_t lds1 = lines ? scatter1l_lds(L.nt, L.ns, want_hist, kP1Block, kP1Tile) : scatter1_lds(L.nt, L.ns, want_hist);
+    auto k1 = lines ? (want_hist ? k_scatter_l<kP1Block, kItems, 4, true> : k_scatter_l<kP1Block, kItems, 4, false>)
+                    : (want_hist ? k_scatter_c<kP1Block, kItems, 4, kP1NT, true>
+                                 : k_scatter_c<kP1Block, kItems, 4, kP1NT, false>);
+    allow_lds(k1, lds1);
     for (int i = 0; i < nt; ++i) {
         if (ms[i] <= 0) continue;
         KernelTimer kt(s, "part_scatter1");
-        if (lines)
-            hipLaunchKernelGGL((k_scatter_l<kP1Block, kItems, 4>), dim3(g1[i]), dim3(kP1Block), lds1, st, srcs[i], dsts[i],
-                               ms[i], L, swap ? 1 : 0, c0[i], (size_t)npool * kCh, P<uint2>(cp.pool),
-                               P<unsigned long long>(cp.meta), P<uint32_t>(cp.chist));
-        else
-            hipLaunchKernelGGL((k_scatter_c<kP1Block, kItems, 4, kP1NT>), dim3(g1[i]), dim3(kP1Block), lds1, st, srcs[i],
-                               dsts[i], ms[i], L, swap ? 1 : 0, c0[i], (size_t)npool * kCh, P<uint2>(cp.pool),
-                               P<unsigned long long>(cp.meta), P<uint32_t>(cp.chist));
+        hipLaunchKernelGGL(k1, dim3(g1[i]), dim3(kP1Block), lds1, st, srcs[i], dsts[i], ms[i], L, swap ? 1 : 0, c0[i],
+                           (size_t)npool * kCh, P<uint2>(cp.pool), P<unsigned long long>(cp.meta),
+                           want_hist ? P<uint32_t>(cp.chist) : nullptr);
     }
     HIP_CHECK(hipGetLastError());
     cp.mtot = mtot;
@@ -1346,7 +1398,9 @@ void relpart_build(capsmi_session* s, const int64_t* const* srcs, const int64_t*
     ChunkPart& cp = rp.cp;
     // (measured and removed in round 6: a 6-byte pass-1 pool, u32 + u16 arrays per chunk -- pass 1 5.26 ->
     // 5.58 ms, pass 2 + hop 1 3.76 -> 4.45 ms at C3; both passes are bound by their LDS / VALU phases)
-    chunk_partition(s, srcs, dsts, ms, nt, false, L, (int64_t)s->num_cus * (fuse ? 1 : 2), cp);
+    // the pool hops read no cell counts: pass 1 leaves them out, and a later reader of the cells has
+    // k_chunk_hist make them (cells_build)
+    chunk_partition(s, srcs, dsts, ms, nt, false, L, (int64_t)s->num_cus * (fuse ? 1 : 2), cp, !pool_hop);
     rp.cells = false;
     rp.sel = -1;
     rp.kept = -1;  // known on the device (boff[ncells]); read only when asked (relpart_kept)
@@ -1383,6 +1437,17 @@ static void cells_build(capsmi_session* s, RelPart& rp, const RelPartHop1* h1) {
     uint32_t* order = cp.order;
     Buf& pool = cp.pool;
     Buf& meta = cp.meta;
+    if (!cp.has_hist) {  // pass 1 ran without the cell counts: one more read of the pool
+        cp.chist = dev_alloc(sizeof(uint32_t) * hist_words(L.ns) * (size_t)cp.npool, s);
+        const unsigned hg = (unsigned)std::max<int64_t>(
+            1, std::min<int64_t>((int64_t)s->num_cus * 8, (cp.pool_chunks + kHistBlock / 64 - 1) / (kHistBlock / 64)));
+        KernelTimer kt(s, "part_chunk_hist");
+        hipLaunchKernelGGL(k_chunk_hist, dim3(hg), dim3(kHistBlock), 0, st, P<uint2>(cp.pool),
+                           P<unsigned long long>(cp.meta), cp.pool_chunks, L.ns, L.sbits, P<uint32_t>(cp.chist));
+        HIP_CHECK(hipGetLastError());
+        cp.has_hist = true;
+        s->routes["chunk_hist"] += 1;
+    }
     Buf& chist = cp.chist;
     Buf pbuf = dev_alloc(sizeof(uint32_t) * (size_t)maxg * L.ns, s);
     uint32_t* psum = P<uint32_t>(pbuf);

@@ -1147,7 +1147,7 @@ int64_t var_length_count(capsmi_session* s, const int64_t* const* srcs, const in
         ChunkPart cp, ct;
         {
             KernelTimer kt(s, "varlen_part");
-            chunk_partition(s, srcs, dsts, ms, nt, true, L, s->num_cus, cp);
+            chunk_partition(s, srcs, dsts, ms, nt, true, L, s->num_cus, cp, false);
         }
         const ChunkWalk cw{P<uint2>(cp.pool), P<unsigned long long>(cp.meta), cp.order, cp.jst, cp.segbase, cp.ja, L.nt};
         const unsigned g = (unsigned)cp.g2;
@@ -1164,7 +1164,7 @@ int64_t var_length_count(capsmi_session* s, const int64_t* const* srcs, const in
             // LDS while k_vl_bset builds it), so a slice with more pairs gets 2^sublog regions, one
             // more k_vl_bset pass each
             KernelTimer kt(s, "varlen_rev");
-            chunk_partition(s, srcs, dsts, ms, nt, false, L, s->num_cus, ct);
+            chunk_partition(s, srcs, dsts, ms, nt, false, L, s->num_cus, ct, false);
             const int64_t per_slice = (mtot + L.nt - 1) / L.nt;
             // 8 bits per pair (config CAPSMI_VL_BITS), in 2^sublog regions of <= 2^20 bits per slice
             const int64_t bits_per = s->cfg.vl_bits;
@@ -1397,7 +1397,7 @@ VarlenShard* varlen_shard_begin(capsmi_session* s, const int64_t* const* srcs, c
     if (mout > 0) {
         {
             KernelTimer kt(s, "varlen_part");
-            chunk_partition(s, srcs, dsts, ms, nt, true, L, s->num_cus, v->cp);
+            chunk_partition(s, srcs, dsts, ms, nt, true, L, s->num_cus, v->cp, false);
         }
         const ChunkWalk cw{P<uint2>(v->cp.pool), P<unsigned long long>(v->cp.meta), v->cp.order, v->cp.jst,
                            v->cp.segbase, v->cp.ja, L.nt};
@@ -1419,7 +1419,7 @@ VarlenShard* varlen_shard_begin(capsmi_session* s, const int64_t* const* srcs, c
         ChunkPart ct;
         KernelTimer kt(s, "varlen_rev");
         std::unique_ptr<KernelTimer> sub(new KernelTimer(s, "vls_rev_part"));
-        chunk_partition(s, as.data(), ad.data(), am.data(), na, false, L, s->num_cus, ct);
+        chunk_partition(s, as.data(), ad.data(), am.data(), na, false, L, s->num_cus, ct, false);
         sub.reset(new KernelTimer(s, "vls_rev_bloom"));
         const int64_t per_slice = (mall + L.nt - 1) / L.nt;
         int rshift = 10;

@@ -15,8 +15,9 @@ constexpr int kItems = 8;                        // relationships per lane per t
 constexpr int kSBlock = 1024;                    // scatter workgroups
 constexpr int kTile = kSBlock * kItems;          // relationships per scatter tile (8192)
 constexpr int kCh = kTile;                       // pairs per pass-1 chunk: a tile's run spans <= 2 chunks
-constexpr int kP1Block = 1024;                   // pass-1 workgroup (512 x 2 per CU measured slower; 768 lanes
-                                                 // with 134 VGPRs, round 6: pass 1 5.25 -> 5.97 ms at C3)
+constexpr int kP1Block = 1024;                   // pass-1 workgroup (512 x 2 per CU measured slower, again in round 8
+                                                 // without the cell counts: DESIGN §9; 768 lanes with 134 VGPRs,
+                                                 // round 6: pass 1 5.25 -> 5.97 ms at C3)
 constexpr int kP1Tile = kP1Block * kItems;       // pass-1 tile (<= kCh)
 static_assert(kP1Tile <= kCh, "a pass-1 run must span at most two chunks");
 constexpr bool kP1NT = false;                    // pass-1 pool stores non-temporal
@@ -338,9 +339,11 @@ __device__ __forceinline__ bool owns_slice(const ChunkWalk& cw, int j) {
 
 }  // namespace part
 
-// ChunkPart (capsmi_impl.h): pass 1 of the partition, the chunk ordering and the segment split
+// ChunkPart (capsmi_impl.h): pass 1 of the partition, the chunk ordering and the segment split.
+// want_hist: pass 1 also counts every chunk's pairs per source slice (cp.chist, read by pass 2 of the 2-D
+// layout); callers whose consumers walk the pool pass false.
 void chunk_partition(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
-                     int nt, bool swap, const part::Layout& L, int64_t g2, ChunkPart& cp);
+                     int nt, bool swap, const part::Layout& L, int64_t g2, ChunkPart& cp, bool want_hist);
 // the ordering half of chunk_partition for a pool another kernel filled (cp.meta: bucket | fill << 32)
 void chunk_order(capsmi_session* s, int nt, int64_t pool_chunks, int64_t g2, ChunkPart& cp);
 
