@@ -5,6 +5,10 @@
 // with Spark SQL three-valued logic:
 //   - comparisons with a NULL operand are NULL; comparisons between incomparable
 //     types (Long vs String, ...) are NULL (Spark casts the string and gets null);
+//   - a Long compared with a Double is cast to Double first (2^53 + 1 = 2^53.0 is TRUE);
+//   - NaN follows Spark SQL's documented "NaN Semantics": NaN = NaN is TRUE and NaN is greater
+//     than every other number, for = <> < <= > >= and IN alike (any sign, any payload is one NaN);
+//     a comparison with NaN is therefore never NULL unless an operand is NULL;
 //   - NOT NULL = NULL; AND: any FALSE -> FALSE, else any NULL -> NULL; OR dually;
 //   - x IN (..): TRUE on a match, else NULL if x or any element is NULL, else FALSE;
 //   - Filter keeps a row iff the value is TRUE (SparkTable.scala:65-67; pinned by
@@ -43,7 +47,8 @@ __device__ __forceinline__ int cmp3(const Val& a, const Val& b) {
     if (numeric(a.t) && numeric(b.t)) {
         if (a.t == CAPSMI_I64 && b.t == CAPSMI_I64) return a.b < b.b ? -1 : (a.b > b.b ? 1 : 0);
         const double x = as_f64(a), y = as_f64(b);
-        if (x != x || y != y) return -2;
+        const bool xn = x != x, yn = y != y;  // NaN = NaN, and NaN is greater than any other number
+        if (xn || yn) return xn == yn ? 0 : (xn ? 1 : -1);
         return x < y ? -1 : (x > y ? 1 : 0);
     }
     if (a.t != b.t) return -2;
@@ -354,6 +359,7 @@ void launch_eval(capsmi_session* s, const capsmi_table* t, int32_t nn, const cap
         HIP_CHECK(hipMemcpyAsync(P<void>(dprog), prog, sizeof(capsmi_expr) * nn, hipMemcpyHostToDevice, s->stream));
     int64_t g = (n + 255) / 256;
     if (g > 8192) g = 8192;
+    KernelTimer kt(s, "expr_eval");  // counts interpreter launches (a scan whose predicate ran inline has none)
     hipLaunchKernelGGL(k_eval, dim3((unsigned)g), dim3(256), 0, s->stream, P<capsmi_expr>(dprog), nn, cp, n, out,
                        out_valid, flags);
     HIP_CHECK(hipGetLastError());

@@ -206,7 +206,10 @@ __global__ void k_agg_minmax(const int64_t* __restrict__ gid, const int64_t* __r
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t g = gid[i];
         if (g < 0 || (valid && !valid[i])) continue;
-        const long long x = is_f64 ? f64_key(v[i]) : v[i];
+        int64_t b = v[i];
+        // Spark's Min / Max order Doubles with NaN greatest and every NaN one value: canonicalise first
+        if (is_f64 && (b & 0x7FFFFFFFFFFFFFFFLL) > 0x7FF0000000000000LL) b = 0x7FF8000000000000LL;
+        const long long x = is_f64 ? f64_key(b) : b;
         if (is_max) atomicMax(&out[g], x); else atomicMin(&out[g], x);
         seen[g] = 1;
     }

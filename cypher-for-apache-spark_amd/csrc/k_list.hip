@@ -4,7 +4,10 @@
 // Device form: one stable LSD sort of the rows by (group, value) -- the value's order key first,
 // then the group id -- drops the rows that do not contribute, removes (group, value) repeats for
 // collect_set, and the per-group counts become the list offsets.  Equal values are equal 64-bit
-// words (Spark 2.2.1's collect_set hashes the raw values; -0.0 and 0.0 stay apart).
+// words, except that every Double NaN is one value: Spark 2.2.1's collect_set keeps boxed values in a
+// hash set, and Double.equals goes by doubleToLongBits, which canonicalises NaN and keeps -0.0 and 0.0
+// apart.  The sort ties all NaNs too (k_order_keys), so a group's NaNs are adjacent whatever their
+// bits; the first of them in input order is the one kept.
 #include "capsmi_impl.h"
 
 namespace capsmi {
@@ -26,14 +29,21 @@ __global__ void k_collect_gkey(const int64_t* __restrict__ perm, const int64_t* 
     }
 }
 
+// the word collect_set compares: the value's own, with every Double NaN mapped to one
+__device__ __forceinline__ int64_t set_word(int64_t b, int is_f64) {
+    return (is_f64 && (b & 0x7FFFFFFFFFFFFFFFLL) > 0x7FF0000000000000LL) ? 0x7FF8000000000000LL : b;
+}
+
 // row i of the (group, value) order is kept when it contributes and, for collect_set, differs from
 // the previous row of its group
 __global__ void k_collect_keep(const uint64_t* __restrict__ key, const int64_t* __restrict__ perm,
-                               const int64_t* __restrict__ v, int64_t n, int64_t ng, int distinct,
+                               const int64_t* __restrict__ v, int64_t n, int64_t ng, int distinct, int is_f64,
                                uint8_t* __restrict__ flags) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         bool keep = key[i] < (uint64_t)ng;
-        if (keep && distinct && i > 0 && key[i - 1] == key[i] && v[perm[i - 1]] == v[perm[i]]) keep = false;
+        if (keep && distinct && i > 0 && key[i - 1] == key[i] &&
+            set_word(v[perm[i - 1]], is_f64) == set_word(v[perm[i]], is_f64))
+            keep = false;
         flags[i] = keep ? 1 : 0;
     }
 }
@@ -71,7 +81,7 @@ std::shared_ptr<ListStore> collect_lists(capsmi_session* s, const int64_t* gid, 
     radix_sort_pairs(s, P<uint64_t>(key), P<int64_t>(perm), n, 0, bits);
     Buf flags = dev_alloc(n, s);
     hipLaunchKernelGGL(k_collect_keep, dim3(grid_for(n)), dim3(256), 0, st, P<uint64_t>(key), P<int64_t>(perm), v, n,
-                       ng, distinct ? 1 : 0, P<uint8_t>(flags));
+                       ng, distinct ? 1 : 0, type == CAPSMI_F64 ? 1 : 0, P<uint8_t>(flags));
     HIP_CHECK(hipGetLastError());
     Buf idx;
     const int64_t k = flags_to_indices(s, P<uint8_t>(flags), n, idx);

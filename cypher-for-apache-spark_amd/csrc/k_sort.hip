@@ -275,7 +275,11 @@ namespace capsmi {
 namespace {
 
 // sort key of column value at perm[i]: unsigned-order-preserving image, complemented for DESC;
-// null_pass: 1-byte key on the null flag (ASC: nulls first, DESC: nulls last -- Spark defaults)
+// null_pass: 1-byte key on the null flag (ASC: nulls first, DESC: nulls last -- Spark defaults).
+// In the value pass every null row gets one constant key, so nulls tie whatever word lies under
+// them and the later keys (sorted earlier, LSD) decide.  Every Double NaN (either sign, any payload)
+// is one value, the greatest: Spark's sort prefix takes doubleToLongBits, which canonicalises NaN,
+// and compares with nanSafeCompareDoubles.  -0.0 < 0.0 stays as the bits order them.
 __global__ void k_order_keys(const int64_t* __restrict__ col, const uint8_t* __restrict__ valid, int is_f64, int desc,
                              int null_pass, const int64_t* __restrict__ perm, int64_t n, uint64_t* __restrict__ key) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -285,8 +289,15 @@ __global__ void k_order_keys(const int64_t* __restrict__ col, const uint8_t* __r
             key[i] = desc ? (ok ? 0 : 1) : (ok ? 1 : 0);
             continue;
         }
+        if (valid != nullptr && !valid[r]) {
+            key[i] = 0;
+            continue;
+        }
         int64_t b = col[r];
-        if (is_f64) b = b ^ ((b >> 63) & 0x7FFFFFFFFFFFFFFFLL);
+        if (is_f64) {
+            if ((b & 0x7FFFFFFFFFFFFFFFLL) > 0x7FF0000000000000LL) b = 0x7FF8000000000000LL;
+            b = b ^ ((b >> 63) & 0x7FFFFFFFFFFFFFFFLL);
+        }
         const uint64_t u = (uint64_t)b ^ 0x8000000000000000ULL;
         key[i] = desc ? ~u : u;
     }

@@ -212,7 +212,8 @@ capsmi_status capsmi_session_set_profiling(capsmi_session* s, int32_t enabled);
  * microseconds of device idle each), so a timed run can bracket only the launch it reports. */
 capsmi_status capsmi_session_set_profiling_names(capsmi_session* s, const char* names);
 /* resolve pending events (synchronises) and report totals for kernel `name` ("hop1", "hop2",
- * "expand_filter", "bitmap_add", ...): launches and summed milliseconds; then the counters reset. */
+ * "expand_filter", "bitmap_add", ...; "expr_eval" is the expression interpreter, which a bitmap scan with an
+ * inline range predicate does not launch): launches and summed milliseconds; then the counters reset. */
 capsmi_status capsmi_session_kernel_time(capsmi_session* s, const char* name, int64_t* launches, double* total_ms);
 /* summed algorithmic bytes (inputs read once, outputs written once) of the timed launches of `name`,
  * for kernels that declare them (the join kernels: "direct_join_probe", "radix_join_count",

@@ -16,6 +16,9 @@ documented behaviour as CAPS relies on it):
   group: count(lit 0), count, countDistinct (nulls ignored), min, max, sum, avg,
          collect / collect(DISTINCT) as sorted lists     SparkTable.scala:121-188
   orderBy: ASC nulls first, DESC nulls last              SparkTable.scala:94-103
+The null, NaN, -0.0 and Long-overflow rules (nulls tie whatever lies under them; NaN is one value,
+equal to itself and the greatest Double in sorts, comparisons and min / max) are listed in DESIGN.md
+"Value semantics at the edges" and pinned by literals in tests/test_relational_pins_cpu.py.
 Tables here are plain numpy columns; the implementation deliberately shares nothing with the
 device code (sort/searchsorted joins instead of hash tables, np.unique instead of hashing).
 """
@@ -204,8 +207,9 @@ class NumpyTable:
         for name, order in reversed(items):  # np.lexsort: last key is primary
             c = self.cols[name]
             desc = order.lower().startswith("desc")
-            v = c.values
-            keys.append(-v if desc and c.type == F64 else (~v if desc else v))
+            u = _order_image(c)
+            # the word under a null takes no part: nulls tie, the next key (then input order) decides
+            keys.append(np.where(c.valid, ~u if desc else u, np.uint64(0)))
             # ASC: nulls first (null flag 0 sorts first); DESC: nulls last
             keys.append(np.where(c.valid, 0, 1) if desc else np.where(c.valid, 1, 0))
         idx = np.lexsort(keys) if keys else np.arange(self.n)
@@ -243,8 +247,11 @@ class NumpyTable:
                 lists = np.empty(ng, dtype=object)
                 for k in range(ng):
                     v = c.values[m & (gid == k)]
-                    if distinct:  # collect_set: equal 64-bit words are one value
-                        v = np.unique(v.view(np.int64)).view(v.dtype) if len(v) else v
+                    if distinct and len(v):  # collect_set: equal 64-bit words are one value, and so is every NaN
+                        w = v.view(np.int64)
+                        if c.type == F64:  # Double.equals: doubleToLongBits makes all NaNs one, keeps -0.0 from 0.0
+                            w = np.where(np.isnan(v), np.int64(0x7FF8000000000000), w)
+                        v = np.unique(w).view(v.dtype)
                     lists[k] = np.sort(v, kind="stable")
                 out[name] = Col_(LIST + c.type, lists, np.ones(ng, dtype=bool))
                 continue
@@ -266,7 +273,8 @@ class NumpyTable:
                 if kind == "sum":
                     if c.type == F64:
                         acc = np.zeros(ng, dtype=np.float64)
-                        np.add.at(acc, g, vals)
+                        with np.errstate(over="ignore", invalid="ignore"):  # inf + -inf is NaN, not an error
+                            np.add.at(acc, g, vals)
                     else:
                         acc = np.zeros(ng, dtype=np.int64)
                         np.add.at(acc, g, vals)  # wraps like Spark Long sums
@@ -281,12 +289,22 @@ class NumpyTable:
                         out[name] = Col_(I64, np.trunc(res).astype(np.int64), seen)
                     else:
                         out[name] = Col_(F64, res, seen)
-                else:
-                    if c.type == F64:
-                        acc = np.full(ng, np.inf if kind == "min" else -np.inf)
+                elif c.type == F64:
+                    # Spark's Min / Max order Doubles with NaN greatest: max is NaN when any value is,
+                    # min only when all are.  The numbers are reduced alone; the NaN cases are put back after.
+                    nan = np.isnan(vals)
+                    if kind == "min":
+                        acc = np.full(ng, np.inf)
+                        np.minimum.at(acc, g[~nan], vals[~nan])
+                        acc = np.where(np.bincount(g[~nan], minlength=ng) > 0, acc, np.nan)
                     else:
-                        acc = np.full(ng, np.iinfo(np.int64).max if kind == "min" else np.iinfo(np.int64).min,
-                                      dtype=np.int64)
+                        acc = np.full(ng, -np.inf)
+                        np.maximum.at(acc, g[~nan], vals[~nan])
+                        acc = np.where(np.bincount(g[nan], minlength=ng) > 0, np.nan, acc)
+                    out[name] = Col_(F64, np.where(seen, acc, 0.0), seen)
+                else:
+                    acc = np.full(ng, np.iinfo(np.int64).max if kind == "min" else np.iinfo(np.int64).min,
+                                  dtype=np.int64)
                     (np.minimum if kind == "min" else np.maximum).at(acc, g, vals)
                     out[name] = Col_(c.type, np.where(seen, acc, 0).astype(acc.dtype), seen)
             else:
@@ -310,6 +328,26 @@ def _verify_entity(t: NumpyTable, keys, flags):
     want = fixed + sorted(k for k in t.cols if k not in fixed)
     if list(t.cols) != want:
         raise OracleError(f"Columns: {', '.join(want)} expected, got Columns: {', '.join(t.cols)}")
+
+
+def _order_image(c: Col_) -> np.ndarray:
+    """uint64 whose unsigned order is the column type's sort order.  Doubles: -inf < .. < -0.0 < 0.0 <
+    .. < +inf < NaN, every NaN bit pattern one value (Spark's sort prefix takes doubleToLongBits,
+    which canonicalises NaN, and compares with nanSafeCompareDoubles)."""
+    if c.type == F64:
+        f = c.values.astype(np.float64)
+        b = np.where(np.isnan(f), np.int64(0x7FF8000000000000), f.view(np.int64))
+        b = b ^ ((b >> 63) & np.int64(0x7FFFFFFFFFFFFFFF))
+    else:
+        b = c.values.astype(np.int64)
+    return b.view(np.uint64) ^ np.uint64(1 << 63)
+
+
+def _nan_safe_compare(a: np.ndarray, b: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:
+    """(a < b, a = b) over Doubles with Spark SQL's NaN semantics: NaN = NaN, NaN above all else."""
+    an, bn = np.isnan(a), np.isnan(b)
+    either = an | bn
+    return np.where(either, ~an & bn, a < b), np.where(either, an & bn, a == b)
 
 
 def _key_matrix(cols: Sequence[Col_], n: int, with_nulls: bool) -> np.ndarray:
@@ -419,7 +457,8 @@ def evaluate(e, t: NumpyTable):
                 return I64, np.zeros(n, np.int64), np.zeros(n, bool)
             if lt == F64 or rt == F64:
                 a, b = lv.astype(np.float64), rv.astype(np.float64)
-                res = a + b if e.op == "+" else (a - b if e.op == "-" else a * b)
+                with np.errstate(over="ignore", invalid="ignore"):  # inf and NaN are results, not errors
+                    res = a + b if e.op == "+" else (a - b if e.op == "-" else a * b)
                 return F64, res, m
             with np.errstate(over="ignore"):
                 a, b = lv.astype(np.int64), rv.astype(np.int64)
@@ -435,14 +474,12 @@ def evaluate(e, t: NumpyTable):
         numeric = lt in (I64, F64) and rt in (I64, F64)
         if not numeric and lt != rt:
             return BOOL, np.zeros(n, np.int64), np.zeros(n, bool)
-        if numeric and (lt == F64 or rt == F64):
-            a, b = lv.astype(np.float64), rv.astype(np.float64)
-            m = m & ~np.isnan(a) & ~np.isnan(b)
+        if numeric and (lt == F64 or rt == F64):  # a Long operand is cast to Double
+            less, same = _nan_safe_compare(lv.astype(np.float64), rv.astype(np.float64))
         else:
-            a, b = lv, rv
-        op = {"=": np.equal, "<>": np.not_equal, "<": np.less, "<=": np.less_equal, ">": np.greater,
-              ">=": np.greater_equal}[e.op]
-        return BOOL, op(a, b).astype(np.int64), m
+            less, same = lv < rv, lv == rv
+        res = {"=": same, "<>": ~same, "<": less, "<=": less | same, ">": ~(less | same), ">=": ~less}[e.op]
+        return BOOL, res.astype(np.int64), m
     if name == "Not":
         ty, v, m = evaluate(e.arg, t)
         return BOOL, (v == 0).astype(np.int64), m
@@ -469,7 +506,10 @@ def evaluate(e, t: NumpyTable):
         for v in e.values:
             vt, vv, vm = evaluate(v, t)
             if xt in (I64, F64) and vt in (I64, F64):
-                same = xv.astype(np.float64) == vv.astype(np.float64)
+                if xt == F64 or vt == F64:
+                    _, same = _nan_safe_compare(xv.astype(np.float64), vv.astype(np.float64))
+                else:
+                    same = xv == vv
             elif xt == vt:
                 same = xv == vv
             else:

@@ -107,7 +107,14 @@ def test_union_distinct_order_skip_limit(session):
     oval = [c.valid for c in oo.select("k", "f").to_columns()]
     for a, b in zip(gval, oval):
         np.testing.assert_array_equal(a if a is not None else True, b if b is not None else True)
-    assert [x for x in zip(*gk)][:10] is not None and len(gk[0]) == len(ok[0])
+    assert len(gk[0]) == len(ok[0]) == gu.size
+    for name in ("k", "f", "v"):  # every sort key, row by row: validity, and the values where valid
+        gc, oc = go.column(name), oo.column(name)
+        gm = np.ones(go.size, bool) if gc.valid is None else np.asarray(gc.valid, bool)
+        om = np.ones(oo.size, bool) if oc.valid is None else np.asarray(oc.valid, bool)
+        np.testing.assert_array_equal(gm, om, err_msg=name)
+        np.testing.assert_array_equal(np.asarray(gc.values)[gm], np.asarray(oc.values)[om], err_msg=name)
+    assert (~np.asarray(go.column("k").valid, bool)).sum() > 100  # null primary keys: "f" and "v" decide there
     gs, os_ = go.skip(100).limit(50).column("k"), oo.skip(100).limit(50).column("k")
     gv = np.ones(len(gs.values), bool) if gs.valid is None else np.asarray(gs.valid, bool)
     ov = np.ones(len(os_.values), bool) if os_.valid is None else np.asarray(os_.valid, bool)
