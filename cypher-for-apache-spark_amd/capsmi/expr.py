@@ -10,6 +10,12 @@ Add / Subtract / Multiply, and the id-tag vocabulary BitwiseAnd / BitwiseOr / Sh
 ShiftRightUnsigned (:264-274), CaseExpr (:283-298), and Explode of a list column, ListLit or list
 parameter (:237-241), which ``GpuTable.withColumns`` runs as the UNWIND operator.
 
+List expressions: Size (:124-130; NULL for a NULL list), Index (ContainerIndex, :300-307; 0-based, NULL
+outside the list, a negative index included), InList (In with a list-valued right-hand side,
+array_contains, :138-145; three-valued) over a list column, and Range (:243-245; the reference's
+rangeUdf, inclusive bounds, NULL when an operand is NULL, step 0 an error), which
+``GpuTable.withColumns`` turns into a list column (``capsmi_with_range_column``).
+
 ``compile_program`` lowers a tree to the postfix ``capsmi_expr`` program of include/capsmi.h.
 """
 from __future__ import annotations
@@ -28,6 +34,7 @@ TYPE_NAMES = {I64: "I64", BOOL: "BOOL", F64: "F64", STR: "STR"}
 X_COL, X_LIT, X_NULL, X_EQ, X_NEQ, X_LT, X_LE, X_GT, X_GE, X_NOT, X_AND, X_OR = range(12)
 X_ISNULL, X_ISNOTNULL, X_IN, X_ADD, X_SUB, X_MUL, X_NEG, X_COALESCE = range(12, 20)
 X_BITAND, X_BITOR, X_SHL, X_SHRU, X_CASE, X_PARAM = range(20, 26)
+X_SIZE, X_INDEX, X_IN_LIST = range(26, 29)  # list operands: a Col of a list column
 
 BIN_OPS = {"=": X_EQ, "<>": X_NEQ, "<": X_LT, "<=": X_LE, ">": X_GT, ">=": X_GE, "+": X_ADD, "-": X_SUB, "*": X_MUL,
            "&": X_BITAND, "|": X_BITOR, "<<": X_SHL, ">>>": X_SHRU}
@@ -153,6 +160,65 @@ class Explode(Expr):
     arg: Expr
 
 
+@dataclass(frozen=True, eq=False)
+class Size(Expr):
+    """Size(list) (SparkSQLExprMapper.scala:124-130): the element count of a list column; NULL for a NULL
+    list.  ``size()`` of a string is not implemented on the device path."""
+    arg: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class Index(Expr):
+    """ContainerIndex(list, index) (SparkSQLExprMapper.scala:300-307, Spark's GetArrayItem): element
+    ``index`` (0-based, a Long expression) of a list column; NULL when the list or the index is NULL or
+    the index lies outside the list -- a negative index does not count from the end."""
+    list: Expr
+    index: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class InList(Expr):
+    """In(arg, list) with a list-valued right-hand side (SparkSQLExprMapper.scala:138-145,
+    array_contains): NULL when ``arg`` or the list is NULL, TRUE when some element equals ``arg`` under
+    ``=``, NULL when the element type cannot be compared with ``arg``'s, else FALSE.  With a ``ListLit``
+    or a list ``Param`` on the right it is the plain ``In``."""
+    arg: Expr
+    list: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class Range(Expr):
+    """Range(start, end, step) (SparkSQLExprMapper.scala:243-245; CAPSFunctions.scala:50 rangeUdf, Scala's
+    ``start.to(end, step)``): the Long list start, start + step, ... up to and including ``end``; empty
+    when ``end`` lies on the wrong side; NULL when an operand is NULL; step 0 fails the query.  ``step``
+    None is 1.  Allowed as a whole ``withColumns`` column, as the argument of ``Explode`` and as the list
+    of ``Size`` / ``Index`` / ``InList``."""
+    start: Expr
+    end: Expr
+    step: object = None
+
+
+def _children(e: Expr):
+    for v in e.__dict__.values():
+        for x in (v if isinstance(v, tuple) else (v,)):
+            for y in (x if isinstance(x, tuple) else (x,)):  # Case alternatives are pairs
+                if isinstance(y, Expr):
+                    yield y
+
+
+def contains_range(e: Expr) -> bool:
+    """Whether a Range occurs anywhere in ``e``."""
+    return isinstance(e, Range) or any(contains_range(c) for c in _children(e))
+
+
+def needs_list_lowering(e: Expr) -> bool:
+    """Whether ``GpuTable`` has to rewrite ``e`` before compiling it: a Range, a Size or an InList occurs, or an
+    Index of a literal."""
+    if isinstance(e, (Range, Size, InList)) or (isinstance(e, Index) and isinstance(e.list, (ListLit, Lit))):
+        return True
+    return any(needs_list_lowering(c) for c in _children(e))
+
+
 def contains_explode(e: Expr) -> bool:
     """Whether an Explode occurs anywhere in ``e``."""
     if isinstance(e, Explode):
@@ -271,6 +337,17 @@ def compile_program(e: Expr, column_index: Callable[[str], int], encode_str: Cal
             for a in x.args:
                 go(a)
             out.append((X_COALESCE, len(x.args), 0, 0))
+        elif isinstance(x, Size):
+            go(x.arg)
+            out.append((X_SIZE, 0, 0, 0))
+        elif isinstance(x, Index):
+            go(x.list)
+            go(x.index)
+            out.append((X_INDEX, 0, 0, 0))
+        elif isinstance(x, InList):
+            go(x.arg)
+            go(x.list)
+            out.append((X_IN_LIST, 0, 0, 0))
         elif isinstance(x, Case):
             if not x.alternatives:
                 go(x.default if x.default is not None else NULL)

@@ -28,7 +28,7 @@ from typing import Dict, FrozenSet, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .expr import (BOOL, F64, I64, LIST, STR, Ands, BinOp, Col, Explode, Expr, In, IsNotNull, IsNull, ListLit, Lit, Not, Ors,
-                   ands, eq)
+                   Index, InList, Range, Size, ands, eq)
 from .table import ColumnData, decode_value
 
 
@@ -469,7 +469,25 @@ def to_expr(spec, header: Sequence[str]) -> Expr:
         return IsNotNull(to_expr(spec[1], header))
     if op == "in":
         return In(to_expr(spec[1], header), tuple(Lit(v) for v in spec[2]))
+    # list expressions: the list operand is a list column, ["listlit", [...]] or ["range", ...]
+    if op == "size":
+        return Size(_list_operand(spec[1], header))
+    if op == "index":
+        return Index(_list_operand(spec[1], header), to_expr(spec[2], header))
+    if op == "in_list":
+        return InList(to_expr(spec[1], header), _list_operand(spec[2], header))
+    if op == "range":
+        if len(spec) not in (3, 4):
+            raise PlanningError(f"range takes two or three operands: {spec!r}")
+        opd = [to_expr(s, header) if isinstance(s, list) else Lit(s) for s in spec[1:]]
+        return Range(opd[0], opd[1], opd[2] if len(opd) > 2 else None)
     raise PlanningError(f"unknown expression {spec!r}")
+
+
+def _list_operand(spec, header: Sequence[str]) -> Expr:
+    if spec[0] == "listlit":
+        return ListLit(tuple(spec[1]))
+    return to_expr(spec, header)
 
 
 AGGS = {"count*": "count_star", "count": "count", "count_distinct": "count", "min": "min", "max": "max",
@@ -501,7 +519,7 @@ class Planner:
         """Execute ``{"clauses": [{"match": str, "where": expr?}], "return": {...}}``; returns
         (table, output spec) ready for :func:`result_rows`.  Further clause kinds:
         ``{"unwind": spec, "as": name}`` with spec ``["listlit", [...]]``, ``["param", name]`` (a list of the
-        query's ``"params"`` map), ``["var", column]`` or ``["prop", var, key]``, and
+        query's ``"params"`` map), ``["var", column]``, ``["prop", var, key]`` or ``["range", from, to, step?]``, and
         ``{"with": {"items": ...}, "where": expr?}`` (the items of a RETURN)."""
         cur: Optional[_Op] = None
         varlen: Dict[str, int] = {}
@@ -544,6 +562,8 @@ class Planner:
             if not isinstance(params.get(spec[1]), (list, tuple)):
                 raise PlanningError(f"UNWIND needs a list parameter ${spec[1]}")
             lst = ListLit(tuple(params[spec[1]]))
+        elif kind == "range":  # UNWIND range(from, to[, step]): literal or expression operands
+            lst = to_expr(spec, cur.header)
         elif kind in ("var", "prop"):
             col = spec[1] if kind == "var" else f"{spec[1]}.{spec[2]}"
             if col not in cur.header or col in cur.null_cols:

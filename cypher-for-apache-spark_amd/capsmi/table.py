@@ -12,6 +12,7 @@ from __future__ import annotations
 import bisect
 import contextlib
 import ctypes
+import itertools
 import threading
 from dataclasses import dataclass
 from typing import Iterable, List, Optional, Sequence, Tuple
@@ -19,12 +20,14 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .expr import (BOOL, F64, I64, LIST, STR, CapsmiExpr, Col, Explode, Expr, ListLit, Lit, Param, compile_program,
+from .expr import (BOOL, F64, I64, LIST, STR, BinOp, CapsmiExpr, Case, Col, Explode, Expr, In, Index, InList, ListLit, Lit, Param, Range,
+                   Size, contains_range, needs_list_lowering, compile_program,
                    contains_explode, to_ctypes)
 
 _TLS = threading.local()
 
 _EXPR_PTR = ctypes.POINTER(CapsmiExpr)
+_TMP_IDS = itertools.count()  # names of the temporary list columns of Range operands
 _LIT_PROGS = {}  # (python type, value, declared type) -> one-node program of a Boolean / Long / null literal
 
 JOIN_TYPES = {"inner": 0, "left_outer": 1, "right_outer": 2, "full_outer": 3, "cross": 4}
@@ -585,6 +588,20 @@ class GpuTable:
         return len(prog), arr
 
     def filter(self, expr: Expr) -> "GpuTable":
+        if type(expr) is not Col and needs_list_lowering(expr):
+            if isinstance(expr, Range):  # a list is no predicate
+                raise _lib.NotImplementedException(
+                    "Range is a whole withColumns column or the argument of Explode / Size / Index / InList")
+            e, temps = self._lower_lists(expr)
+            if temps:  # Range operands: temporary list columns, dropped again
+                t = self
+                for tmp, r in temps:
+                    t = t.withRangeColumn(r.start, r.end, r.step, tmp)
+                return t._filter(e).drop(*[tmp for tmp, _ in temps])
+            expr = e
+        return self._filter(expr)
+
+    def _filter(self, expr: Expr) -> "GpuTable":
         n, prog = self._program(expr)
         out = ctypes.c_void_p()
         _lib.call("capsmi_filter", self._h, n, prog, ctypes.byref(out))
@@ -700,7 +717,116 @@ class GpuTable:
             return self.explodeValues(params[a.index], name)
         raise _lib.NotImplementedException(f"Explode of {a!r}: a list column, ListLit or list Param")
 
+    def withRangeColumn(self, start, end, step, name: str) -> "GpuTable":
+        """This table plus the Long list column `name` = range(start, end, step) per row (include/capsmi.h
+        capsmi_with_range_column): Long expressions or Python ints; `step` None is 1."""
+        as_expr = lambda x: x if isinstance(x, Expr) else Lit(x)  # noqa: E731
+        progs = [self._program(as_expr(x)) for x in (start, end)]
+        progs.append((0, None) if step is None else self._program(as_expr(step)))
+        args = []
+        for n, prog in progs:
+            args += [n, None if prog is None else ctypes.cast(prog, _EXPR_PTR)]
+        out = ctypes.c_void_p()
+        _lib.call("capsmi_with_range_column", self._h, *args, name.encode(), ctypes.byref(out))
+        return self._wrap(out)
+
+    def _lower_lists(self, e: Expr):
+        """The list expressions the library does not take as they are, rewritten: InList over a ListLit or a
+        list Param is the plain In; Size(ListLit) is a literal; a Range under Explode / Size / Index / InList
+        becomes a reference to a temporary list column.  Returns (expression, [(temporary name, Range)])."""
+        temps = []
+
+        def as_list(a: Expr) -> Expr:
+            if isinstance(a, Range):
+                check_range(a)
+                tmp = f"__range_{next(_TMP_IDS)}"
+                temps.append((tmp, a))
+                return Col(tmp)
+            return go(a)
+
+        def check_range(r: Range) -> None:
+            for x in (r.start, r.end, r.step):
+                if isinstance(x, Expr) and (contains_range(x) or contains_explode(x)):
+                    raise _lib.NotImplementedException("Range nested in a Range operand")
+
+        def go(x):
+            if isinstance(x, Range):
+                raise _lib.NotImplementedException(
+                    "Range is a whole withColumns column or the argument of Explode / Size / Index / InList")
+            if isinstance(x, Index) and not needs_list_lowering(x) and not isinstance(x.list, (ListLit, Lit)):
+                return x
+            if isinstance(x, InList):
+                if isinstance(x.list, ListLit):
+                    return In(go(x.arg), tuple(Lit(v) for v in x.list.values))
+                if isinstance(x.list, Param):
+                    return In(go(x.arg), (x.list,))
+                if isinstance(x.list, Lit) and x.list.value is None:
+                    return Lit(None, BOOL)
+                return InList(go(x.arg), as_list(x.list))
+            if isinstance(x, Size):
+                if isinstance(x.arg, ListLit):
+                    return Lit(len(x.arg.values))
+                if isinstance(x.arg, Lit) and x.arg.value is None:
+                    return Lit(None, I64)
+                if (isinstance(x.arg, Lit) and isinstance(x.arg.value, str)) or (
+                        isinstance(x.arg, Col) and self.columnType.get(x.arg.name) == STR):
+                    raise _lib.NotImplementedException(
+                        "size() of a string is not implemented: string lengths live in the caller's dictionary")
+                return Size(as_list(x.arg))
+            if isinstance(x, Index):
+                if isinstance(x.list, ListLit):  # a literal list: the element whose position the index equals
+                    i = go(x.index)
+                    return Case(tuple((BinOp("=", i, Lit(k)), Lit(v)) for k, v in enumerate(x.list.values)))
+                if isinstance(x.list, Lit) and x.list.value is None:
+                    return Lit(None)
+                return Index(as_list(x.list), go(x.index))
+            if isinstance(x, Explode):
+                return Explode(as_list(x.arg))
+            if not isinstance(x, Expr) or isinstance(x, (Col, Lit, Param, ListLit)):
+                return x
+            kw = {}
+            for k, v in x.__dict__.items():
+                if isinstance(v, tuple):
+                    v = tuple(tuple(go(y) for y in w) if isinstance(w, tuple) else go(w) for w in v)
+                kw[k] = go(v) if isinstance(v, Expr) else v
+            return type(x)(**kw)
+
+        if isinstance(e, Range):  # the whole column
+            check_range(e)
+            return e, temps
+        return go(e), temps
+
+    def _with_list_columns(self, columns) -> "GpuTable":
+        """withColumns with Range / Size / Index / InList among the expressions (see _lower_lists).  A column
+        that is a Range splits the call, as an Explode does: the columns before it are evaluated first, the
+        ones after it see it."""
+        t, drop, batch = self, [], []
+        for e, name in columns:
+            e, temps = t._lower_lists(e)
+            if temps or isinstance(e, (Range, Explode)):
+                if batch:
+                    t, batch = t._with_columns(batch), []
+                for tmp, r in temps:
+                    t = t.withRangeColumn(r.start, r.end, r.step, tmp)
+                    drop.append(tmp)
+            if isinstance(e, Range):
+                t = t.withRangeColumn(e.start, e.end, e.step, name)
+            elif temps or isinstance(e, Explode):
+                t = t._with_columns(((e, name),))
+            else:
+                batch.append((e, name))
+        if batch:
+            t = t._with_columns(batch)
+        return t.drop(*drop) if drop else t
+
     def withColumns(self, *columns: Tuple[Expr, str]) -> "GpuTable":
+        if any(type(e) is not Col and type(e) is not Lit and needs_list_lowering(e) for e, _ in columns):
+            if sum(1 for e, _ in columns if contains_explode(e)) > 1:
+                raise _lib.NotImplementedException("more than one Explode in one withColumns")
+            return self._with_list_columns(columns)
+        return self._with_columns(columns)
+
+    def _with_columns(self, columns) -> "GpuTable":
         gen = [i for i, (e, _) in enumerate(columns) if contains_explode(e)]
         if gen:  # UNWIND: Explode(list) AS item (RelationalPlanner.scala:94-96); one generator per call
             if len(gen) > 1:

@@ -1121,6 +1121,49 @@ capsmi_status eager_with_columns(capsmi_table* t, int32_t ncols, const capsmi_ex
     API_END
 }
 
+// range(from, to, step) per row as a list column (capsmi_with_range_column): the operands are evaluated into
+// temporary columns by the interpreter, k_listexpr.hip builds the store
+capsmi_status eager_with_range_column(capsmi_table* t, const std::vector<capsmi_expr>& from,
+                                      const std::vector<capsmi_expr>& to, const std::vector<capsmi_expr>& step,
+                                      const char* name, capsmi_table** out) {
+    API_BEGIN
+    need(t, "table");
+    need(out, "out");
+    need(name, "column name");
+    capsmi_session* s = t->sess;
+    use_device(s);
+    const int64_t n = t->nrows;
+    Column opd[3];
+    const std::vector<capsmi_expr>* progs[3] = {&from, &to, &step};
+    for (int i = 0; i < 3; ++i) {
+        const std::vector<capsmi_expr>& p = *progs[i];
+        if (p.empty()) continue;  // the step's literal 1
+        REQUIRE(infer_type(t, (int32_t)p.size(), p.data()) == CAPSMI_I64, CAPSMI_ERR_ILLEGAL_ARGUMENT,
+                "range: operands must be Long");
+        if (p.size() == 1 && p[0].op == CAPSMI_X_COL && p[0].arg >= 0 && p[0].arg < (int)t->cols.size()) {
+            opd[i] = t->cols[p[0].arg];
+            continue;
+        }
+        opd[i].data = dev_alloc(sizeof(int64_t) * (n > 0 ? n : 1), s);
+        opd[i].valid = dev_alloc(n > 0 ? n : 1, s);
+        eval_expr(s, t, (int32_t)p.size(), p.data(), P<int64_t>(opd[i].data), P<uint8_t>(opd[i].valid), nullptr);
+    }
+    Column c;
+    c.name = name;
+    c.type = CAPSMI_LIST_I64;
+    c.list = range_lists(s, opd[0].d(), opd[0].v(), opd[1].d(), opd[1].v(), step.empty() ? nullptr : opd[2].d(),
+                         step.empty() ? nullptr : opd[2].v(), n, c.valid);
+    c.data = dev_alloc(sizeof(int64_t) * (n > 0 ? n : 1), s);
+    iota_i64(P<int64_t>(c.data), 0, n, s->stream);  // row r's list is list r of the new store
+    auto* o = new_table(s, n);
+    o->cols = t->cols;
+    const int j = o->find(c.name);
+    if (j >= 0) o->cols[j] = std::move(c);  // replaced in place, as capsmi_with_columns does
+    else o->cols.push_back(std::move(c));
+    *out = o;
+    API_END
+}
+
 capsmi_status eager_join(capsmi_table* l, capsmi_table* r, int32_t join_type, int32_t npairs,
                           const char* const* lcols, const char* const* rcols, capsmi_table** out) {
     API_BEGIN

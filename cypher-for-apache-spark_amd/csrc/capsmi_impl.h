@@ -366,6 +366,16 @@ int64_t explode_lists(capsmi_session* s, const int64_t* word, const uint8_t* val
 // item_valid both null when no value is null); item / src hold n * count entries
 void explode_values(capsmi_session* s, int64_t n, int64_t count, const int64_t* vals, const uint8_t* vvalid, int64_t* item,
                     uint8_t* item_valid, int64_t* src);
+// list expressions (k_listexpr.hip), over the same tiles.  x IN list: out / out_valid[r] = the three-valued
+// CAPSMI_X_IN_LIST of probe word (probe, pvalid)[r] of type ptype and the list (word, lvalid)[r] of store L
+// (synchronises)
+void list_contains(capsmi_session* s, const int64_t* probe, const uint8_t* pvalid, int32_t ptype, const int64_t* word,
+                   const uint8_t* lvalid, const ListStore& L, int64_t n, int64_t* out, uint8_t* out_valid);
+// range(from, to, step) per row (step null: 1) as a store whose list r is row r's; `valid`: the rows none of
+// whose operands is null.  Throws ILLEGAL_ARGUMENT for a step 0, UNSUPPORTED for more elements than the device
+// holds (synchronises)
+std::shared_ptr<ListStore> range_lists(capsmi_session* s, const int64_t* from, const uint8_t* fv, const int64_t* to,
+                                       const uint8_t* tv, const int64_t* step, const uint8_t* sv, int64_t n, Buf& valid);
 // multi-GPU (k_dist.hip): the session's collective, stream-ordered (capsmi_collective_fn)
 void collective(capsmi_session* s, int op, const void* send, void* recv, int64_t count, int dtype);
 // calls of the host collective move at most coll_chunk() elements (CAPSMI_COLL_CHUNK); collective() and
@@ -614,6 +624,8 @@ int32_t infer_type(const capsmi_table* t, int32_t nn, const capsmi_expr* prog);
 std::vector<capsmi_expr> bind_params(const capsmi_session* s, int32_t nn, const capsmi_expr* prog);
 bool has_params(int32_t nn, const capsmi_expr* prog);
 void validate_program(const capsmi_table* t, int32_t nn, const capsmi_expr* prog);
+// operands the node pops: the one arity table of the opcodes (-1: an opcode the interpreter does not know)
+int expr_pops(const capsmi_expr& x);
 
 // lazy plans (plan.hip): run the plan (a fused kernel when the recogniser matches) and keep the result
 void materialize(capsmi_table* t);
@@ -649,6 +661,10 @@ capsmi_status eager_explode(capsmi_table* t, const char* list_col, const char* i
                             const std::vector<std::string>* keep, capsmi_table** out);
 capsmi_status eager_explode_values(capsmi_table* t, int32_t elem_type, int32_t count, const capsmi_value* values,
                                    const char* item_name, const std::vector<std::string>* keep, capsmi_table** out);
+// programs over t's columns; step empty: the literal 1
+capsmi_status eager_with_range_column(capsmi_table* t, const std::vector<capsmi_expr>& from,
+                                      const std::vector<capsmi_expr>& to, const std::vector<capsmi_expr>& step,
+                                      const char* name, capsmi_table** out);
 
 // CSV ingest (ingest.hip)
 capsmi_table* read_csv(capsmi_session* s, const std::vector<std::string>& paths, char delim, char comment,

@@ -16,26 +16,13 @@
 //
 // Constant form (explode(array(lit...)), SparkSQLExprMapper.scala:86-89, 111-112): output row j repeats input
 // row j / count with item values[j % count].
-#include "capsmi_impl.h"
+#include "tile_owner.h"
 
 namespace capsmi {
 
 namespace {
 
-constexpr int kExB = 256;                   // threads per block
-constexpr int kExI = kExplodeTile / kExB;   // output slots per thread
-static_assert(kExplodeTile % kExB == 0 && kExplodeTile <= 65536, "tile slots are uint16 marks, kExI per thread");
-
-inline unsigned grid_for(int64_t n) {
-    const int64_t g = (n + 255) / 256;
-    return (unsigned)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
-}
-
-// blocks of a tile kernel: every tile its block up to a few resident blocks per CU, then block-stride
-inline unsigned tile_grid(const capsmi_session* s, int64_t ntiles) {
-    const int64_t cap = (int64_t)s->num_cus * 8;
-    return (unsigned)(ntiles < 1 ? 1 : (ntiles > cap ? cap : ntiles));
-}
+using namespace tiles;
 
 // len[r] = elements of row r's list (0 for a null row), flag[r] = len > 0
 __global__ void k_explode_len(const int64_t* __restrict__ word, const uint8_t* __restrict__ valid, int64_t n,
@@ -64,24 +51,6 @@ __global__ void k_explode_heads(const int64_t* __restrict__ cs, int64_t k, int64
     }
 }
 
-// max over the threads before this one of one value per thread (kExB threads)
-__device__ __forceinline__ uint32_t max_before(uint32_t v, uint32_t* wtot) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(x, o, 64);
-        if (lane >= o) x = max(x, y);
-    }
-    if (lane == 63) wtot[wave] = x;
-    __syncthreads();
-    const uint32_t xp = __shfl_up(x, 1, 64);  // every lane active
-    uint32_t pre = lane > 0 ? xp : 0u;
-    for (int q = 0; q < wave; ++q) pre = max(pre, wtot[q]);
-    __syncthreads();  // wtot is reused by the next tile
-    return pre;
-}
-
 // cs: first output row of compacted row c (k of them); nz: its input row (null: c itself); word / off / vals:
 // the input rows' list indices and the store
 __global__ void __launch_bounds__(kExB) k_explode(const int64_t* __restrict__ cs, const int64_t* __restrict__ nz, int64_t k,
@@ -89,45 +58,21 @@ __global__ void __launch_bounds__(kExB) k_explode(const int64_t* __restrict__ cs
                                                  const int64_t* __restrict__ word, const int64_t* __restrict__ off,
                                                  const int64_t* __restrict__ vals, int64_t* __restrict__ item,
                                                  int64_t* __restrict__ src) {
-    __shared__ int64_t sbase[kExplodeTile];  // store position of the tile's c-th row's element at tile slot 0
-    __shared__ int64_t srow[kExplodeTile];   // its input row
-    __shared__ uint16_t own[kExplodeTile];   // slot -> its row (tile-local c)
-    __shared__ uint32_t wtot[kExB / 64];
+    __shared__ TileLds L;
     const int t = threadIdx.x;
     const int64_t ntiles = (m + kExplodeTile - 1) / kExplodeTile;
     for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {  // block-uniform
-        const int64_t j0 = tile * kExplodeTile, c0 = tk[tile];
+        const int64_t j0 = tile * kExplodeTile;
         const int nt = (int)min((int64_t)kExplodeTile, m - j0);
-        for (int i = t; i < kExplodeTile; i += kExB) own[i] = 0;
-        __syncthreads();
-        for (int i = t; i < kExplodeTile && c0 + i < k; i += kExB) {
-            const int64_t w = cs[c0 + i];
-            if (i > 0 && w >= j0 + nt) break;  // past the tile (starts ascend)
-            const int64_t r = nz ? nz[c0 + i] : c0 + i;
-            sbase[i] = off[word[r]] - (w - j0);  // slot s of this row holds element sbase + s
-            srow[i] = r;
-            if (i > 0) own[w - j0] = (uint16_t)i;  // w > j0: row c0 is the last one starting at or before j0
-        }
-        __syncthreads();
-        // fill forward: own[s] = max(own[0..s]) (the heads ascend with c); thread t holds slots kExI*t ..
-        uint32_t v[kExI];
-        uint32_t mx = 0;
-#pragma unroll
-        for (int j = 0; j < kExI; ++j) {
-            mx = max(mx, (uint32_t)own[t * kExI + j]);
-            v[j] = mx;
-        }
-        const uint32_t pre = max_before(mx, wtot);
-#pragma unroll
-        for (int j = 0; j < kExI; ++j) own[t * kExI + j] = (uint16_t)max(v[j], pre);
-        __syncthreads();
+        // slot s of a row holds store element sbase + s
+        tile_owners(L, cs, nz, k, tk[tile], j0, nt, [&](int64_t r) { return off[word[r]]; });
 #pragma unroll
         for (int j = 0; j < kExI; ++j) {
             const int i = t + j * kExB;
             if (i < nt) {
-                const int c = own[i];
-                item[j0 + i] = vals[sbase[c] + i];
-                src[j0 + i] = srow[c];
+                const int c = L.own[i];
+                item[j0 + i] = vals[L.sbase[c] + i];
+                src[j0 + i] = L.srow[c];
             }
         }
         __syncthreads();  // the next tile rewrites the LDS arrays
@@ -147,47 +92,67 @@ __global__ void k_explode_values(int64_t total, int64_t count, const int64_t* __
 
 }  // namespace
 
+void list_lengths(capsmi_session* s, const int64_t* word, const uint8_t* valid, int64_t n, const int64_t* off, int64_t* len,
+                  uint8_t* flag) {
+    hipLaunchKernelGGL(k_explode_len, dim3(grid_for(n)), dim3(256), 0, s->stream, word, valid, n, off, len, flag);
+    HIP_CHECK(hipGetLastError());
+}
+
+TilePlan tile_plan(capsmi_session* s, const int64_t* len, const uint8_t* flag, int64_t n, const char* timer,
+                   int64_t max_slots) {
+    TilePlan tp;
+    tp.starts = dev_alloc(sizeof(int64_t) * (n + 1), s);
+    {
+        KernelTimer kt(s, timer);
+        exclusive_scan_i64(len, P<int64_t>(tp.starts), n, s);
+    }
+    tp.m = read_scalar(s, P<int64_t>(tp.starts) + n);
+    if (tp.m == 0 || (max_slots >= 0 && tp.m > max_slots)) return tp;
+    // the rows that contribute, in order; when every row does, the starts are already the compacted ones
+    tp.cs = P<int64_t>(tp.starts);
+    {
+        KernelTimer kt(s, timer);
+        tp.k = flags_to_indices(s, flag, n, tp.nzb);
+        if (tp.k < n) {
+            tp.csb = dev_alloc(sizeof(int64_t) * tp.k, s);
+            gather_col(P<int64_t>(tp.starts), nullptr, P<int64_t>(tp.nzb), tp.k, P<int64_t>(tp.csb), nullptr, s->stream);
+            tp.cs = P<int64_t>(tp.csb);
+            tp.nz = P<int64_t>(tp.nzb);
+        }
+    }
+    tp.ntiles = (tp.m + kExplodeTile - 1) / kExplodeTile;
+    tp.tk = dev_alloc(sizeof(int64_t) * tp.ntiles, s);
+    return tp;
+}
+
+// the tile heads of a plan (part of the consumer's timed launch)
+void tile_heads(capsmi_session* s, const TilePlan& tp) {
+    hipLaunchKernelGGL(k_explode_heads, dim3(grid_for(tp.ntiles)), dim3(256), 0, s->stream, tp.cs, tp.k, tp.ntiles,
+                       P<int64_t>(tp.tk));
+    HIP_CHECK(hipGetLastError());
+}
+
 int64_t explode_lists(capsmi_session* s, const int64_t* word, const uint8_t* valid, int64_t n, const ListStore& L,
                       Buf& item, Buf& src) {
     hipStream_t st = s->stream;
     item = src = nullptr;
     if (n == 0) return 0;
-    Buf len = dev_alloc(sizeof(int64_t) * n, s), flag = dev_alloc(n, s), starts = dev_alloc(sizeof(int64_t) * (n + 1), s);
+    Buf len = dev_alloc(sizeof(int64_t) * n, s), flag = dev_alloc(n, s);
     {
         KernelTimer kt(s, "explode_starts");
-        hipLaunchKernelGGL(k_explode_len, dim3(grid_for(n)), dim3(256), 0, st, word, valid, n, P<int64_t>(L.offsets),
-                           P<int64_t>(len), P<uint8_t>(flag));
-        HIP_CHECK(hipGetLastError());
-        exclusive_scan_i64(P<int64_t>(len), P<int64_t>(starts), n, s);
+        list_lengths(s, word, valid, n, P<int64_t>(L.offsets), P<int64_t>(len), P<uint8_t>(flag));
     }
-    const int64_t m = read_scalar(s, P<int64_t>(starts) + n);
+    const TilePlan tp = tile_plan(s, P<int64_t>(len), P<uint8_t>(flag), n, "explode_starts");
+    const int64_t m = tp.m;
     if (m == 0) return 0;
-    // the rows that contribute, in order; when every row does, the starts are already the compacted ones
-    Buf nz, csb;
-    int64_t k;
-    const int64_t* cs = P<int64_t>(starts);
-    const int64_t* nzp = nullptr;
-    {
-        KernelTimer kt(s, "explode_starts");
-        k = flags_to_indices(s, P<uint8_t>(flag), n, nz);
-        if (k < n) {
-            csb = dev_alloc(sizeof(int64_t) * k, s);
-            gather_col(P<int64_t>(starts), nullptr, P<int64_t>(nz), k, P<int64_t>(csb), nullptr, st);
-            cs = P<int64_t>(csb);
-            nzp = P<int64_t>(nz);
-        }
-    }
-    const int64_t ntiles = (m + kExplodeTile - 1) / kExplodeTile;
-    Buf tk = dev_alloc(sizeof(int64_t) * ntiles, s);
     item = dev_alloc(sizeof(int64_t) * m, s);
     src = dev_alloc(sizeof(int64_t) * m, s);
     {
         // algorithmic bytes: n starts and n row words read, m values read, m items and m source rows written
         KernelTimer kt(s, "explode", 8.0 * (2.0 * (double)n + 3.0 * (double)m));
-        hipLaunchKernelGGL(k_explode_heads, dim3(grid_for(ntiles)), dim3(256), 0, st, cs, k, ntiles, P<int64_t>(tk));
-        HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(k_explode, dim3(tile_grid(s, ntiles)), dim3(kExB), 0, st, cs, nzp, k, P<int64_t>(tk), m, word,
-                           P<int64_t>(L.offsets), P<int64_t>(L.values), P<int64_t>(item), P<int64_t>(src));
+        tile_heads(s, tp);
+        hipLaunchKernelGGL(k_explode, dim3(tile_grid(s, tp.ntiles)), dim3(kExB), 0, st, tp.cs, tp.nz, tp.k, P<int64_t>(tp.tk), m,
+                           word, P<int64_t>(L.offsets), P<int64_t>(L.values), P<int64_t>(item), P<int64_t>(src));
         HIP_CHECK(hipGetLastError());
     }
     return m;

@@ -14,7 +14,11 @@
 //   - Filter keeps a row iff the value is TRUE (SparkTable.scala:65-67; pinned by
 //     PredicateBehaviour.scala:131-149);
 //   - bitwise and shift operators on Long (the id-tag expressions of Tags.scala:101-123), NULL in ->
-//     NULL out; CASE takes the first alternative whose predicate is TRUE (a NULL predicate is not).
+//     NULL out; CASE takes the first alternative whose predicate is TRUE (a NULL predicate is not);
+//   - list columns (SparkSQLExprMapper.scala:124-130 Size, :300-307 ContainerIndex, :138-145 In): a column
+//     reference to a list column pushes the row's list; size() and list[i] read the store's offsets and one value
+//     here; x IN list is lowered on the host (lower_in_list below) to a column that k_listexpr.hip computes over
+//     all the rows' elements before this interpreter runs.  No other opcode takes a list.
 #include "capsmi_impl.h"
 
 namespace capsmi {
@@ -29,11 +33,14 @@ struct ColPtrs {
     const int64_t* data[kMaxCols];
     const uint8_t* valid[kMaxCols];
     int8_t type[kMaxCols];
+    const int64_t* loff[kMaxCols];  // list columns: the store's offsets and values
+    const int64_t* lval[kMaxCols];
 };
 
 struct Val {
     int64_t b;
     int8_t t;  // CAPSMI_* or kNull
+    int8_t c;  // a list value (t >= CAPSMI_LIST): the column whose store b indexes
 };
 
 __device__ __forceinline__ bool numeric(int8_t t) { return t == CAPSMI_I64 || t == CAPSMI_F64; }
@@ -67,7 +74,7 @@ __device__ Val eval_row(const capsmi_expr* __restrict__ prog, int nn, const ColP
             case CAPSMI_X_COL: {
                 const int c = x.arg;
                 const bool ok = cp.valid[c] == nullptr || cp.valid[c][r];
-                st[sp++] = ok ? Val{cp.data[c][r], cp.type[c]} : mk_null();
+                st[sp++] = ok ? Val{cp.data[c][r], cp.type[c], (int8_t)c} : mk_null();
                 break;
             }
             case CAPSMI_X_LIT: st[sp++] = Val{x.ival, (int8_t)x.type}; break;
@@ -176,6 +183,22 @@ __device__ Val eval_row(const capsmi_expr* __restrict__ prog, int nn, const ColP
                 st[sp++] = res;
                 break;
             }
+            case CAPSMI_X_SIZE: {
+                const Val a = st[--sp];
+                if (a.t < CAPSMI_LIST) { st[sp++] = mk_null(); break; }
+                const int64_t* off = cp.loff[a.c];
+                st[sp++] = Val{off[a.b + 1] - off[a.b], (int8_t)CAPSMI_I64};
+                break;
+            }
+            case CAPSMI_X_INDEX: {
+                const Val i = st[--sp], a = st[--sp];
+                if (a.t < CAPSMI_LIST || i.t != CAPSMI_I64) { st[sp++] = mk_null(); break; }
+                const int64_t* off = cp.loff[a.c];
+                const int64_t lo = off[a.b], size = off[a.b + 1] - lo;
+                if (i.b < 0 || i.b >= size) { st[sp++] = mk_null(); break; }  // GetArrayItem: no counting from the end
+                st[sp++] = Val{cp.lval[a.c][lo + i.b], (int8_t)(a.t - CAPSMI_LIST)};
+                break;
+            }
             default: st[sp++] = mk_null(); break;
         }
     }
@@ -208,6 +231,13 @@ int32_t infer_type(const capsmi_table* t, int32_t nn, const capsmi_expr* prog) {
             case CAPSMI_X_IN: for (int k = 0; k < x.arg + 1; ++k) pop(); st.push_back(CAPSMI_BOOL); break;
             case CAPSMI_X_NOT: case CAPSMI_X_ISNULL: case CAPSMI_X_ISNOTNULL: pop(); st.push_back(CAPSMI_BOOL); break;
             case CAPSMI_X_NEG: break;
+            case CAPSMI_X_SIZE: pop(); st.push_back(CAPSMI_I64); break;
+            case CAPSMI_X_INDEX: {
+                pop();
+                const int l = pop();
+                st.push_back(l >= CAPSMI_LIST ? l - CAPSMI_LIST : -1);
+                break;
+            }
             case CAPSMI_X_COALESCE: {
                 int ty = -1;
                 for (int k = 0; k < x.arg; ++k) { int v = pop(); if (v >= 0) ty = v; }
@@ -236,6 +266,22 @@ int32_t infer_type(const capsmi_table* t, int32_t nn, const capsmi_expr* prog) {
     }
     const int ty = st.empty() ? -1 : st.back();
     return ty < 0 ? CAPSMI_I64 : ty;
+}
+
+// operands an opcode pops (-1: unknown opcode, CAPSMI_X_PARAM included: it is bound before anything counts)
+int expr_pops(const capsmi_expr& x) {
+    switch (x.op) {
+        case CAPSMI_X_COL: case CAPSMI_X_LIT: case CAPSMI_X_NULL: return 0;
+        case CAPSMI_X_NOT: case CAPSMI_X_ISNULL: case CAPSMI_X_ISNOTNULL: case CAPSMI_X_NEG: case CAPSMI_X_SIZE: return 1;
+        case CAPSMI_X_AND: case CAPSMI_X_OR: case CAPSMI_X_COALESCE: return x.arg;
+        case CAPSMI_X_IN: return x.arg + 1;
+        case CAPSMI_X_CASE: return 2 * x.arg + 1;
+        case CAPSMI_X_EQ: case CAPSMI_X_NEQ: case CAPSMI_X_LT: case CAPSMI_X_LE: case CAPSMI_X_GT: case CAPSMI_X_GE:
+        case CAPSMI_X_ADD: case CAPSMI_X_SUB: case CAPSMI_X_MUL:
+        case CAPSMI_X_BITAND: case CAPSMI_X_BITOR: case CAPSMI_X_SHL: case CAPSMI_X_SHRU:
+        case CAPSMI_X_INDEX: case CAPSMI_X_IN_LIST: return 2;
+        default: return -1;
+    }
 }
 
 bool has_params(int32_t nn, const capsmi_expr* prog) {
@@ -277,15 +323,8 @@ std::vector<capsmi_expr> bind_params(const capsmi_session* s, int32_t nn, const 
             }
             continue;
         }
-        int pops = 0;
-        switch (x.op) {
-            case CAPSMI_X_COL: case CAPSMI_X_LIT: case CAPSMI_X_NULL: pops = 0; break;
-            case CAPSMI_X_NOT: case CAPSMI_X_ISNULL: case CAPSMI_X_ISNOTNULL: case CAPSMI_X_NEG: pops = 1; break;
-            case CAPSMI_X_AND: case CAPSMI_X_OR: case CAPSMI_X_COALESCE: pops = x.arg; break;
-            case CAPSMI_X_IN: pops = x.arg + 1; break;
-            case CAPSMI_X_CASE: pops = 2 * x.arg + 1; break;
-            default: pops = 2; break;
-        }
+        const int pops = expr_pops(x);
+        if (pops < 0 && x.op > CAPSMI_X_IN_LIST) throw Error(CAPSMI_ERR_NOT_IMPLEMENTED, "unknown expression op " + std::to_string(x.op));
         REQUIRE(pops >= 0 && (int)width.size() >= pops, CAPSMI_ERR_ILLEGAL_ARGUMENT,
                 "malformed expression program (stack underflow)");
         capsmi_expr y = x;
@@ -306,53 +345,172 @@ std::vector<capsmi_expr> bind_params(const capsmi_session* s, int32_t nn, const 
     return out;
 }
 
+// Static checks of a program over t's schema: indices, arity, depth, and the operand types of the list opcodes.
+// The type of every stack entry is tracked as infer_type does (-1: unknown, an untyped NULL); a list value may
+// only be the list operand of SIZE / INDEX / IN_LIST, or the whole program (one COL: an alias).
 void validate_program(const capsmi_table* t, int32_t nn, const capsmi_expr* prog) {
-    int depth = 0, maxd = 0;
+    int maxd = 0;
+    std::vector<int> ty;  // types of the stack entries
     for (int i = 0; i < nn; ++i) {
         const capsmi_expr& x = prog[i];
-        int pops = 0;
-        switch (x.op) {
+        switch (x.op) {  // the operand counts of the n-ary opcodes first: they decide what is popped
             case CAPSMI_X_COL:
                 REQUIRE(x.arg >= 0 && x.arg < (int)t->cols.size(), CAPSMI_ERR_ILLEGAL_ARGUMENT,
                         "expression column index out of range");
                 REQUIRE(x.arg < kMaxCols, CAPSMI_ERR_NOT_IMPLEMENTED, "expression references column >= 64");
-                if (nn > 1) no_list_key(t->cols[x.arg].type, t->cols[x.arg].name, "an expression operand");
-                pops = 0; break;
-            case CAPSMI_X_LIT: case CAPSMI_X_NULL: pops = 0; break;
-            case CAPSMI_X_NOT: case CAPSMI_X_ISNULL: case CAPSMI_X_ISNOTNULL: case CAPSMI_X_NEG: pops = 1; break;
+                break;
             case CAPSMI_X_AND: case CAPSMI_X_OR: case CAPSMI_X_COALESCE:
                 REQUIRE(x.arg >= 1, CAPSMI_ERR_ILLEGAL_ARGUMENT, "n-ary operator needs >= 1 operand");
-                pops = x.arg; break;
-            case CAPSMI_X_IN: REQUIRE(x.arg >= 0, CAPSMI_ERR_ILLEGAL_ARGUMENT, "IN arity"); pops = x.arg + 1; break;
-            case CAPSMI_X_EQ: case CAPSMI_X_NEQ: case CAPSMI_X_LT: case CAPSMI_X_LE: case CAPSMI_X_GT: case CAPSMI_X_GE:
-            case CAPSMI_X_ADD: case CAPSMI_X_SUB: case CAPSMI_X_MUL:
-            case CAPSMI_X_BITAND: case CAPSMI_X_BITOR: case CAPSMI_X_SHL: case CAPSMI_X_SHRU: pops = 2; break;
-            case CAPSMI_X_CASE:
-                REQUIRE(x.arg >= 1, CAPSMI_ERR_ILLEGAL_ARGUMENT, "CASE needs >= 1 alternative");
-                pops = 2 * x.arg + 1; break;
-            default: throw Error(CAPSMI_ERR_NOT_IMPLEMENTED, "unknown expression op " + std::to_string(x.op));
+                break;
+            case CAPSMI_X_IN: REQUIRE(x.arg >= 0, CAPSMI_ERR_ILLEGAL_ARGUMENT, "IN arity"); break;
+            case CAPSMI_X_CASE: REQUIRE(x.arg >= 1, CAPSMI_ERR_ILLEGAL_ARGUMENT, "CASE needs >= 1 alternative"); break;
+            default: break;
         }
-        REQUIRE(depth >= pops, CAPSMI_ERR_ILLEGAL_ARGUMENT, "malformed expression program (stack underflow)");
-        depth = depth - pops + 1;
-        if (depth > maxd) maxd = depth;
+        const int pops = expr_pops(x);
+        if (pops < 0) throw Error(CAPSMI_ERR_NOT_IMPLEMENTED, "unknown expression op " + std::to_string(x.op));
+        REQUIRE((int)ty.size() >= pops, CAPSMI_ERR_ILLEGAL_ARGUMENT, "malformed expression program (stack underflow)");
+        const int* opd = ty.data() + (ty.size() - pops);  // the operands, first pushed first
+        const bool list_op = x.op == CAPSMI_X_SIZE || x.op == CAPSMI_X_INDEX || x.op == CAPSMI_X_IN_LIST;
+        const int list_at = x.op == CAPSMI_X_IN_LIST ? 1 : 0;  // which operand is the list
+        for (int q = 0; q < pops; ++q)
+            REQUIRE(!is_list_type(opd[q]) || (list_op && q == list_at), CAPSMI_ERR_NOT_IMPLEMENTED,
+                    "a list value as an operand of expression op " + std::to_string(x.op) +
+                        " on the device path (only size(), list[i] and IN over a list column take one)");
+        int res = -1;
+        switch (x.op) {
+            case CAPSMI_X_COL: res = t->cols[x.arg].type; break;
+            case CAPSMI_X_LIT: res = x.type; break;
+            case CAPSMI_X_NULL: res = x.arg > 0 ? x.arg - 1 : -1; break;
+            case CAPSMI_X_SIZE: case CAPSMI_X_INDEX: case CAPSMI_X_IN_LIST: {
+                const int l = opd[list_at];
+                REQUIRE(l != CAPSMI_STR, CAPSMI_ERR_NOT_IMPLEMENTED,
+                        "size() / index / IN of a string value is not implemented (string lengths live in the caller's "
+                        "dictionary)");
+                REQUIRE(l < 0 || is_list_type(l), CAPSMI_ERR_ILLEGAL_ARGUMENT, "the operand of a list opcode is not a list");
+                // nothing but a column (or a NULL) yields a list: the node before an IN_LIST is its list operand
+                REQUIRE(x.op != CAPSMI_X_IN_LIST || prog[i - 1].op == CAPSMI_X_COL || prog[i - 1].op == CAPSMI_X_NULL,
+                        CAPSMI_ERR_ILLEGAL_ARGUMENT, "the list operand of IN_LIST must be a list column");
+                if (x.op == CAPSMI_X_INDEX)
+                    REQUIRE(opd[1] < 0 || opd[1] == CAPSMI_I64, CAPSMI_ERR_ILLEGAL_ARGUMENT, "a list index must be a Long");
+                res = x.op == CAPSMI_X_SIZE ? CAPSMI_I64 : (x.op == CAPSMI_X_IN_LIST ? CAPSMI_BOOL : (l < 0 ? -1 : l - CAPSMI_LIST));
+                break;
+            }
+            case CAPSMI_X_NEG: res = opd[0]; break;
+            case CAPSMI_X_COALESCE: case CAPSMI_X_CASE:
+                for (int q = x.op == CAPSMI_X_CASE ? 1 : 0; q < pops; q += x.op == CAPSMI_X_CASE ? 2 : 1)
+                    if (opd[q] >= 0) res = opd[q];
+                if (x.op == CAPSMI_X_CASE && res < 0) res = opd[pops - 1];
+                break;
+            case CAPSMI_X_ADD: case CAPSMI_X_SUB: case CAPSMI_X_MUL:
+                res = (opd[0] == CAPSMI_F64 || opd[1] == CAPSMI_F64) ? CAPSMI_F64 : CAPSMI_I64;
+                break;
+            case CAPSMI_X_BITAND: case CAPSMI_X_BITOR: case CAPSMI_X_SHL: case CAPSMI_X_SHRU: res = CAPSMI_I64; break;
+            default: res = CAPSMI_BOOL; break;
+        }
+        ty.resize(ty.size() - pops);
+        ty.push_back(res);
+        if ((int)ty.size() > maxd) maxd = (int)ty.size();
     }
-    REQUIRE(nn == 0 || depth == 1, CAPSMI_ERR_ILLEGAL_ARGUMENT, "expression program must leave one value");
+    REQUIRE(nn == 0 || ty.size() == 1, CAPSMI_ERR_ILLEGAL_ARGUMENT, "expression program must leave one value");
     REQUIRE(maxd <= kMaxStack, CAPSMI_ERR_NOT_IMPLEMENTED, "expression too deep");
+    REQUIRE(nn <= 1 || !is_list_type(ty[0]), CAPSMI_ERR_NOT_IMPLEMENTED,
+            "an expression that yields a list on the device path (only a column reference does)");
 }
 
 namespace {
+
+void launch_eval(capsmi_session* s, const capsmi_table* t, int32_t nn, const capsmi_expr* prog, int64_t* out,
+                 uint8_t* out_valid, uint8_t* flags);
+
+// first node of the complete sub-expression that ends at prog[end] (postfix)
+int subtree_start(const capsmi_expr* prog, int end) {
+    int want = 1;
+    for (int i = end; i >= 0; --i) {
+        want += expr_pops(prog[i]) - 1;
+        if (want == 0) return i;
+    }
+    throw Error(CAPSMI_ERR_INTERNAL, "malformed expression program");
+}
+
+// The program's first x IN list (node `at`; its list operand is the column reference before it) leaves the
+// interpreter: the probe sub-program is evaluated into a temporary column (a plain column reference is read
+// where it is), k_listexpr.hip's load-balanced pass produces a temporary BOOL column, and the sub-range
+// [probe .. IN_LIST] of the program becomes a reference to it, over a view of t with that column appended.
+// Further IN_LIST nodes are lowered by the recursion.
+void lower_in_list(capsmi_session* s, const capsmi_table* t, int32_t nn, const capsmi_expr* prog, int at, int64_t* out,
+                   uint8_t* out_valid, uint8_t* flags) {
+    const int64_t n = t->nrows;
+    const capsmi_expr& lx = prog[at - 1];
+    const int p1 = at - 2, p0 = subtree_start(prog, p1);
+    capsmi_table view;
+    view.sess = s;
+    view.nrows = n;
+    view.cols = t->cols;
+    std::vector<capsmi_expr> low(prog, prog + p0);
+    capsmi_expr ref{};
+    if (lx.op == CAPSMI_X_NULL) {  // a NULL list: NULL
+        ref.op = CAPSMI_X_NULL;
+        ref.arg = CAPSMI_BOOL + 1;
+    } else {
+        const Column& lc = t->cols[lx.arg];
+        Column probe;
+        if (p0 == p1 && prog[p0].op == CAPSMI_X_COL) {
+            probe = t->cols[prog[p0].arg];
+        } else {
+            probe.data = dev_alloc(sizeof(int64_t) * n, s);
+            probe.valid = dev_alloc(n, s);
+            probe.type = infer_type(t, p1 - p0 + 1, prog + p0);
+            launch_eval(s, t, p1 - p0 + 1, prog + p0, P<int64_t>(probe.data), P<uint8_t>(probe.valid), nullptr);
+        }
+        Column res;
+        res.name = "__in_list";
+        res.type = CAPSMI_BOOL;
+        res.data = dev_alloc(sizeof(int64_t) * n, s);
+        res.valid = dev_alloc(n, s);
+        list_contains(s, probe.d(), probe.v(), probe.type, lc.d(), lc.v(), *lc.list, n, P<int64_t>(res.data),
+                      P<uint8_t>(res.valid));
+        ref.op = CAPSMI_X_COL;
+        if ((int)view.cols.size() < kMaxCols) {
+            ref.arg = (int32_t)view.cols.size();
+            view.cols.push_back(std::move(res));
+        } else {  // a table at the interpreter's column limit: the view lends a column the rest does not read
+            std::vector<bool> used(kMaxCols, false);
+            for (int i = 0; i < nn; ++i)
+                if ((i < p0 || i > at) && prog[i].op == CAPSMI_X_COL) used[prog[i].arg] = true;
+            int slot = 0;
+            while (slot < kMaxCols && used[slot]) ++slot;
+            REQUIRE(slot < kMaxCols, CAPSMI_ERR_NOT_IMPLEMENTED, "IN over a list column in a program that reads 64 columns");
+            ref.arg = slot;
+            view.cols[slot] = std::move(res);
+        }
+    }
+    low.push_back(ref);
+    low.insert(low.end(), prog + at + 1, prog + nn);
+    launch_eval(s, &view, (int32_t)low.size(), low.data(), out, out_valid, flags);
+}
 
 void launch_eval(capsmi_session* s, const capsmi_table* t, int32_t nn, const capsmi_expr* prog, int64_t* out,
                  uint8_t* out_valid, uint8_t* flags) {
     validate_program(t, nn, prog);
     const int64_t n = t->nrows;
     if (n == 0) return;
+    for (int i = 0; i < nn; ++i)
+        if (prog[i].op == CAPSMI_X_IN_LIST) return lower_in_list(s, t, nn, prog, i, out, out_valid, flags);
     ColPtrs cp;
-    for (int c = 0; c < kMaxCols; ++c) { cp.data[c] = nullptr; cp.valid[c] = nullptr; cp.type[c] = 0; }
+    for (int c = 0; c < kMaxCols; ++c) {
+        cp.data[c] = nullptr;
+        cp.valid[c] = nullptr;
+        cp.type[c] = 0;
+        cp.loff[c] = cp.lval[c] = nullptr;
+    }
     for (size_t c = 0; c < t->cols.size() && c < (size_t)kMaxCols; ++c) {
         cp.data[c] = t->cols[c].d();
         cp.valid[c] = t->cols[c].v();
         cp.type[c] = (int8_t)t->cols[c].type;
+        if (t->cols[c].list) {
+            cp.loff[c] = P<int64_t>(t->cols[c].list->offsets);
+            cp.lval[c] = P<int64_t>(t->cols[c].list->values);
+        }
     }
     Buf dprog = dev_alloc(sizeof(capsmi_expr) * (nn > 0 ? nn : 1), s);
     if (nn > 0)

@@ -676,16 +676,9 @@ void bitmap_set_range(capsmi_bitmap* b, int64_t b0, int64_t b1) {
 bool compile_range_pred(const capsmi_table* t, int32_t nn, const capsmi_expr* prog, RangePred& rp) {
     rp = RangePred();
     if (nn <= 0) return false;
-    auto arity = [](const capsmi_expr& x) {
-        switch (x.op) {
-            case CAPSMI_X_COL: case CAPSMI_X_LIT: case CAPSMI_X_NULL: return 0;
-            case CAPSMI_X_NOT: case CAPSMI_X_ISNULL: case CAPSMI_X_ISNOTNULL: case CAPSMI_X_NEG: return 1;
-            case CAPSMI_X_AND: case CAPSMI_X_OR: case CAPSMI_X_COALESCE: return (int)x.arg;
-            case CAPSMI_X_IN: return (int)x.arg + 1;
-            case CAPSMI_X_CASE: return 2 * (int)x.arg + 1;
-            default: return 2;
-        }
-    };
+    for (int i = 0; i < nn; ++i)
+        if (expr_pops(prog[i]) < 0) return false;  // an opcode the interpreter does not know
+    auto arity = [](const capsmi_expr& x) { return expr_pops(x); };
     // conjunct spans [lo, hi] of the root AND (or the root itself)
     std::vector<std::pair<int, int>> spans;
     const capsmi_expr& root = prog[nn - 1];

@@ -37,7 +37,7 @@ struct AggSpec {
 
 struct PlanNode {
     enum Kind { SELECT, DROP, RENAME, FILTER, WITH_COLUMNS, JOIN, UNION, DISTINCT, DISTINCT_ON, GROUP, ORDER, SKIP, LIMIT,
-                EXPLODE };
+                EXPLODE, RANGE };
     Kind kind = SELECT;
     std::vector<capsmi_table*> in;            // retained inputs
     std::vector<std::string> a, b;            // column names (see builders)
@@ -49,6 +49,7 @@ struct PlanNode {
     // EXPLODE: b[0] the item column; a[0] the list column, or a empty for the constant form with its
     // `n` values `vals` of element type `jt`
     std::vector<capsmi_value> vals;
+    // RANGE: a[0] the list column; progs[0..2] the from / to / step programs (step empty: the literal 1)
     ~PlanNode() {
         for (capsmi_table* t : in) capsmi_table_release(t);
     }
@@ -126,15 +127,11 @@ std::vector<const char*> cstrs(const std::vector<std::string>& v) {
     return o;
 }
 
+// operands of a node of a validated program (the one table of k_expr.hip)
 int arity(const capsmi_expr& x) {
-    switch (x.op) {
-        case CAPSMI_X_COL: case CAPSMI_X_LIT: case CAPSMI_X_NULL: return 0;
-        case CAPSMI_X_NOT: case CAPSMI_X_ISNULL: case CAPSMI_X_ISNOTNULL: case CAPSMI_X_NEG: return 1;
-        case CAPSMI_X_AND: case CAPSMI_X_OR: case CAPSMI_X_COALESCE: return x.arg;
-        case CAPSMI_X_IN: return x.arg + 1;
-        case CAPSMI_X_CASE: return 2 * x.arg + 1;
-        default: return 2;
-    }
+    const int k = expr_pops(x);
+    REQUIRE(k >= 0, CAPSMI_ERR_NOT_IMPLEMENTED, "unknown expression op " + std::to_string(x.op));
+    return k;
 }
 
 // ============================ operator-by-operator execution ===============================
@@ -183,6 +180,7 @@ capsmi_table* exec_node(const PlanNode& p) {
             if (p.a.empty()) check(eager_explode_values(x, p.jt, (int32_t)p.n, p.vals.data(), p.b[0].c_str(), nullptr, &r));
             else check(eager_explode(x, p.a[0].c_str(), p.b[0].c_str(), nullptr, &r));
             break;
+        case PlanNode::RANGE: check(eager_with_range_column(x, p.progs[0], p.progs[1], p.progs[2], p.a[0].c_str(), &r)); break;
     }
     return r;
 }
@@ -2215,6 +2213,30 @@ Res exec(capsmi_table* t, const Names& need, std::vector<Pred> preds, const Pare
             r.reset();
             return finish(owned(o), need, stay);
         }
+        case PlanNode::RANGE: {
+            // row-local, like WITH_COLUMNS: a conjunct that reads the new column stays above, the others run on
+            // the input rows; the input keeps the columns somebody above or an operand program reads
+            const std::string& name = p.a[0];
+            std::vector<Pred> down, stay;
+            for (Pred& pr : preds) (has(pr.names, name) ? stay : down).push_back(std::move(pr));
+            Names out = need;
+            for (const Pred& pr : stay)
+                for (const std::string& n : pr.names) add(out, n);
+            Names nin;
+            for (const std::string& n : out)
+                if (n != name) add(nin, n);
+            for (const auto& prog : p.progs)
+                for (const capsmi_expr& e : prog)
+                    if (e.op == CAPSMI_X_COL) add(nin, x->cols.at(e.arg).name);
+            if (nin.empty() && !x->cols.empty()) add(nin, x->cols[0].name);  // the row count travels with a column
+            Res r = exec(x, nin, std::move(down), par);
+            capsmi_table* o = nullptr;
+            check(eager_with_range_column(r.t, remap(p.progs[0], x, r.t), remap(p.progs[1], x, r.t),
+                                          remap(p.progs[2], x, r.t), name.c_str(), &o));
+            o->partitioned = r.t->partitioned;  // no exchange
+            r.reset();
+            return finish(owned(o), need, stay);
+        }
         default: {  // union, distinct, grouping, ordering, skip / limit: conjuncts stay above
             std::vector<Names> nin(p.in.size());
             for (size_t i = 0; i < p.in.size(); ++i) nin[i] = all_names(p.in[i]);
@@ -2470,6 +2492,30 @@ capsmi_status capsmi_explode_values(capsmi_table* t, int32_t elem_type, int32_t 
         bool any_null = false;
         for (const capsmi_value& v : p->vals) any_null |= v.is_null != 0;
         return lazy_table(t->sess, p, explode_schema(t, schema_col(item_name, elem_type, any_null)));
+    });
+}
+
+capsmi_status capsmi_with_range_column(capsmi_table* t, int32_t from_nnodes, const capsmi_expr* from_prog,
+                                       int32_t to_nnodes, const capsmi_expr* to_prog, int32_t step_nnodes,
+                                       const capsmi_expr* step_prog, const char* name, capsmi_table** out) {
+    return build(t, out, [&] {
+        need(name, "column name");
+        auto p = std::make_shared<PlanNode>();
+        p->kind = PlanNode::RANGE;
+        hold(*p, t);
+        p->a = {name};
+        const int32_t nn[3] = {from_nnodes, to_nnodes, step_prog ? step_nnodes : 0};
+        const capsmi_expr* pr[3] = {from_prog, to_prog, step_prog};
+        for (int i = 0; i < 3; ++i) {
+            REQUIRE(nn[i] > 0 ? pr[i] != nullptr : i == 2, CAPSMI_ERR_ILLEGAL_ARGUMENT, "range: null or empty operand program");
+            std::vector<capsmi_expr> prog(pr[i], pr[i] + nn[i]);
+            if (has_params(nn[i], pr[i])) prog = bind_params(t->sess, nn[i], pr[i]);
+            validate_program(t, (int32_t)prog.size(), prog.data());
+            REQUIRE(prog.empty() || infer_type(t, (int32_t)prog.size(), prog.data()) == CAPSMI_I64,
+                    CAPSMI_ERR_ILLEGAL_ARGUMENT, "range: operands must be Long");
+            p->progs.push_back(std::move(prog));
+        }
+        return lazy_table(t->sess, p, explode_schema(t, schema_col(name, CAPSMI_LIST_I64, true)));
     });
 }
 

@@ -69,8 +69,11 @@ enum {
  * (CAPSMI_LIST_I64 ... CAPSMI_LIST_STR); rows are read with capsmi_table_export_list, opened again into
  * rows by capsmi_explode, and ingested from the host by capsmi_table_add_list_column.  List columns
  * travel through select / drop / rename / filter / join payloads / union all / order-by payloads /
- * skip / limit; using one as a join, grouping, distinct or sort key, or inside an expression, is
- * CAPSMI_ERR_NOT_IMPLEMENTED. */
+ * skip / limit, and are made from Long operands by capsmi_with_range_column.  Inside an expression a list
+ * column is an operand of CAPSMI_X_SIZE, CAPSMI_X_INDEX and CAPSMI_X_IN_LIST only: CAPSMI_X_COL of a list
+ * column pushes a list value (the row's list, typed CAPSMI_LIST + elem, or NULL for a null row), and a list
+ * value that reaches any other opcode is CAPSMI_ERR_NOT_IMPLEMENTED, as is a list column used as a join,
+ * grouping, distinct or sort key. */
 enum {
     CAPSMI_LIST = 8,
     CAPSMI_LIST_I64 = 8,
@@ -130,10 +133,24 @@ enum {
     CAPSMI_X_SHRU = 23,     /* Long a >>> (b & 63) (:273-274, functions.shiftRightUnsigned) */
     CAPSMI_X_CASE = 24,     /* stack [p1, v1, .., p_arg, v_arg, default]: v_i of the first TRUE p_i, else
                                default (push a NULL for none); CaseExpr, :283-298 */
-    CAPSMI_X_PARAM = 25     /* push query parameter `arg` of the session's table (capsmi_session_set_params);
+    CAPSMI_X_PARAM = 25,    /* push query parameter `arg` of the session's table (capsmi_session_set_params);
                                bound to a literal when the program enters the library, as Param(name) ->
                                functions.lit (:86-92).  A list parameter may only be an element operand of
                                IN, where it expands to its values (:86-89, functions.array) */
+    /* List operands (a CAPSMI_X_COL of a CAPSMI_LIST_* column; nothing else yields a list). */
+    CAPSMI_X_SIZE = 26,     /* stack [list]: Long element count; NULL for a NULL list (the bag the acceptance
+                               case "size() on null" states, not Spark 2's legacy -1); Size, :124-130 */
+    CAPSMI_X_INDEX = 27,    /* stack [list, i]: element i (0-based) of the element type; NULL when the list or i
+                               is NULL or when i < 0 or i >= size (Spark's GetArrayItem: a negative index does
+                               not count from the end); i must be Long, else CAPSMI_ERR_ILLEGAL_ARGUMENT;
+                               ContainerIndex, :300-307 */
+    CAPSMI_X_IN_LIST = 28   /* stack [x, list]: BOOL, 3VL: NULL when x or the list is NULL; TRUE when some
+                               element equals x under the interpreter's `=` (Long against Double as doubles,
+                               NaN = NaN); NULL when the element type is not comparable with x (Long against
+                               STR), as `=` gives; else FALSE (stores hold no element nulls).  In with a
+                               list-valued right-hand side, array_contains, :138-145.  Each IN_LIST of a
+                               program runs as one load-balanced pass over all the rows' elements before the
+                               row-wise interpreter, which then reads its result as a column. */
 };
 
 typedef struct {
@@ -384,6 +401,26 @@ capsmi_status capsmi_explode(capsmi_table* t, const char* list_col, const char* 
  * gives zero rows.  Values are copied. */
 capsmi_status capsmi_explode_values(capsmi_table* t, int32_t elem_type, int32_t count, const capsmi_value* values,
                                     const char* item_name, capsmi_table** out);
+
+/* range(from, to[, step]) as a list column (Range, SparkSQLExprMapper.scala:243-245; the reference's rangeUdf,
+ * CAPSFunctions.scala:50, Scala's from.to(to, step), over Long).  The three programs are scalar Long
+ * expressions over `t` (step_prog NULL with step_nnodes 0: the literal 1); the result is `t` plus a
+ * CAPSMI_LIST_I64 column `name` under the capsmi_with_columns replace-or-append rule.  Row i's list is from,
+ * from + step, ... up to the last element <= to (step > 0) or >= to (step < 0); empty when `to` lies on the
+ * wrong side of `from`; NULL when an operand is NULL.  Lengths are computed without signed overflow and no
+ * element past `to` is ever formed, so operands at the ends of the Long range are safe.  A non-Long operand is
+ * CAPSMI_ERR_ILLEGAL_ARGUMENT when the node is built; a row with step == 0 fails the action with
+ * CAPSMI_ERR_ILLEGAL_ARGUMENT ("range: step 0"), as Scala throws; a total element count beyond what the
+ * session can allocate is CAPSMI_ERR_UNSUPPORTED with the count in the message, decided from the scanned
+ * lengths before anything sized by the count is allocated.  "Can allocate" is judged against the device's
+ * whole memory (8 bytes per element), and a single row of 2^40 elements or more (of 2^62 / rows elements where that is less, so that the sum
+ * cannot overflow) is always refused (its length
+ * is not counted further: the message then says "N or more"); a count that the device could hold but that
+ * is not free at the moment, the per-row buffers included, is the allocator's CAPSMI_ERR_OUT_OF_MEMORY.
+ * Lazy and row-local: no collective is called and a partitioned table stays partitioned. */
+capsmi_status capsmi_with_range_column(capsmi_table* t, int32_t from_nnodes, const capsmi_expr* from_prog,
+                                       int32_t to_nnodes, const capsmi_expr* to_prog, int32_t step_nnodes,
+                                       const capsmi_expr* step_prog, const char* name, capsmi_table** out);
 
 /* ---- graph fast path ------------------------------------------------------------------
  * The relational planner lowers Expand into `join(relScan, source = start)` then

@@ -65,6 +65,9 @@ object Capsmi {
   final val X_SHRU = 23
   final val X_CASE = 24
   final val X_PARAM = 25
+  final val X_SIZE = 26     // [list]: element count, NULL for a NULL list
+  final val X_INDEX = 27    // [list, i]: element i (0-based), NULL outside the list
+  final val X_IN_LIST = 28  // [x, list]: x IN list-column, 3VL
 
   // join types (JoinType of RelationalPlanner; SparkTable.scala:205-229)
   final val JOIN_INNER = 0
@@ -240,6 +243,9 @@ trait CapsmiLib extends Library {
   def capsmi_with_column_renamed(t: Pointer, oldName: String, newName: String, out: PointerByReference): Int
   // UNWIND: Explode(list) AS item (RelationalPlanner.scala:94-96) of a list column / of literal values
   def capsmi_explode(t: Pointer, listCol: String, itemName: String, out: PointerByReference): Int
+  // range(from, to[, step]) per row as a list column (stepProg null: the literal 1)
+  def capsmi_with_range_column(t: Pointer, fromNnodes: Int, fromProg: CapsmiExpr, toNnodes: Int, toProg: CapsmiExpr,
+                               stepNnodes: Int, stepProg: CapsmiExpr, name: String, out: PointerByReference): Int
   def capsmi_explode_values(t: Pointer, elemType: Int, count: Int, values: CapsmiValue, itemName: String,
                             out: PointerByReference): Int
   // list-property ingest from host CSR arrays (CAPSTable's array columns)

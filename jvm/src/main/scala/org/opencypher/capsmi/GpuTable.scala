@@ -214,6 +214,54 @@ final class GpuTable private (val handle: Pointer)(implicit val session: GpuSess
       case _: Explode => true
       case other => other.children.exists(hasExplode)
     }
+    // Range (SparkSQLExprMapper.scala:243-245): a column that is a Range goes to capsmi_with_range_column; a Range
+    // that is the argument of a top-level Explode, of Size, the container of ContainerIndex or the right side of In
+    // is first added as a temporary list column under a name the table does not have, which is dropped
+    // afterwards.  Either splits the call as an Explode does.  A Range anywhere else, a Range inside a Range's
+    // operands included, is NotImplementedException.
+    def hasRange(e: Expr): Boolean = e match {
+      case _: Range => true
+      case other => other.children.exists(hasRange)
+    }
+    def plain(r: Range): Range = {
+      if ((Seq(r.from, r.to) ++ r.o).exists(x => hasRange(x) || hasExplode(x)))
+        throw NotImplementedException("Range nested in a Range operand")
+      r
+    }
+    def misplaced(): Nothing = throw NotImplementedException(
+      "Range on the device path: a whole withColumns column or the argument of Explode / Size / ContainerIndex / In")
+    // the Ranges of `e` that sit in an allowed place
+    def lifted(e: Expr): Seq[Range] = e match {
+      case _: Range => misplaced()
+      case _: Explode => throw NotImplementedException("Explode nested in another expression")
+      case Size(r: Range) => Seq(plain(r))
+      case ContainerIndex(r: Range, index) => plain(r) +: lifted(index)
+      case In(lhs, r: Range) => lifted(lhs) :+ plain(r)
+      case other => other.children.toSeq.flatMap(lifted)
+    }
+    def freshNames(taken: Seq[String]): Iterator[String] =
+      Iterator.from(0).map(i => s"__capsmi_range_$i").filterNot(taken.contains)
+    val rangeAt = columns.indexWhere { case (e, _) => hasRange(e) }
+    if (rangeAt >= 0) {
+      val (before, rest) = columns.splitAt(rangeAt)
+      val base = if (before.isEmpty) this else withColumns(before: _*)
+      val (e, name) = rest.head
+      val names = freshNames(base.physicalColumns ++ columns.map(_._2))
+      val added = e match {
+        case r: Range => base.withRangeColumn(plain(r), name)
+        case Explode(r: Range) =>
+          val tmp = names.next()
+          val listed = base.withRangeColumn(plain(r), tmp)
+          listed.wrap(I.capsmi_explode(listed.handle, tmp, name, _)).drop(tmp)
+        case other =>
+          val temps = lifted(other).distinct.map(r => r -> names.next())
+          val listed = temps.foldLeft(base) { case (t, (r, tmp)) => t.withRangeColumn(r, tmp) }
+          val prog = ExprCompiler(listed, header, parameters, temps.toMap[Expr, String]).compile(other)
+          listed.wrap(I.capsmi_with_columns(listed.handle, 1, CapsmiLib.exprColumns(Seq(name -> prog)), _))
+            .drop(temps.map(_._2): _*)
+      }
+      return if (rest.tail.isEmpty) added else added.withColumns(rest.tail: _*)
+    }
     val at = columns.indexWhere { case (e, _) => hasExplode(e) }
     if (at >= 0) {
       if (columns.count { case (e, _) => hasExplode(e) } > 1)
@@ -225,6 +273,17 @@ final class GpuTable private (val handle: Pointer)(implicit val session: GpuSess
     val compiler = ExprCompiler(this, header, parameters)
     val progs = columns.map { case (e, name) => name -> compiler.compile(e) }
     wrap(I.capsmi_with_columns(handle, progs.size, CapsmiLib.exprColumns(progs), _))
+  }
+
+  /** range(from, to[, step]) per row as the Long list column `name` (capsmi_with_range_column; the reference's
+    * rangeUdf, CAPSFunctions.scala:50): inclusive bounds, NULL when an operand is NULL, step 0 fails the action. */
+  private def withRangeColumn(r: Range, name: String)(implicit header: RecordHeader, parameters: CypherMap): GpuTable = {
+    val compiler = ExprCompiler(this, header, parameters)
+    val from = compiler.compile(r.from)
+    val to = compiler.compile(r.to)
+    val step = r.o.map(compiler.compile)
+    wrap(I.capsmi_with_range_column(handle, from.size, CapsmiLib.exprs(from), to.size, CapsmiLib.exprs(to),
+      step.fold(0)(_.size), step.map(CapsmiLib.exprs).orNull, name, _))
   }
 
   /** functions.explode (SparkSQLExprMapper.scala:237-241) of a list column (capsmi_explode), or of a ListLit /
@@ -287,10 +346,14 @@ final class GpuTable private (val handle: Pointer)(implicit val session: GpuSess
   * okapi Expr -> postfix capsmi_expr program, as SparkSQLExprMapper.asSparkSQLExpr
   * (spark-cypher/.../impl/SparkSQLExprMapper.scala:81-312) maps it to a Spark Column: header lookups
   * to column references (:93-104), literals (:107-117), parameters through the session's parameter
-  * table (CAPSMI_X_PARAM, :86-92), predicates and arithmetic.  Shapes the device path does not
-  * evaluate (string matching, functions, maps, lists other than IN's) raise NotImplementedException.
+  * table (CAPSMI_X_PARAM, :86-92), predicates and arithmetic, and the list expressions Size (:124-130),
+  * ContainerIndex (:300-307) and In with a list-typed column on the right (array_contains, :138-145) as
+  * CAPSMI_X_SIZE / CAPSMI_X_INDEX / CAPSMI_X_IN_LIST.  `lists` names the temporary list columns that stand for
+  * Range operands (GpuTable.withColumns).  Shapes the device path does not evaluate (string matching, other
+  * functions, maps, size() of a string) raise NotImplementedException.
   */
-final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters: CypherMap) {
+final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters: CypherMap,
+                              lists: Map[Expr, String] = Map.empty) {
   private type Node = (Int, Int, Int, Long)
   private val cols = table.physicalColumns
   private val params = mutable.LinkedHashMap.empty[String, Int]
@@ -320,7 +383,27 @@ final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters:
     out += (if (i >= 0) (Capsmi.X_COL, i, 0, 0L) else nullOf(e.cypherType))
   }
 
+  /** Whether `e` is a list the library holds as a column: a temporary Range column or a list-typed header column. */
+  private def listColumn(e: Expr): Boolean =
+    lists.contains(e) || (e.cypherType.material.isInstanceOf[CTList] && header.contains(e) && cols.contains(header.column(e)))
+
+  /** The list operand of Size / ContainerIndex / In: a reference to its column. */
+  private def list(e: Expr, out: mutable.ArrayBuffer[Node]): Unit = lists.get(e) match {
+    case Some(tmp) => out += ((Capsmi.X_COL, cols.indexOf(tmp), 0, 0L))
+    case None if listColumn(e) => column(e, out)
+    case None => e match {
+      case p: Property if !header.contains(p) => out += nullOf(CTNull) // a missing property: a NULL list
+      case other => throw NotImplementedException(s"list $other on the device path: a list column or a Range")
+    }
+  }
+
   private def go(e: Expr, out: mutable.ArrayBuffer[Node]): Unit = e match {
+    case Size(ListLit(vs)) => out += lit(Capsmi.I64, vs.size.toLong)
+    case Size(x) if x.cypherType.material == CTString =>
+      throw NotImplementedException("size() of a string on the device path: string lengths live in the caller's dictionary")
+    case Size(x) => list(x, out); out += ((Capsmi.X_SIZE, 0, 0, 0L))
+    case ContainerIndex(container, index) => list(container, out); go(index, out); out += ((Capsmi.X_INDEX, 0, 0, 0L))
+    case In(lhs, rhs) if listColumn(rhs) => go(lhs, out); list(rhs, out); out += ((Capsmi.X_IN_LIST, 0, 0, 0L))
     case p: Property if !header.contains(p) => out += nullOf(p.cypherType)
     case p: Param if !header.contains(p) =>
       out += ((Capsmi.X_PARAM, params.getOrElseUpdate(p.name, params.size), 0, 0L))
