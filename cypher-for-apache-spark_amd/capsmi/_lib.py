@@ -146,6 +146,7 @@ _SIGS = {
     "capsmi_table_add_list_column": (c_int32, [P, c_char_p, c_int32, c_void_p, c_void_p, c_void_p, PP]),
     "capsmi_with_range_column": (c_int32, [P, c_int32, POINTER(CapsmiExpr), c_int32, POINTER(CapsmiExpr), c_int32,
                                            POINTER(CapsmiExpr), c_char_p, PP]),
+    "capsmi_with_mask_list_column": (c_int32, [P, c_int32, c_int32, STRS, POINTER(c_int64), c_char_p, PP]),
     "capsmi_bitmap_create": (c_int32, [P, c_int64, c_int64, PP]),
     "capsmi_bitmap_add_scan": (c_int32, [P, P, c_char_p, c_int32, POINTER(CapsmiExpr)]),
     "capsmi_bitmap_stats": (c_int32, [P, POINTER(c_int64), POINTER(c_int32)]),

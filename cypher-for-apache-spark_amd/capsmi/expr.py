@@ -16,6 +16,10 @@ array_contains, :138-145; three-valued) over a list column, and Range (:243-245;
 rangeUdf, inclusive bounds, NULL when an operand is NULL, step 0 an error), which
 ``GpuTable.withColumns`` turns into a list column (``capsmi_with_range_column``).
 
+Entity functions (:192-227): Labels and Keys, String lists built on the device from flag and property columns
+(``capsmi_with_mask_list_column``), and RelType, a Case over the type flags; startNode / endNode are the
+relationship's source and target columns.
+
 ``compile_program`` lowers a tree to the postfix ``capsmi_expr`` program of include/capsmi.h.
 """
 from __future__ import annotations
@@ -198,6 +202,76 @@ class Range(Expr):
     step: object = None
 
 
+def _sorted_by_name(cols, names):
+    cols, names = tuple(cols), tuple(names)
+    if len(cols) != len(names):
+        raise ValueError(f"{len(cols)} columns for {len(names)} names")
+    order = sorted(range(len(names)), key=lambda i: names[i])
+    return tuple(cols[i] for i in order), tuple(names[i] for i in order)
+
+
+@dataclass(frozen=True, eq=False)
+class Labels(Expr):
+    """Labels(node) (SparkSQLExprMapper.scala:192-201; CAPSFunctions.scala:73-81 get_node_labels): the String
+    list of the ``names`` whose Boolean flag column is TRUE, in name order (``sortBy(_._1)``, :198 -- sorted
+    here, whatever order is given).  A NULL flag is not set, so a null node (an OPTIONAL MATCH miss) gives
+    ``[]``, never NULL: a reading of filterWithMask's ``case (label, true)``, not an observation of a run.
+    Allowed where a ``Range`` is: a whole ``withColumns`` column, the argument of ``Explode`` and the list of
+    ``Size`` / ``Index`` / ``InList`` (``capsmi_with_mask_list_column``, CAPSMI_MASK_TRUE)."""
+    flag_cols: Tuple[str, ...]
+    names: Tuple[str, ...]
+
+    def __post_init__(self):
+        cols, names = _sorted_by_name(self.flag_cols, self.names)
+        object.__setattr__(self, "flag_cols", cols)
+        object.__setattr__(self, "names", names)
+
+
+@dataclass(frozen=True, eq=False)
+class Keys(Expr):
+    """Keys(entity) (SparkSQLExprMapper.scala:203-208; CAPSFunctions.scala:83-91 get_property_keys): the String
+    list of the ``names`` whose property column is not NULL in the row, in key order (``sortBy(_.key.name)``,
+    :205 -- sorted here).  Columns of any type, list columns included; never NULL (a null entity gives ``[]``,
+    read from filterNotNull's ``value != null``).  Allowed where a ``Labels`` is (CAPSMI_MASK_NOT_NULL)."""
+    cols: Tuple[str, ...]
+    names: Tuple[str, ...]
+
+    def __post_init__(self):
+        cols, names = _sorted_by_name(self.cols, self.names)
+        object.__setattr__(self, "cols", cols)
+        object.__setattr__(self, "names", names)
+
+
+@dataclass(frozen=True, eq=False)
+class RelType(Expr):
+    """Type(rel) over relationship-type flag columns (SparkSQLExprMapper.scala:210-219; CAPSFunctions.scala:68-71
+    get_rel_type, ``headOption.orNull``): the name of the first TRUE flag in the order given (the reference does
+    not sort the types), NULL when none is.  Compiled as the ``Case`` of ``to_case``; no kernel of its own."""
+    flag_cols: Tuple[str, ...]
+    names: Tuple[str, ...]
+
+    def __post_init__(self):
+        object.__setattr__(self, "flag_cols", tuple(self.flag_cols))
+        object.__setattr__(self, "names", tuple(self.names))
+        if len(self.flag_cols) != len(self.names):
+            raise ValueError(f"{len(self.flag_cols)} columns for {len(self.names)} names")
+
+    def to_case(self) -> "Case":
+        return Case(tuple((Col(c), Lit(n)) for c, n in zip(self.flag_cols, self.names)), Lit(None, STR))
+
+
+MASK_TRUE, MASK_NOT_NULL = 0, 1  # include/capsmi.h CAPSMI_MASK_*
+
+
+def mask_list_args(e: Expr):
+    """(mode, columns, names) of a Labels / Keys for ``GpuTable.withMaskListColumn``."""
+    if isinstance(e, Labels):
+        return MASK_TRUE, e.flag_cols, e.names
+    if isinstance(e, Keys):
+        return MASK_NOT_NULL, e.cols, e.names
+    raise TypeError(f"not a Labels / Keys: {e!r}")
+
+
 def _children(e: Expr):
     for v in e.__dict__.values():
         for x in (v if isinstance(v, tuple) else (v,)):
@@ -212,9 +286,9 @@ def contains_range(e: Expr) -> bool:
 
 
 def needs_list_lowering(e: Expr) -> bool:
-    """Whether ``GpuTable`` has to rewrite ``e`` before compiling it: a Range, a Size or an InList occurs, or an
-    Index of a literal."""
-    if isinstance(e, (Range, Size, InList)) or (isinstance(e, Index) and isinstance(e.list, (ListLit, Lit))):
+    """Whether ``GpuTable`` has to rewrite ``e`` before compiling it: a Range, a Labels, a Keys, a Size or an
+    InList occurs, or an Index of a literal."""
+    if isinstance(e, (Range, Labels, Keys, Size, InList)) or (isinstance(e, Index) and isinstance(e.list, (ListLit, Lit))):
         return True
     return any(needs_list_lowering(c) for c in _children(e))
 
@@ -256,6 +330,10 @@ def columns_of(e: Expr) -> set:
     """Physical columns an expression reads."""
     if isinstance(e, Col):
         return {e.name}
+    if isinstance(e, (Labels, RelType)):
+        return set(e.flag_cols)
+    if isinstance(e, Keys):
+        return set(e.cols)
     out = set()
     for v in e.__dict__.values():
         if isinstance(v, Expr):
@@ -348,6 +426,8 @@ def compile_program(e: Expr, column_index: Callable[[str], int], encode_str: Cal
             go(x.arg)
             go(x.list)
             out.append((X_IN_LIST, 0, 0, 0))
+        elif isinstance(x, RelType):
+            go(x.to_case())
         elif isinstance(x, Case):
             if not x.alternatives:
                 go(x.default if x.default is not None else NULL)

@@ -28,7 +28,7 @@ from typing import Dict, FrozenSet, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .expr import (BOOL, F64, I64, LIST, STR, Ands, BinOp, Col, Explode, Expr, In, IsNotNull, IsNull, ListLit, Lit, Not, Ors,
-                   Index, InList, Range, Size, ands, eq)
+                   Index, InList, Keys, Labels, Range, Size, ands, eq)
 from .table import ColumnData, decode_value
 
 
@@ -469,7 +469,8 @@ def to_expr(spec, header: Sequence[str]) -> Expr:
         return IsNotNull(to_expr(spec[1], header))
     if op == "in":
         return In(to_expr(spec[1], header), tuple(Lit(v) for v in spec[2]))
-    # list expressions: the list operand is a list column, ["listlit", [...]] or ["range", ...]
+    # list expressions: the list operand is a list column, ["listlit", [...]], ["range", ...], ["labels", var] or
+    # ["keys", var]
     if op == "size":
         return Size(_list_operand(spec[1], header))
     if op == "index":
@@ -481,6 +482,17 @@ def to_expr(spec, header: Sequence[str]) -> Expr:
             raise PlanningError(f"range takes two or three operands: {spec!r}")
         opd = [to_expr(s, header) if isinstance(s, list) else Lit(s) for s in spec[1:]]
         return Range(opd[0], opd[1], opd[2] if len(opd) > 2 else None)
+    # entity functions (SparkSQLExprMapper.scala:192-227): the columns the variable owns in the current header
+    if op == "labels":  # header.labelsFor(node)
+        flags = [h for h in header if h.startswith(f"{spec[1]}:")]
+        return Labels(tuple(flags), tuple(h[len(spec[1]) + 1:] for h in flags))
+    if op == "keys":  # header.propertiesFor(entity)
+        props = [h for h in header if h.startswith(f"{spec[1]}.") and not h.startswith(f"{spec[1]}.__")]
+        return Keys(tuple(props), tuple(h[len(spec[1]) + 1:] for h in props))
+    if op == "startnode":  # header.startNodeFor(rel)
+        return Col(f"{spec[1]}.__src")
+    if op == "endnode":  # header.endNodeFor(rel)
+        return Col(f"{spec[1]}.__dst")
     raise PlanningError(f"unknown expression {spec!r}")
 
 
@@ -519,7 +531,8 @@ class Planner:
         """Execute ``{"clauses": [{"match": str, "where": expr?}], "return": {...}}``; returns
         (table, output spec) ready for :func:`result_rows`.  Further clause kinds:
         ``{"unwind": spec, "as": name}`` with spec ``["listlit", [...]]``, ``["param", name]`` (a list of the
-        query's ``"params"`` map), ``["var", column]``, ``["prop", var, key]`` or ``["range", from, to, step?]``, and
+        query's ``"params"`` map), ``["var", column]``, ``["prop", var, key]``, ``["range", from, to, step?]``, ``["labels", var]`` or
+        ``["keys", var]``, and
         ``{"with": {"items": ...}, "where": expr?}`` (the items of a RETURN)."""
         cur: Optional[_Op] = None
         varlen: Dict[str, int] = {}
@@ -562,7 +575,7 @@ class Planner:
             if not isinstance(params.get(spec[1]), (list, tuple)):
                 raise PlanningError(f"UNWIND needs a list parameter ${spec[1]}")
             lst = ListLit(tuple(params[spec[1]]))
-        elif kind == "range":  # UNWIND range(from, to[, step]): literal or expression operands
+        elif kind in ("range", "labels", "keys"):  # UNWIND range(from, to[, step]) / labels(n) / keys(n)
             lst = to_expr(spec, cur.header)
         elif kind in ("var", "prop"):
             col = spec[1] if kind == "var" else f"{spec[1]}.{spec[2]}"

@@ -20,14 +20,16 @@ from typing import Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .expr import (BOOL, F64, I64, LIST, STR, BinOp, CapsmiExpr, Case, Col, Explode, Expr, In, Index, InList, ListLit, Lit, Param, Range,
-                   Size, contains_range, needs_list_lowering, compile_program,
-                   contains_explode, to_ctypes)
+from .expr import (BOOL, F64, I64, LIST, STR, BinOp, CapsmiExpr, Case, Col, Explode, Expr, In, Index, InList, Keys, Labels, ListLit,
+                   Lit, Param, Range, Size, contains_range, needs_list_lowering, compile_program,
+                   contains_explode, mask_list_args, to_ctypes)
 
 _TLS = threading.local()
 
 _EXPR_PTR = ctypes.POINTER(CapsmiExpr)
-_TMP_IDS = itertools.count()  # names of the temporary list columns of Range operands
+_TMP_IDS = itertools.count()  # names of the temporary list columns of Range / Labels / Keys operands
+_LIST_SOURCES = (Range, Labels, Keys)  # the expressions that a plan node of their own turns into a list column
+_MISPLACED = "{} is a whole withColumns column or the argument of Explode / Size / Index / InList"
 _LIT_PROGS = {}  # (python type, value, declared type) -> one-node program of a Boolean / Long / null literal
 
 JOIN_TYPES = {"inner": 0, "left_outer": 1, "right_outer": 2, "full_outer": 3, "cross": 4}
@@ -589,14 +591,13 @@ class GpuTable:
 
     def filter(self, expr: Expr) -> "GpuTable":
         if type(expr) is not Col and needs_list_lowering(expr):
-            if isinstance(expr, Range):  # a list is no predicate
-                raise _lib.NotImplementedException(
-                    "Range is a whole withColumns column or the argument of Explode / Size / Index / InList")
+            if isinstance(expr, _LIST_SOURCES):  # a list is no predicate
+                raise _lib.NotImplementedException(_MISPLACED.format(type(expr).__name__))
             e, temps = self._lower_lists(expr)
-            if temps:  # Range operands: temporary list columns, dropped again
+            if temps:  # Range / Labels / Keys operands: temporary list columns, dropped again
                 t = self
-                for tmp, r in temps:
-                    t = t.withRangeColumn(r.start, r.end, r.step, tmp)
+                for tmp, src in temps:
+                    t = t._with_list_source(src, tmp)
                 return t._filter(e).drop(*[tmp for tmp, _ in temps])
             expr = e
         return self._filter(expr)
@@ -730,16 +731,37 @@ class GpuTable:
         _lib.call("capsmi_with_range_column", self._h, *args, name.encode(), ctypes.byref(out))
         return self._wrap(out)
 
+    def withMaskListColumn(self, mode: int, cols: Sequence[str], names: Sequence[str], name: str) -> "GpuTable":
+        """This table plus the String list column `name`: per row the names[i], in the order given, whose column
+        cols[i] passes -- non-null and TRUE (mode expr.MASK_TRUE, labels()) or non-null (expr.MASK_NOT_NULL,
+        keys()); include/capsmi.h capsmi_with_mask_list_column.  The names go through the session dictionary."""
+        if len(cols) != len(names):
+            raise _lib.IllegalArgumentException(f"{len(cols)} columns for {len(names)} names")
+        self.session.dictionary.extend(names)
+        codes = (ctypes.c_int64 * max(1, len(names)))(*[self.session.encode_str(x) for x in names])
+        out = ctypes.c_void_p()
+        _lib.call("capsmi_with_mask_list_column", self._h, mode, len(cols), _lib.strs(list(cols)), codes, name.encode(),
+                  ctypes.byref(out))
+        return self._wrap(out)
+
+    def _with_list_source(self, src: Expr, name: str) -> "GpuTable":
+        """Column `name` = the list a Range / Labels / Keys stands for (one plan node each)."""
+        if isinstance(src, Range):
+            return self.withRangeColumn(src.start, src.end, src.step, name)
+        return self.withMaskListColumn(*mask_list_args(src), name)
+
     def _lower_lists(self, e: Expr):
         """The list expressions the library does not take as they are, rewritten: InList over a ListLit or a
-        list Param is the plain In; Size(ListLit) is a literal; a Range under Explode / Size / Index / InList
-        becomes a reference to a temporary list column.  Returns (expression, [(temporary name, Range)])."""
+        list Param is the plain In; Size(ListLit) is a literal; a Range, Labels or Keys under Explode / Size /
+        Index / InList becomes a reference to a temporary list column.  Returns (expression, [(temporary name,
+        the Range / Labels / Keys)])."""
         temps = []
 
         def as_list(a: Expr) -> Expr:
-            if isinstance(a, Range):
-                check_range(a)
-                tmp = f"__range_{next(_TMP_IDS)}"
+            if isinstance(a, _LIST_SOURCES):
+                if isinstance(a, Range):
+                    check_range(a)
+                tmp = f"__list_{next(_TMP_IDS)}"
                 temps.append((tmp, a))
                 return Col(tmp)
             return go(a)
@@ -750,9 +772,8 @@ class GpuTable:
                     raise _lib.NotImplementedException("Range nested in a Range operand")
 
         def go(x):
-            if isinstance(x, Range):
-                raise _lib.NotImplementedException(
-                    "Range is a whole withColumns column or the argument of Explode / Size / Index / InList")
+            if isinstance(x, _LIST_SOURCES):
+                raise _lib.NotImplementedException(_MISPLACED.format(type(x).__name__))
             if isinstance(x, Index) and not needs_list_lowering(x) and not isinstance(x.list, (ListLit, Lit)):
                 return x
             if isinstance(x, InList):
@@ -791,26 +812,27 @@ class GpuTable:
                 kw[k] = go(v) if isinstance(v, Expr) else v
             return type(x)(**kw)
 
-        if isinstance(e, Range):  # the whole column
-            check_range(e)
+        if isinstance(e, _LIST_SOURCES):  # the whole column
+            if isinstance(e, Range):
+                check_range(e)
             return e, temps
         return go(e), temps
 
     def _with_list_columns(self, columns) -> "GpuTable":
-        """withColumns with Range / Size / Index / InList among the expressions (see _lower_lists).  A column
-        that is a Range splits the call, as an Explode does: the columns before it are evaluated first, the
-        ones after it see it."""
+        """withColumns with Range / Labels / Keys / Size / Index / InList among the expressions (see
+        _lower_lists).  A column that is a Range, Labels or Keys splits the call, as an Explode does: the columns
+        before it are evaluated first, the ones after it see it."""
         t, drop, batch = self, [], []
         for e, name in columns:
             e, temps = t._lower_lists(e)
-            if temps or isinstance(e, (Range, Explode)):
+            if temps or isinstance(e, _LIST_SOURCES + (Explode,)):
                 if batch:
                     t, batch = t._with_columns(batch), []
-                for tmp, r in temps:
-                    t = t.withRangeColumn(r.start, r.end, r.step, tmp)
+                for tmp, src in temps:
+                    t = t._with_list_source(src, tmp)
                     drop.append(tmp)
-            if isinstance(e, Range):
-                t = t.withRangeColumn(e.start, e.end, e.step, name)
+            if isinstance(e, _LIST_SOURCES):
+                t = t._with_list_source(e, name)
             elif temps or isinstance(e, Explode):
                 t = t._with_columns(((e, name),))
             else:

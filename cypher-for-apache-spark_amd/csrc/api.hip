@@ -1164,6 +1164,46 @@ capsmi_status eager_with_range_column(capsmi_table* t, const std::vector<capsmi_
     API_END
 }
 
+// labels() / keys() per row as a String list column (capsmi_with_mask_list_column): k_masklist.hip reads the
+// columns where they are and builds the store
+capsmi_status eager_with_mask_list_column(capsmi_table* t, int32_t mode, const std::vector<std::string>& cols,
+                                          const std::vector<int64_t>& codes, const char* name, capsmi_table** out) {
+    API_BEGIN
+    need(t, "table");
+    need(out, "out");
+    need(name, "column name");
+    REQUIRE(mode == CAPSMI_MASK_TRUE || mode == CAPSMI_MASK_NOT_NULL, CAPSMI_ERR_ILLEGAL_ARGUMENT, "mask list: mode");
+    REQUIRE(cols.size() == codes.size(), CAPSMI_ERR_ILLEGAL_ARGUMENT, "mask list: one code per column");
+    REQUIRE((int)cols.size() <= kMaskListCols, CAPSMI_ERR_UNSUPPORTED,
+            "mask list: " + std::to_string(cols.size()) + " columns, at most " + std::to_string(kMaskListCols) +
+                " (one mask word per row)");
+    capsmi_session* s = t->sess;
+    use_device(s);
+    const int64_t n = t->nrows;
+    std::vector<const int64_t*> data;
+    std::vector<const uint8_t*> valid;
+    for (const std::string& cn : cols) {
+        const Column& c = t->cols[col_index(t, cn.c_str())];
+        REQUIRE(mode != CAPSMI_MASK_TRUE || c.type == CAPSMI_BOOL, CAPSMI_ERR_ILLEGAL_ARGUMENT,
+                "mask list: column '" + c.name + "' is not Boolean");
+        data.push_back(c.d());
+        valid.push_back(c.v());
+    }
+    Column c;
+    c.name = name;
+    c.type = CAPSMI_LIST_STR;
+    c.list = mask_lists(s, mode, data, valid, codes, n);
+    c.data = dev_alloc(sizeof(int64_t) * (n > 0 ? n : 1), s);
+    iota_i64(P<int64_t>(c.data), 0, n, s->stream);  // row r's list is list r of the new store
+    auto* o = new_table(s, n);
+    o->cols = t->cols;
+    const int j = o->find(c.name);
+    if (j >= 0) o->cols[j] = std::move(c);  // replaced in place, as capsmi_with_columns does
+    else o->cols.push_back(std::move(c));
+    *out = o;
+    API_END
+}
+
 capsmi_status eager_join(capsmi_table* l, capsmi_table* r, int32_t join_type, int32_t npairs,
                           const char* const* lcols, const char* const* rcols, capsmi_table** out) {
     API_BEGIN

@@ -376,6 +376,14 @@ void list_contains(capsmi_session* s, const int64_t* probe, const uint8_t* pvali
 // holds (synchronises)
 std::shared_ptr<ListStore> range_lists(capsmi_session* s, const int64_t* from, const uint8_t* fv, const int64_t* to,
                                        const uint8_t* tv, const int64_t* step, const uint8_t* sv, int64_t n, Buf& valid);
+// labels() / keys() (k_masklist.hip): a String store whose list r holds codes[i], in order, for every column i
+// (flag words data[i], validity valid[i] or null) that passes in row r -- non-null and TRUE under
+// CAPSMI_MASK_TRUE, non-null under CAPSMI_MASK_NOT_NULL, where data is not read.  At most kMaskListCols columns
+// (one mask word per row).  Throws UNSUPPORTED for more elements than the device holds (synchronises)
+constexpr int kMaskListCols = 64;
+std::shared_ptr<ListStore> mask_lists(capsmi_session* s, int32_t mode, const std::vector<const int64_t*>& data,
+                                      const std::vector<const uint8_t*>& valid, const std::vector<int64_t>& codes,
+                                      int64_t n);
 // multi-GPU (k_dist.hip): the session's collective, stream-ordered (capsmi_collective_fn)
 void collective(capsmi_session* s, int op, const void* send, void* recv, int64_t count, int dtype);
 // calls of the host collective move at most coll_chunk() elements (CAPSMI_COLL_CHUNK); collective() and
@@ -665,6 +673,9 @@ capsmi_status eager_explode_values(capsmi_table* t, int32_t elem_type, int32_t c
 capsmi_status eager_with_range_column(capsmi_table* t, const std::vector<capsmi_expr>& from,
                                       const std::vector<capsmi_expr>& to, const std::vector<capsmi_expr>& step,
                                       const char* name, capsmi_table** out);
+// the list of codes[i] for every column cols[i] of t that passes under `mode` (capsmi_with_mask_list_column)
+capsmi_status eager_with_mask_list_column(capsmi_table* t, int32_t mode, const std::vector<std::string>& cols,
+                                          const std::vector<int64_t>& codes, const char* name, capsmi_table** out);
 
 // CSV ingest (ingest.hip)
 capsmi_table* read_csv(capsmi_session* s, const std::vector<std::string>& paths, char delim, char comment,

@@ -37,7 +37,7 @@ struct AggSpec {
 
 struct PlanNode {
     enum Kind { SELECT, DROP, RENAME, FILTER, WITH_COLUMNS, JOIN, UNION, DISTINCT, DISTINCT_ON, GROUP, ORDER, SKIP, LIMIT,
-                EXPLODE, RANGE };
+                EXPLODE, RANGE, MASK_LIST };
     Kind kind = SELECT;
     std::vector<capsmi_table*> in;            // retained inputs
     std::vector<std::string> a, b;            // column names (see builders)
@@ -50,6 +50,8 @@ struct PlanNode {
     // `n` values `vals` of element type `jt`
     std::vector<capsmi_value> vals;
     // RANGE: a[0] the list column; progs[0..2] the from / to / step programs (step empty: the literal 1)
+    // MASK_LIST: a[0] the list column; b the mask's columns with their names' `codes`; jt the CAPSMI_MASK_* mode
+    std::vector<int64_t> codes;
     ~PlanNode() {
         for (capsmi_table* t : in) capsmi_table_release(t);
     }
@@ -181,6 +183,7 @@ capsmi_table* exec_node(const PlanNode& p) {
             else check(eager_explode(x, p.a[0].c_str(), p.b[0].c_str(), nullptr, &r));
             break;
         case PlanNode::RANGE: check(eager_with_range_column(x, p.progs[0], p.progs[1], p.progs[2], p.a[0].c_str(), &r)); break;
+        case PlanNode::MASK_LIST: check(eager_with_mask_list_column(x, p.jt, p.b, p.codes, p.a[0].c_str(), &r)); break;
     }
     return r;
 }
@@ -2076,6 +2079,106 @@ Names all_names(const capsmi_table* t) {
     return v;
 }
 
+// The input `x` of a MASK_LIST node when it is a pattern and `need` holds label or property columns of its
+// nodes (labels(b) above MATCH (a)-[r]->(b)).  The fused routes carry relationship columns, endpoint ids and
+// constants, not node columns, so the pattern is projected on the rest of `need` plus the ids of the nodes in
+// question, that projection takes whatever fused route it matches, and the node columns are joined back by id
+// from the members of the node scans the pattern names (a base column or the member's constant).  *out then
+// holds `need` and helper columns, in any row order.  false: no route matched and nothing was run.
+bool expand_with_node_columns(capsmi_table* x, const Names& need, const Parents& par, capsmi_table** out) {
+    capsmi_session* s = x->sess;
+    if (!x->lazy() || !s->fused) return false;
+    auto shared = par.find(x);
+    if (shared != par.end() && shared->second > 1) return false;  // a shared sub-plan materialises once, in place
+    std::vector<Path> B;
+    if (!as_paths(x, B) || B.size() != 1 || B[0].cols.size() != x->cols.size()) return false;
+    const Path& P = B[0];
+    for (const Scan& sc : P.inst)
+        for (const Member& m : sc.m)
+            if (m.base->shard) return false;  // a distributed graph: the generic plan and its exchanges
+    Names proj;
+    std::map<int, std::vector<int>> fetch;  // node scan instance -> the columns of x to join back
+    for (const std::string& n : need) {
+        const int i = find_col(x, n);
+        if (i < 0) return false;
+        const Role& r = P.cols[i];
+        if (r.k == RK_NODE && P.inst[r.inst].role[r.scol] != ROLE_ID) fetch[r.inst].push_back(i);
+        else add(proj, n);
+    }
+    if (fetch.empty()) return false;
+    std::map<int, std::string> id_of;
+    for (const auto& f : fetch) {
+        for (size_t j = 0; j < P.cols.size() && !id_of.count(f.first); ++j) {
+            const Role& r = P.cols[j];
+            if (r.k == RK_NODE && r.inst == f.first && P.inst[r.inst].role[r.scol] == ROLE_ID) id_of[f.first] = x->cols[j].name;
+        }
+        if (!id_of.count(f.first)) return false;
+        add(proj, id_of[f.first]);
+    }
+    Res acc;
+    {
+        capsmi_table* sel = nullptr;
+        auto pc = cstrs(proj);
+        check(capsmi_select(x, (int32_t)pc.size(), pc.data(), &sel));
+        Res selr = owned(sel);
+        capsmi_table* fr = nullptr;
+        if (!try_fused_shapes(sel, &fr)) return false;
+        acc = owned(fr);
+        REQUIRE(fr->cols.size() == sel->cols.size(), CAPSMI_ERR_INTERNAL, "fused result schema differs from the plan's");
+        for (size_t i = 0; i < fr->cols.size(); ++i) fr->cols[i].name = sel->cols[i].name;
+    }
+    int q = 0;
+    for (const auto& f : fetch) {
+        const std::string key = "__node_id" + std::to_string(q++);
+        Names names{key};
+        for (int c : f.second) names.push_back(x->cols[c].name);
+        Res nodes;
+        for (const Member& m : P.inst[f.first].m) {
+            std::vector<capsmi_expr> progs(names.size());
+            progs[0].op = CAPSMI_X_COL;
+            progs[0].arg = m.base->entity->id;
+            for (size_t k = 0; k < f.second.size(); ++k) {
+                const int sc = P.cols[f.second[k]].scol;
+                if (m.src[sc] >= 0) {
+                    progs[k + 1].op = CAPSMI_X_COL;
+                    progs[k + 1].arg = m.src[sc];
+                } else {
+                    progs[k + 1] = m.cst[sc];  // the member's constant: a label flag, a property it lacks
+                }
+            }
+            std::vector<capsmi_expr_column> cols(names.size());
+            for (size_t k = 0; k < names.size(); ++k) {
+                cols[k].name = names[k].c_str();
+                cols[k].nnodes = 1;
+                cols[k].prog = &progs[k];
+            }
+            capsmi_table* w = nullptr;
+            check(eager_with_columns(m.base, (int32_t)cols.size(), cols.data(), &w));
+            Res wr = owned(w);
+            capsmi_table* part = nullptr;
+            auto nc = cstrs(names);
+            check(eager_select(w, (int32_t)nc.size(), nc.data(), &part));
+            Res pr = owned(part);
+            if (!nodes.t) {
+                nodes = std::move(pr);
+            } else {
+                capsmi_table* u = nullptr;
+                check(eager_union_all(nodes.t, part, &u));
+                nodes = owned(u);
+            }
+        }
+        REQUIRE(nodes.t != nullptr, CAPSMI_ERR_INTERNAL, "node scan without members");
+        const char* lk[1] = {id_of[f.first].c_str()};
+        const char* rk[1] = {key.c_str()};
+        capsmi_table* j = nullptr;
+        check(eager_join(acc.t, nodes.t, CAPSMI_JOIN_INNER, 1, lk, rk, &j));
+        acc = owned(j);
+    }
+    *out = acc.t;
+    acc.t = nullptr;
+    return true;
+}
+
 Res exec(capsmi_table* t, const Names& need, std::vector<Pred> preds, const Parents& par) {
     if (t->lazy()) {
         auto it = par.find(t);
@@ -2237,6 +2340,30 @@ Res exec(capsmi_table* t, const Names& need, std::vector<Pred> preds, const Pare
             r.reset();
             return finish(owned(o), need, stay);
         }
+        case PlanNode::MASK_LIST: {
+            // row-local, as RANGE: a conjunct that reads the new column stays above, the others run on the input
+            // rows; the input keeps the columns somebody above reads plus the mask's
+            const std::string& name = p.a[0];
+            std::vector<Pred> down, stay;
+            for (Pred& pr : preds) (has(pr.names, name) ? stay : down).push_back(std::move(pr));
+            Names out = need;
+            for (const Pred& pr : stay)
+                for (const std::string& n : pr.names) add(out, n);
+            Names nin;
+            for (const std::string& n : out)
+                if (n != name) add(nin, n);
+            for (const std::string& n : p.b) add(nin, n);
+            if (nin.empty() && !x->cols.empty()) add(nin, x->cols[0].name);  // the row count travels with a column
+            Res r;
+            capsmi_table* routed = nullptr;
+            if (down.empty() && expand_with_node_columns(x, nin, par, &routed)) r = owned(routed);
+            else r = exec(x, nin, std::move(down), par);
+            capsmi_table* o = nullptr;
+            check(eager_with_mask_list_column(r.t, p.jt, p.b, p.codes, name.c_str(), &o));
+            o->partitioned = r.t->partitioned;  // no exchange
+            r.reset();
+            return finish(owned(o), need, stay);
+        }
         default: {  // union, distinct, grouping, ordering, skip / limit: conjuncts stay above
             std::vector<Names> nin(p.in.size());
             for (size_t i = 0; i < p.in.size(); ++i) nin[i] = all_names(p.in[i]);
@@ -2261,6 +2388,7 @@ Res exec(capsmi_table* t, const Names& need, std::vector<Pred> preds, const Pare
             run.aggs = p.aggs;
             run.jt = p.jt;
             run.n = p.n;
+            run.codes = p.codes;
             bool part = false;
             std::vector<Res> ins;
             for (size_t i = 0; i < p.in.size(); ++i) {
@@ -2516,6 +2644,32 @@ capsmi_status capsmi_with_range_column(capsmi_table* t, int32_t from_nnodes, con
             p->progs.push_back(std::move(prog));
         }
         return lazy_table(t->sess, p, explode_schema(t, schema_col(name, CAPSMI_LIST_I64, true)));
+    });
+}
+
+capsmi_status capsmi_with_mask_list_column(capsmi_table* t, int32_t mode, int32_t ncols, const char* const* cols,
+                                           const int64_t* elem_codes, const char* name, capsmi_table** out) {
+    return build(t, out, [&] {
+        need(name, "column name");
+        REQUIRE(mode == CAPSMI_MASK_TRUE || mode == CAPSMI_MASK_NOT_NULL, CAPSMI_ERR_ILLEGAL_ARGUMENT, "mask list: mode");
+        REQUIRE(ncols >= 0 && (ncols == 0 || (cols && elem_codes)), CAPSMI_ERR_ILLEGAL_ARGUMENT,
+                "mask list: null columns or codes");
+        REQUIRE(ncols <= kMaskListCols, CAPSMI_ERR_UNSUPPORTED,
+                "mask list: " + std::to_string(ncols) + " columns, at most " + std::to_string(kMaskListCols) +
+                    " (one mask word per row)");
+        auto p = std::make_shared<PlanNode>();
+        p->kind = PlanNode::MASK_LIST;
+        hold(*p, t);
+        p->a = {name};
+        p->jt = mode;
+        for (int i = 0; i < ncols; ++i) {
+            const Column& c = t->cols[col_of(t, cols[i])];
+            REQUIRE(mode != CAPSMI_MASK_TRUE || c.type == CAPSMI_BOOL, CAPSMI_ERR_ILLEGAL_ARGUMENT,
+                    "mask list: column '" + c.name + "' is not Boolean");
+            p->b.push_back(c.name);
+            p->codes.push_back(elem_codes[i]);
+        }
+        return lazy_table(t->sess, p, explode_schema(t, schema_col(name, CAPSMI_LIST_STR, false)));
     });
 }
 

@@ -69,7 +69,8 @@ enum {
  * (CAPSMI_LIST_I64 ... CAPSMI_LIST_STR); rows are read with capsmi_table_export_list, opened again into
  * rows by capsmi_explode, and ingested from the host by capsmi_table_add_list_column.  List columns
  * travel through select / drop / rename / filter / join payloads / union all / order-by payloads /
- * skip / limit, and are made from Long operands by capsmi_with_range_column.  Inside an expression a list
+ * skip / limit, and are made from Long operands by capsmi_with_range_column and from flag or property
+ * columns by capsmi_with_mask_list_column.  Inside an expression a list
  * column is an operand of CAPSMI_X_SIZE, CAPSMI_X_INDEX and CAPSMI_X_IN_LIST only: CAPSMI_X_COL of a list
  * column pushes a list value (the row's list, typed CAPSMI_LIST + elem, or NULL for a null row), and a list
  * value that reaches any other opcode is CAPSMI_ERR_NOT_IMPLEMENTED, as is a list column used as a join,
@@ -237,8 +238,11 @@ capsmi_status capsmi_session_kernel_time(capsmi_session* s, const char* name, in
  * "radix_join_write"; UNWIND's "explode": 8 B x (n starts + n row words read, m values read, m items + m source
  * rows written) for n input rows and m output rows, its payload gathers timed apart as "explode_gather" (24 B per
  * output row and gathered column) and its
- * lengths / scan / compaction as "explode_starts"; "explode_values": 16 B per output row); 0 otherwise; then the
- * counter resets. */
+ * lengths / scan / compaction as "explode_starts"; "explode_values": 16 B per output row;
+ * capsmi_with_mask_list_column's "mask_list_len": per row 9 B per nullable and 8 B per non-nullable column read
+ * under CAPSMI_MASK_TRUE, 1 B per nullable column under CAPSMI_MASK_NOT_NULL, 17 B written, and "mask_list":
+ * 8 B x (n starts + n masks read, M elements written), its scan and compaction timed as "mask_list_starts");
+ * 0 otherwise; then the counter resets. */
 capsmi_status capsmi_session_kernel_bytes(capsmi_session* s, const char* name, double* bytes);
 /* fused-path routing of lazy plans: enable / disable (default on; off = operator by operator, for
  * A/B checks), and the number of plans routed to fused entry point `name` ("expand", "expand_count",
@@ -421,6 +425,29 @@ capsmi_status capsmi_explode_values(capsmi_table* t, int32_t elem_type, int32_t 
 capsmi_status capsmi_with_range_column(capsmi_table* t, int32_t from_nnodes, const capsmi_expr* from_prog,
                                        int32_t to_nnodes, const capsmi_expr* to_prog, int32_t step_nnodes,
                                        const capsmi_expr* step_prog, const char* name, capsmi_table** out);
+
+/* labels(n) and keys(n) as a list column (Labels / Keys, SparkSQLExprMapper.scala:192-208; the reference's
+ * get_node_labels / get_property_keys UDFs over array(flag or property columns), CAPSFunctions.scala:73-91).
+ * The result is `t` plus a non-nullable CAPSMI_LIST_STR column `name` under the capsmi_with_columns
+ * replace-or-append rule (`name` may equal one of `cols`).  Row r's list holds elem_codes[i] (dictionary codes)
+ * for every i, in the order given, whose column cols[i] passes in row r:
+ *   CAPSMI_MASK_TRUE      every column is CAPSMI_BOOL (anything else: CAPSMI_ERR_ILLEGAL_ARGUMENT when the node
+ *                         is built); a column passes where it is non-null and TRUE.  A NULL flag is not set, and
+ *                         a TRUE word stored under a null row is not seen.
+ *   CAPSMI_MASK_NOT_NULL  columns of any type, list columns included; a column passes where the row is
+ *                         non-null.  Only validity is read: a non-nullable column always passes.
+ * The list is never NULL: filterWithMask's `case (label, true)` and filterNotNull's `value != null`
+ * (CAPSFunctions.scala:73-91) skip the null elements of the array the UDF receives, so a null entity (an
+ * OPTIONAL MATCH miss) yields [].  This is a reading of the reference's source, not an observation of a run.
+ * The library does not sort: the caller passes the names in the reference's order (sortBy(_._1) for labels,
+ * :198; sortBy(_.key.name) for keys, :205).  ncols == 0 is legal (every row gets []; the reference's array()
+ * for a graph without labels); ncols > 64 is CAPSMI_ERR_UNSUPPORTED when the node is built (one 64-bit mask
+ * word per row).  The element count is checked as capsmi_with_range_column checks it, before anything sized by
+ * it is allocated (it is at most 64 per row, so only memory pressure can trigger it).
+ * Lazy and row-local: no collective is called and a partitioned table stays partitioned. */
+enum { CAPSMI_MASK_TRUE = 0, CAPSMI_MASK_NOT_NULL = 1 };
+capsmi_status capsmi_with_mask_list_column(capsmi_table* t, int32_t mode, int32_t ncols, const char* const* cols,
+                                           const int64_t* elem_codes, const char* name, capsmi_table** out);
 
 /* ---- graph fast path ------------------------------------------------------------------
  * The relational planner lowers Expand into `join(relScan, source = start)` then

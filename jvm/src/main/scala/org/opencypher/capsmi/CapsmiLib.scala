@@ -69,6 +69,10 @@ object Capsmi {
   final val X_INDEX = 27    // [list, i]: element i (0-based), NULL outside the list
   final val X_IN_LIST = 28  // [x, list]: x IN list-column, 3VL
 
+  // capsmi_with_mask_list_column: which columns of a row pass
+  final val MASK_TRUE = 0     // labels(): the Boolean flag is non-null and TRUE
+  final val MASK_NOT_NULL = 1 // keys(): the value is non-null
+
   // join types (JoinType of RelationalPlanner; SparkTable.scala:205-229)
   final val JOIN_INNER = 0
   final val JOIN_LEFT_OUTER = 1
@@ -248,6 +252,9 @@ trait CapsmiLib extends Library {
                                stepNnodes: Int, stepProg: CapsmiExpr, name: String, out: PointerByReference): Int
   def capsmi_explode_values(t: Pointer, elemType: Int, count: Int, values: CapsmiValue, itemName: String,
                             out: PointerByReference): Int
+  // labels(n) / keys(n) per row as a String list column: elemCodes(i) for every cols(i) that passes under `mode`
+  def capsmi_with_mask_list_column(t: Pointer, mode: Int, ncols: Int, cols: Array[String], elemCodes: Array[Long],
+                                   name: String, out: PointerByReference): Int
   // list-property ingest from host CSR arrays (CAPSTable's array columns)
   def capsmi_table_add_list_column(t: Pointer, name: String, elemType: Int, hostOffsets: Pointer, hostValues: Pointer,
                                    hostValid: Pointer, out: PointerByReference): Int

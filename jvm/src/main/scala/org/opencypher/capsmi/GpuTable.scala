@@ -214,48 +214,51 @@ final class GpuTable private (val handle: Pointer)(implicit val session: GpuSess
       case _: Explode => true
       case other => other.children.exists(hasExplode)
     }
-    // Range (SparkSQLExprMapper.scala:243-245): a column that is a Range goes to capsmi_with_range_column; a Range
-    // that is the argument of a top-level Explode, of Size, the container of ContainerIndex or the right side of In
-    // is first added as a temporary list column under a name the table does not have, which is dropped
-    // afterwards.  Either splits the call as an Explode does.  A Range anywhere else, a Range inside a Range's
-    // operands included, is NotImplementedException.
-    def hasRange(e: Expr): Boolean = e match {
-      case _: Range => true
-      case other => other.children.exists(hasRange)
+    // The list sources -- Range (SparkSQLExprMapper.scala:243-245), Labels (:192-201) and Keys (:203-208) -- are
+    // plan nodes of their own: a column that is one goes to capsmi_with_range_column / capsmi_with_mask_list_column;
+    // one that is the argument of a top-level Explode, of Size, the container of ContainerIndex or the right side
+    // of In is first added as a temporary list column under a name the table does not have, which is dropped
+    // afterwards.  Either splits the call as an Explode does.  A list source anywhere else, a Range inside a
+    // Range's operands included, is NotImplementedException.
+    def isListSource(e: Expr): Boolean = e match {
+      case _: Range | _: Labels | _: Keys => true
+      case _ => false
     }
-    def plain(r: Range): Range = {
-      if ((Seq(r.from, r.to) ++ r.o).exists(x => hasRange(x) || hasExplode(x)))
+    def hasListSource(e: Expr): Boolean = isListSource(e) || e.children.exists(hasListSource)
+    def plain(src: Expr): Expr = src match {
+      case r: Range if (Seq(r.from, r.to) ++ r.o).exists(x => hasListSource(x) || hasExplode(x)) =>
         throw NotImplementedException("Range nested in a Range operand")
-      r
+      case other => other
     }
-    def misplaced(): Nothing = throw NotImplementedException(
-      "Range on the device path: a whole withColumns column or the argument of Explode / Size / ContainerIndex / In")
-    // the Ranges of `e` that sit in an allowed place
-    def lifted(e: Expr): Seq[Range] = e match {
-      case _: Range => misplaced()
+    def misplaced(src: Expr): Nothing = throw NotImplementedException(
+      s"${src.getClass.getSimpleName} on the device path: a whole withColumns column or the argument of Explode / " +
+        "Size / ContainerIndex / In")
+    // the list sources of `e` that sit in an allowed place
+    def lifted(e: Expr): Seq[Expr] = e match {
+      case src if isListSource(src) => misplaced(src)
       case _: Explode => throw NotImplementedException("Explode nested in another expression")
-      case Size(r: Range) => Seq(plain(r))
-      case ContainerIndex(r: Range, index) => plain(r) +: lifted(index)
-      case In(lhs, r: Range) => lifted(lhs) :+ plain(r)
+      case Size(src) if isListSource(src) => Seq(plain(src))
+      case ContainerIndex(src, index) if isListSource(src) => plain(src) +: lifted(index)
+      case In(lhs, src) if isListSource(src) => lifted(lhs) :+ plain(src)
       case other => other.children.toSeq.flatMap(lifted)
     }
     def freshNames(taken: Seq[String]): Iterator[String] =
-      Iterator.from(0).map(i => s"__capsmi_range_$i").filterNot(taken.contains)
-    val rangeAt = columns.indexWhere { case (e, _) => hasRange(e) }
-    if (rangeAt >= 0) {
-      val (before, rest) = columns.splitAt(rangeAt)
+      Iterator.from(0).map(i => s"__capsmi_list_$i").filterNot(taken.contains)
+    val sourceAt = columns.indexWhere { case (e, _) => hasListSource(e) }
+    if (sourceAt >= 0) {
+      val (before, rest) = columns.splitAt(sourceAt)
       val base = if (before.isEmpty) this else withColumns(before: _*)
       val (e, name) = rest.head
       val names = freshNames(base.physicalColumns ++ columns.map(_._2))
       val added = e match {
-        case r: Range => base.withRangeColumn(plain(r), name)
-        case Explode(r: Range) =>
+        case src if isListSource(src) => base.withListSource(plain(src), name)
+        case Explode(src) if isListSource(src) =>
           val tmp = names.next()
-          val listed = base.withRangeColumn(plain(r), tmp)
+          val listed = base.withListSource(plain(src), tmp)
           listed.wrap(I.capsmi_explode(listed.handle, tmp, name, _)).drop(tmp)
         case other =>
-          val temps = lifted(other).distinct.map(r => r -> names.next())
-          val listed = temps.foldLeft(base) { case (t, (r, tmp)) => t.withRangeColumn(r, tmp) }
+          val temps = lifted(other).distinct.map(src => src -> names.next())
+          val listed = temps.foldLeft(base) { case (t, (src, tmp)) => t.withListSource(src, tmp) }
           val prog = ExprCompiler(listed, header, parameters, temps.toMap[Expr, String]).compile(other)
           listed.wrap(I.capsmi_with_columns(listed.handle, 1, CapsmiLib.exprColumns(Seq(name -> prog)), _))
             .drop(temps.map(_._2): _*)
@@ -285,6 +288,29 @@ final class GpuTable private (val handle: Pointer)(implicit val session: GpuSess
     wrap(I.capsmi_with_range_column(handle, from.size, CapsmiLib.exprs(from), to.size, CapsmiLib.exprs(to),
       step.fold(0)(_.size), step.map(CapsmiLib.exprs).orNull, name, _))
   }
+
+  /** labels(n) / keys(n) per row as the String list column `name` (capsmi_with_mask_list_column; the reference's
+    * get_node_labels / get_property_keys UDFs, CAPSFunctions.scala:73-91): the names, sorted as
+    * SparkSQLExprMapper.scala:198 / :205 sort them, whose flag column is TRUE / whose property column is not null.
+    * Never NULL: a null entity gives the empty list (read from filterWithMask / filterNotNull, not observed). */
+  private def withMaskListColumn(mode: Int, named: Seq[(String, String)], name: String): GpuTable = {
+    // a header column this table does not hold is a null column: it never passes
+    val (names, cols) = named.filter { case (_, c) => physicalColumns.contains(c) }.sortBy(_._1).unzip
+    val codes = names.map(session.dictionary.encode).toArray
+    wrap(I.capsmi_with_mask_list_column(handle, mode, cols.size, cols.toArray, codes, name, _))
+  }
+
+  /** The list column `name` a Range / Labels / Keys stands for. */
+  private def withListSource(src: Expr, name: String)(implicit header: RecordHeader, parameters: CypherMap): GpuTable =
+    src match {
+      case r: Range => withRangeColumn(r, name)
+      case Labels(e) =>
+        withMaskListColumn(Capsmi.MASK_TRUE, header.labelsFor(e.owner.get).toSeq.map(l => l.label.name -> header.column(l)), name)
+      case Keys(e) =>
+        withMaskListColumn(Capsmi.MASK_NOT_NULL, header.propertiesFor(e.owner.get).toSeq.map(p => p.key.name -> header.column(p)),
+          name)
+      case other => throw NotImplementedException(s"list source $other on the device path")
+    }
 
   /** functions.explode (SparkSQLExprMapper.scala:237-241) of a list column (capsmi_explode), or of a ListLit /
     * list parameter (functions.array of the literals, :86-89, 111-112; capsmi_explode_values). */
@@ -349,8 +375,10 @@ final class GpuTable private (val handle: Pointer)(implicit val session: GpuSess
   * table (CAPSMI_X_PARAM, :86-92), predicates and arithmetic, and the list expressions Size (:124-130),
   * ContainerIndex (:300-307) and In with a list-typed column on the right (array_contains, :138-145) as
   * CAPSMI_X_SIZE / CAPSMI_X_INDEX / CAPSMI_X_IN_LIST.  `lists` names the temporary list columns that stand for
-  * Range operands (GpuTable.withColumns).  Shapes the device path does not evaluate (string matching, other
-  * functions, maps, size() of a string) raise NotImplementedException.
+  * Range / Labels / Keys operands (GpuTable.withColumns).  The entity functions (:192-227): Type of a variable is
+  * the CASE over the header's type flags (get_rel_type's headOption.orNull), StartNodeFunction / EndNodeFunction
+  * are column lookups; Labels and Keys are list columns built by GpuTable.  Shapes the device path does not
+  * evaluate (string matching, other functions, maps, size() of a string) raise NotImplementedException.
   */
 final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters: CypherMap,
                               lists: Map[Expr, String] = Map.empty) {
@@ -383,7 +411,8 @@ final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters:
     out += (if (i >= 0) (Capsmi.X_COL, i, 0, 0L) else nullOf(e.cypherType))
   }
 
-  /** Whether `e` is a list the library holds as a column: a temporary Range column or a list-typed header column. */
+  /** Whether `e` is a list the library holds as a column: a temporary Range / Labels / Keys column or a list-typed
+    * header column. */
   private def listColumn(e: Expr): Boolean =
     lists.contains(e) || (e.cypherType.material.isInstanceOf[CTList] && header.contains(e) && cols.contains(header.column(e)))
 
@@ -409,6 +438,15 @@ final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters:
       out += ((Capsmi.X_PARAM, params.getOrElseUpdate(p.name, params.size), 0, 0L))
     case _: Var | _: Param | _: Property | _: HasLabel | _: HasType | _: StartNode | _: EndNode => column(e, out)
     case AliasExpr(inner, _) => go(inner, out)
+    case Type(v: Var) => // get_rel_type (CAPSFunctions.scala:68-71): the first TRUE type flag's name, else NULL
+      val types = header.typesFor(v).toSeq
+      types.foreach { t => column(t, out); out += lit(Capsmi.STR, table.session.dictionary.encode(t.relType.name)) }
+      out += nullOf(CTString)
+      if (types.nonEmpty) out += ((Capsmi.X_CASE, types.size, 0, 0L))
+    case Type(inner) => // SparkSQLExprMapper.scala:217-218
+      throw NotImplementedException(s"Inner expression $inner of $e is not yet supported (only variables)")
+    case StartNodeFunction(x) => column(header.startNodeFor(x.owner.get), out)
+    case EndNodeFunction(x) => column(header.endNodeFor(x.owner.get), out)
     case IntegerLit(v) => out += lit(Capsmi.I64, v)
     case StringLit(v) => out += lit(Capsmi.STR, table.session.dictionary.encode(v))
     case b: BoolLit => out += lit(Capsmi.BOOL, if (b.v) 1L else 0L)
