@@ -288,20 +288,32 @@ def test_lazy_schema_errors_at_call(session):
     assert u.size == 5
 
 
-@pytest.mark.parametrize("scale,kind", [(12, "all"), (14, "all"), (12, "person"), (16, "person"), (20, "all")])
+@pytest.mark.parametrize("scale,kind", [(12, "all"), (14, "all"), (12, "person"), (16, "person"), (20, "all"),
+                                        (12, "ages")])
 def test_c3_grouped_routed(session, scale, kind):
     """C3's grouped form (RETURN id(a), count(DISTINCT c), the parity variant at s <= 14) and
     the grouped count(*), routed to the grouped 2-hop kernels (csrc/k_grouped.hip), against per-a
-    enumeration (oracle/rmat.c orc_two_hop_enumerate), and the same plan operator by operator."""
+    enumeration (oracle/rmat.c orc_two_hop_enumerate), and the same plan operator by operator.  "ages":
+    three different predicates, a an adult Person (18 <= age < 65), b any Person, c a Person under 40."""
     from oracle import cpu
-    sg = _graph(session, scale, kind=kind)
+    sg = _graph(session, scale, kind="person" if kind == "ages" else kind)
     q = {"clauses": [{"match": "(a:Person)-[:FRIEND_OF]->(b:Person)-[:FRIEND_OF]->(c:Person)"}],
          "return": {"items": [["a", ["id", "a"]], ["dc", ["count_distinct", ["id", "c"]]], ["n", ["count*"]]]}}
+    if kind == "ages":
+        q["clauses"][0]["where"] = ["and", ["and", [">=", ["prop", "a", "age"], ["lit", 18]],
+                                            ["<", ["prop", "a", "age"], ["lit", 65]]],
+                                    ["<", ["prop", "c", "age"], ["lit", 40]]]
     got = _routed(session, "two_hop_grouped", lambda: _run(session, sg, q))
     n = 1 << scale
     src, dst = cpu.rmat_edges(scale, 0, 16 << scale)
     mask = np.ones(n, np.uint8) if kind == "all" else cpu.person_mask(n).astype(np.uint8)
-    _, _, grows, gdist = cpu.two_hop_enumerate(n, src, dst, mask, mask, mask, grouped=True)
+    if kind == "ages":
+        age = cpu.ages(np.arange(n))
+        a_ok, c_ok = (mask & (age >= 18) & (age < 65)).astype(np.uint8), (mask & (age < 40)).astype(np.uint8)
+        assert 0 < c_ok.sum() < a_ok.sum() < mask.sum()
+    else:
+        a_ok = c_ok = mask
+    _, _, grows, gdist = cpu.two_hop_enumerate(n, src, dst, a_ok, mask, c_ok, grouped=True)
     want = [{"a": int(a), "dc": int(gdist[a]), "n": int(grows[a])} for a in np.nonzero(grows)[0]]
     assert same_rows(got, want)
     if scale == 12:
