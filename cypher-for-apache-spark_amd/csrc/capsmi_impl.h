@@ -143,6 +143,9 @@ struct Config {
     int pairs = 0;                // CAPSMI_PAIRS = packed | uint2 (1 | 2): force the cached layout's pair form
     int hop2 = 0;                 // CAPSMI_HOP2 = pool | cells (1 | 2): force the cold 2-hop's form for a full a_ok, both hops
                                   //   over the pass-1 pool or pass 2 + the cell hops (auto: the pool up to 2^26 ids, k_part.hip)
+    bool pool_split = true;       // CAPSMI_POOL = split | pairs: the format of the pass-1 pool that the pool hops walk --
+                                  //   target and source words in two arrays per chunk, so hop 1 reads 4 B per
+                                  //   relationship, or 8-byte pairs (every other pool is pairs)
     bool tri_sorted_build = false;  // CAPSMI_TRI_BUILD = sorted: the sort-oriented trigraph build (above 2^24 ids)
     int tri_deg_sample = 0;       // CAPSMI_TRI_DEG_SAMPLE: 1 in k relationships for the degree order (0: auto)
     bool tri_split = true;        // CAPSMI_TRI_SPLIT = 0: the combined (not direction-split) triangle walks
@@ -489,6 +492,7 @@ struct PartLayout {
 struct ChunkPart {
     PartLayout L;
     Buf pool, meta, chist, jbuf;
+    bool split = false;          // the pool's chunks are two word arrays (part_common.h: split_t / split_s), not pairs
     bool has_hist = false;       // chist holds the chunks' cell-count rows (pass 1 with want_hist, or k_chunk_hist)
     int64_t pool_chunks = 0, npool = 1, mtot = 0, g2 = 1;
     int64_t* jst = nullptr;      // nt + 1 chunk offsets per bucket in `order`

@@ -222,13 +222,17 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
 // complete line of it is stored, and the tail is held back again.  A line is then written once,
 // by one wave, instead of in two pieces by two tiles, which the L2 may write back separately.
 // The chunk contents and histograms equal k_scatter_c's up to the order within a chunk.
-constexpr int kLine = 16;  // pairs per 128-byte line
+// With SPLIT the chunk is the split pool's two word arrays (part_common.h) and a whole line is 32 pairs in each.
+constexpr int kLine = 16;       // pairs per 128-byte line
+constexpr int kLineSplit = 32;  // words per 128-byte line of the split pool's arrays
+__host__ __device__ constexpr int p1_line(bool split) { return split ? kLineSplit : kLine; }
 
-__device__ __forceinline__ uint32_t held(uint32_t o, uint32_t f) { return o == kNone ? 0u : (f & (kLine - 1)); }
+template <int LN>
+__device__ __forceinline__ uint32_t held(uint32_t o, uint32_t f) { return o == kNone ? 0u : (f & (LN - 1)); }
 
 // wave 0: retire the chunks the previous tile filled, add its runs' tails to the opened chunks'
 // histogram rows (HIST), advance the open chunks and clear the previous run lengths `cp`
-template <bool HIST>
+template <bool HIST, int LN>
 __device__ __forceinline__ void p1l_settle(const Layout& L, int hw, const uint2* stage, uint32_t* H, uint32_t* cp,
                                            const uint32_t* loc, uint32_t* ph, uint32_t* fl, const uint32_t* p1,
                                            const uint32_t* opened, uint32_t* misc, unsigned long long* cmeta,
@@ -246,7 +250,7 @@ __device__ __forceinline__ void p1l_settle(const Layout& L, int hw, const uint2*
         wave_lds_order();
         for (uint32_t k = 0; k < nop; ++k) {  // items past the old chunk's room belong to the opened one
             const int b = (int)opened[k];
-            const uint32_t h = held(ph[b], fl[b]);
+            const uint32_t h = held<LN>(ph[b], fl[b]);
             const uint32_t room = ph[b] == kNone ? 0u : (uint32_t)kCh - (fl[b] - h);
             for (uint32_t r = room + lane; r < h + cp[b]; r += 64) hist_add(H, hw, b, stage[loc[b] + r].x >> L.sbits);
         }
@@ -275,18 +279,20 @@ __device__ __forceinline__ void p1l_settle(const Layout& L, int hw, const uint2*
 // from loc / ph / fl / cn / p1.  Staged item r of slice b (r = index - loc) goes to logical position w + r of
 // the open chunk (w = its written prefix) while r < room, else to position r - room of the opened chunk;
 // positions below the landing chunk's last complete line (cut) are stored, the rest held back.
-//   x: loc | room << 16        y: w / kLine | cut(open) / kLine << 10 | cut(opened) / kLine << 20
+//   x: loc | room << 16        y: w / LN | cut(open) / LN << 10 | cut(opened) / LN << 20
 //   z: the open chunk          w: the chunk this tile's run opens
+template <int LN>
 __device__ __forceinline__ uint4 p1l_pack(uint32_t loc, uint32_t c, uint32_t o, uint32_t f, uint32_t np) {
-    const uint32_t h = held(o, f), w = f - h, room = o == kNone ? 0u : (uint32_t)kCh - w;
-    const uint32_t cut0 = min(w + h + c, (uint32_t)kCh) / kLine, cut1 = h + c > room ? (h + c - room) / kLine : 0u;
-    return make_uint4(loc | room << 16, w / kLine | cut0 << 10 | cut1 << 20, o, np);
+    const uint32_t h = held<LN>(o, f), w = f - h, room = o == kNone ? 0u : (uint32_t)kCh - w;
+    const uint32_t cut0 = min(w + h + c, (uint32_t)kCh) / LN, cut1 = h + c > room ? (h + c - room) / LN : 0u;
+    return make_uint4(loc | room << 16, w / LN | cut0 << 10 | cut1 << 20, o, np);
 }
-static_assert(kCh / kLine < 1024 && kCh < 65536, "p1l_pack fields");
+static_assert(kCh / kLine < 1024 && kCh / kLineSplit < 1024 && kCh < 65536, "p1l_pack fields");
 
 // wave 0: run starts `loc` of this tile (exclusive scan over each slice's staged sequence = held
 // items + run), where each run itself starts (base = loc + held), the chunks its runs open (p1, opened,
 // misc[0]), the store loop's per-slice words (Q) and the staged total (misc[2])
+template <int LN>
 __device__ __forceinline__ void p1l_plan(int nb, const uint32_t* cn, uint32_t* loc, const uint32_t* ph,
                                          const uint32_t* fl, uint32_t* p1, uint32_t* opened, uint32_t* misc,
                                          uint32_t* base, uint4* Q) {
@@ -295,7 +301,7 @@ __device__ __forceinline__ void p1l_plan(int nb, const uint32_t* cn, uint32_t* l
     uint32_t sum = 0, need = 0;
     for (int i = b0; i < b1; ++i) {
         const uint32_t c = cn[i];
-        sum += c + held(ph[i], fl[i]);
+        sum += c + held<LN>(ph[i], fl[i]);
         need += (c && (ph[i] == kNone || fl[i] + c > (uint32_t)kCh)) ? 1u : 0u;
     }
     const uint32_t is = wave_incl_scan(sum), in = wave_incl_scan(need);
@@ -304,15 +310,15 @@ __device__ __forceinline__ void p1l_plan(int nb, const uint32_t* cn, uint32_t* l
     for (int i = b0; i < b1; ++i) {
         const uint32_t c = cn[i], o = ph[i], f = fl[i];
         loc[i] = pre;
-        base[i] = pre + held(o, f);
+        base[i] = pre + held<LN>(o, f);
         uint32_t np = kNone;
         if (c && (o == kNone || f + c > (uint32_t)kCh)) {
             np = nf + k;
             opened[k++] = (uint32_t)i;
         }
         p1[i] = np;
-        Q[i] = p1l_pack(pre, c, o, f, np);
-        pre += c + held(o, f);
+        Q[i] = p1l_pack<LN>(pre, c, o, f, np);
+        pre += c + held<LN>(o, f);
     }
     if (lane == 63) {
         misc[0] = in;
@@ -321,20 +327,35 @@ __device__ __forceinline__ void p1l_plan(int nb, const uint32_t* cn, uint32_t* l
     wave_lds_order();
 }
 
-__host__ __device__ constexpr size_t scatter1l_lds(int nb, int ns, bool hist, int block, int tile) {
-    return sizeof(uint2) * ((size_t)tile + (size_t)nb * (2 * kLine)) +
+__host__ __device__ constexpr size_t scatter1l_lds(int nb, int ns, bool hist, int block, int tile, bool split = false) {
+    return sizeof(uint2) * ((size_t)tile + (size_t)nb * (2 * p1_line(split))) +
            sizeof(uint32_t) * ((hist ? (size_t)nb * hist_words(ns) : 0) + 12 * (size_t)nb + block / 64 + 4);
 }
 
-template <int B, int IT, int MINW, bool HIST, bool NTL = false, bool NTS = false>
+template <int B, int IT, int MINW, bool HIST, bool SPLIT = false, bool NTL = false, bool NTS = false>
 __global__ void __launch_bounds__(B, MINW) k_scatter_l(const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
                                                       int64_t m, Layout L, int swap, int64_t chunk0, size_t trash,
                                                       uint2* __restrict__ pool, unsigned long long* __restrict__ cmeta,
                                                       uint32_t* __restrict__ chist) {
     constexpr int T = B * IT;
+    constexpr int kLine = p1_line(SPLIT);  // the instantiation's line, in pairs
     static_assert(T <= kCh && kCh % kLine == 0, "a pass-1 run must span at most two chunks");
+    static_assert(!(SPLIT && HIST), "the split pool is built without the cell counts");
     extern __shared__ __attribute__((aligned(16))) unsigned long long smem[];
     const int nb = L.nt, hw = hist_words(L.ns);
+    // the pair (x, y) at position pos of chunk q
+    auto put = [&](uint32_t q, uint32_t pos, uint2 p) {
+        if (SPLIT) {
+            uint32_t* tw = reinterpret_cast<uint32_t*>(pool + (size_t)q * kCh);
+            tw[pos] = p.y | (p.x == p.y ? kLoopBit : 0u);
+            tw[kCh + pos] = p.x;
+        } else if (NTS) {
+            __builtin_nontemporal_store(*reinterpret_cast<const unsigned long long*>(&p),
+                                        reinterpret_cast<unsigned long long*>(pool + (size_t)q * kCh + pos));
+        } else {
+            pool[(size_t)q * kCh + pos] = p;
+        }
+    };
     uint2* stage = reinterpret_cast<uint2*>(smem);    // T + nb * kLine: runs behind their held items
     uint2* hold = stage + T + (size_t)nb * kLine;      // nb x kLine held items
     uint4* Q = reinterpret_cast<uint4*>(hold + (size_t)nb * kLine);  // p1l_pack, 16-byte aligned
@@ -388,8 +409,9 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_l(const int64_t* __restrict
             if ((valid >> u) & 1u) rk[u] = atomicAdd(&cn[pr[u].y >> L.tbits], 1u);
         __syncthreads();
         if (threadIdx.x < 64) {
-            if (pending) p1l_settle<HIST>(L, hw, stage, H, cnt + (par ^ 1) * nb, loc, ph, fl, p1, opened, misc, cmeta, chist);
-            p1l_plan(nb, cn, loc, ph, fl, p1, opened, misc, base, Q);
+            if (pending)
+                p1l_settle<HIST, kLine>(L, hw, stage, H, cnt + (par ^ 1) * nb, loc, ph, fl, p1, opened, misc, cmeta, chist);
+            p1l_plan<kLine>(nb, cn, loc, ph, fl, p1, opened, misc, base, Q);
         }
         __syncthreads();
         pending = true;
@@ -415,12 +437,7 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_l(const int64_t* __restrict
             if (idx >= total) {
                 break;  // idx only grows
             } else if (pos < cut) {
-                uint2* d = pool + (size_t)(first ? q.z : q.w) * kCh + pos;
-                if (NTS)
-                    __builtin_nontemporal_store(*reinterpret_cast<const unsigned long long*>(&p),
-                                                reinterpret_cast<unsigned long long*>(d));
-                else
-                    *d = p;
+                put(first ? q.z : q.w, pos, p);
             } else {
                 hold[b * kLine + (pos - cut)] = p;
             }
@@ -428,11 +445,12 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_l(const int64_t* __restrict
     }
     __syncthreads();
     if (pending && threadIdx.x < 64)
-        p1l_settle<HIST>(L, hw, stage, H, cnt + (par ^ 1) * nb, loc, ph, fl, p1, opened, misc, cmeta, chist);
+        p1l_settle<HIST, kLine>(L, hw, stage, H, cnt + (par ^ 1) * nb, loc, ph, fl, p1, opened, misc, cmeta, chist);
     __syncthreads();
     for (int x = threadIdx.x; x < nb * kLine; x += B) {  // held tails
         const int b = x / kLine, k = x % kLine;
-        if ((uint32_t)k < held(ph[b], fl[b])) pool[(size_t)ph[b] * kCh + (fl[b] - held(ph[b], fl[b])) + k] = hold[x];
+        const uint32_t h = held<kLine>(ph[b], fl[b]);
+        if ((uint32_t)k < h) put(ph[b], fl[b] - h + k, hold[x]);
     }
     for (int i = threadIdx.x; i < nb; i += B)
         if (ph[i] != kNone) cmeta[ph[i]] = chunk_meta(i, fl[i]);
@@ -449,7 +467,7 @@ constexpr int kHistBlock = 256;
 
 __global__ void __launch_bounds__(kHistBlock) k_chunk_hist(const uint2* __restrict__ pool,
                                                            const unsigned long long* __restrict__ cmeta,
-                                                           int64_t nchunks, int ns, int sbits,
+                                                           int64_t nchunks, int ns, int sbits, int split,
                                                            uint32_t* __restrict__ chist) {
     constexpr int W = kHistBlock / 64;
     __shared__ uint32_t rows[W][64];  // hist_words(ns) <= 64
@@ -461,10 +479,14 @@ __global__ void __launch_bounds__(kHistBlock) k_chunk_hist(const uint2* __restri
         h[lane] = 0;
         wave_lds_order();
         const uint2* __restrict__ c = pool + (size_t)q * kCh;
+        const uint32_t* __restrict__ cs = split_s(pool, (size_t)q);  // the split pool's source words
         for (uint32_t i0 = 0; i0 < fill; i0 += 256) {  // four loads in flight per lane
             uint32_t x[4];
 #pragma unroll
-            for (int k = 0; k < 4; ++k) x[k] = c[min(i0 + (uint32_t)(k * 64 + lane), fill - 1)].x;
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t i = min(i0 + (uint32_t)(k * 64 + lane), fill - 1);
+                x[k] = split ? cs[i] : c[i].x;
+            }
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (i0 + (uint32_t)(k * 64 + lane) < fill) hist_add(h, hw, 0, x[k] >> sbits);
@@ -753,7 +775,7 @@ __host__ __device__ constexpr size_t s2_hold_bytes(int nb, bool pk) {
     return pk ? (((size_t)nb * s2_line(true) * 5 + 15) & ~(size_t)15) : sizeof(uint2) * (size_t)nb * kLine;
 }
 
-template <bool HOP1, bool PK>  // PK: without HOP1 (LDS)
+template <bool HOP1, bool PK, bool SP = false>  // PK: without HOP1 (LDS); SP: the pool is split (part_common.h)
 __global__ void __launch_bounds__(kSBlock) k_scatter_s2(const void* __restrict__ pool_,
                                                         const unsigned long long* __restrict__ cmeta,
                                                         const uint32_t* __restrict__ order,
@@ -819,6 +841,22 @@ __global__ void __launch_bounds__(kSBlock) k_scatter_s2(const void* __restrict__
     auto load_chunk = [&](int64_t q, uint2 (&pr)[kItems]) -> uint32_t {
         const uint32_t phys = order[q];
         const uint32_t fill = (uint32_t)(cmeta[phys] >> 32);
+        if (SP) {  // the same two pairs per load step, from the two word arrays
+            const int bytes = (int)(fill * sizeof(uint32_t));
+            const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<uint32_t*>(split_t(pool, phys)), (short)0, bytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<uint32_t*>(split_s(pool, phys)), (short)0, bytes, 0x00020000);
+#pragma unroll
+            for (int k = 0; k < kItems / 2; ++k) {
+                const uint32_t at = (uint32_t)(k * kSBlock + (int)threadIdx.x) * 8u;
+                const auto t = __builtin_amdgcn_raw_buffer_load_b64(rt, at, 0, 0);
+                const auto x = __builtin_amdgcn_raw_buffer_load_b64(rx, at, 0, 0);
+                pr[2 * k] = make_uint2(x[0], t[0] & ~kLoopBit);
+                pr[2 * k + 1] = make_uint2(x[1], t[1] & ~kLoopBit);
+            }
+            return fill;
+        }
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<uint2*>(pool + (size_t)phys * kCh), (short)0, (int)(fill * sizeof(uint2)), 0x00020000);
 #pragma unroll
@@ -1105,31 +1143,46 @@ __device__ __forceinline__ void pool_flush(uint32_t* tl, uint32_t* g, int j, int
 }
 
 // Hop 1 for a full a_ok: M(t) for s != t in LDS, flushed through b_ok; self-loops -> S1 / S2 as in
-// k_scatter_s2<true>.
+// k_scatter_s2<true>.  It uses the target and whether the pair is a loop, nothing else of the source: over a
+// split pool (SPLIT) it walks the T arrays alone, 4 bytes per relationship.
+template <bool SPLIT>
 __global__ void __launch_bounds__(kPoolBlock) k_pool_hop1(ChunkWalk cw, BitV tmask, uint32_t* __restrict__ M,
                                                           uint32_t* __restrict__ S1, uint32_t* __restrict__ S2,
                                                           int64_t gwords) {
     extern __shared__ __attribute__((aligned(16))) uint32_t tl[];
     for (int k = threadIdx.x; k < kSliceWords; k += kPoolBlock) tl[k] = 0;
     __syncthreads();
-    walk_chunks_n<kPoolBlock>(
-        cw,
-        [&](const uint2 (&pr)[kWalkItems], uint32_t valid, int j) {
-            const uint32_t tbase = (uint32_t)j << kSliceBits;
+    auto mark = [&](uint32_t t, bool loop, uint32_t tbase) {
+        if (!loop) {
+            lds_set(tl, t - tbase);
+        } else if (tmask.full || gbit(tmask.w, t)) {  // rare: self-loops
+            const uint32_t bit = 1u << (t & 31);
+            const uint32_t old = atomicOr(&S1[t >> 5], bit);
+            if (old & bit) atomicOr(&S2[t >> 5], bit);
+        }
+    };
+    auto flush = [&](int j) { pool_flush(tl, M, j, gwords, tmask); };
+    if (SPLIT) {
+        walk_chunks_t<kPoolBlock>(
+            cw,
+            [&](const uint32_t (&tw)[kWalkWords], uint32_t valid, int j) {
+                const uint32_t tbase = (uint32_t)j << kSliceBits;
 #pragma unroll
-            for (int k = 0; k < kWalkItems; ++k) {
-                if (!((valid >> k) & 1u)) continue;
-                const uint32_t s = pr[k].x, t = pr[k].y;
-                if (s != t) {
-                    lds_set(tl, t - tbase);
-                } else if (tmask.full || gbit(tmask.w, t)) {  // rare: self-loops
-                    const uint32_t bit = 1u << (t & 31);
-                    const uint32_t old = atomicOr(&S1[t >> 5], bit);
-                    if (old & bit) atomicOr(&S2[t >> 5], bit);
-                }
-            }
-        },
-        [&](int j) { pool_flush(tl, M, j, gwords, tmask); });
+                for (int k = 0; k < kWalkWords; ++k)
+                    if ((valid >> k) & 1u) mark(tw[k] & ~kLoopBit, (tw[k] & kLoopBit) != 0, tbase);
+            },
+            flush);
+    } else {
+        walk_chunks_n<kPoolBlock>(
+            cw,
+            [&](const uint2 (&pr)[kWalkItems], uint32_t valid, int j) {
+                const uint32_t tbase = (uint32_t)j << kSliceBits;
+#pragma unroll
+                for (int k = 0; k < kWalkItems; ++k)
+                    if ((valid >> k) & 1u) mark(pr[k].y, pr[k].x == pr[k].y, tbase);
+            },
+            flush);
+    }
 }
 
 // Hop 2: C(t) |= X1(s) for s != t, X2(s) for s == t, with the C slice in LDS.  A pair whose target bit is
@@ -1137,6 +1190,7 @@ __global__ void __launch_bounds__(kPoolBlock) k_pool_hop1(ChunkWalk cw, BitV tma
 // are preset so their pairs skip too, and the flush masks them off again.  A lane tests its step's targets
 // first, then issues the X1 gathers of the unset ones together (buffer loads: a lane that needs none gives an
 // offset past the bitmap, which reads as zero without a memory request) and only then sets bits.
+template <bool SPLIT>
 __global__ void __launch_bounds__(kPoolBlock, 8) k_pool_hop2(ChunkWalk cw, const uint32_t* __restrict__ X1,
                                                              const uint32_t* __restrict__ X2, BitV cmask,
                                                              uint32_t* __restrict__ C, int64_t gwords) {
@@ -1145,37 +1199,56 @@ __global__ void __launch_bounds__(kPoolBlock, 8) k_pool_hop2(ChunkWalk cw, const
     __syncthreads();
     const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(
         const_cast<uint32_t*>(X1), (short)0, (int)(gwords * (int64_t)sizeof(uint32_t)), 0x00020000);
-    walk_chunks_n<kPoolBlock>(
-        cw,
-        [&](const uint2 (&pr)[kWalkItems], uint32_t valid, int j) {
-            const uint32_t tbase = (uint32_t)j << kSliceBits;
-            uint32_t need = 0;
+    // a lane's step: pair k is source(k) -> the target whose in-slice offset is off(k), a loop if loop(k)
+    auto step = [&](auto source, auto off, auto loop, uint32_t valid) {
+        uint32_t need = 0;
 #pragma unroll
-            for (int k = 0; k < kWalkItems; ++k) {
-                const uint32_t r = (pr[k].y - tbase) & ((1u << kSliceBits) - 1u);
-                if (((valid >> k) & 1u) && !((tl[r >> 5] >> (r & 31)) & 1u)) need |= 1u << k;
-            }
-            uint32_t xw[kWalkItems];
+        for (int k = 0; k < kWalkItems; ++k) {
+            const uint32_t r = off(k);
+            if (((valid >> k) & 1u) && !((tl[r >> 5] >> (r & 31)) & 1u)) need |= 1u << k;
+        }
+        uint32_t xw[kWalkItems];
 #pragma unroll
-            for (int k = 0; k < kWalkItems; ++k) {
-                const bool ld = ((need >> k) & 1u) && pr[k].x != pr[k].y;
-                xw[k] = __builtin_amdgcn_raw_buffer_load_b32(xr, ld ? (pr[k].x >> 5) * 4u : 0xFFFFFFF0u, 0, 0);
-            }
+        for (int k = 0; k < kWalkItems; ++k) {
+            const bool ld = ((need >> k) & 1u) && !loop(k);
+            xw[k] = __builtin_amdgcn_raw_buffer_load_b32(xr, ld ? (source(k) >> 5) * 4u : 0xFFFFFFF0u, 0, 0);
+        }
 #pragma unroll
-            for (int k = 0; k < kWalkItems; ++k) {
-                if (!((need >> k) & 1u)) continue;
-                const uint32_t s = pr[k].x, t = pr[k].y;
-                const bool ok = s != t ? ((xw[k] >> (s & 31)) & 1u) != 0 : gbit(X2, s);  // self-loops: rare
-                if (ok) lds_set(tl, t - tbase);
-            }
-        },
-        [&](int j) { pool_flush(tl, C, j, gwords, cmask); },
-        [&](int j) {
-            if (cmask.full) return;
-            const int64_t w0 = (int64_t)j * kSliceWords;
-            for (int i = threadIdx.x; i < kSliceWords; i += kPoolBlock)
-                tl[i] = w0 + i < gwords ? ~cmask.w[w0 + i] : 0xFFFFFFFFu;
-        });
+        for (int k = 0; k < kWalkItems; ++k) {
+            if (!((need >> k) & 1u)) continue;
+            const uint32_t s = source(k);
+            const bool ok = !loop(k) ? ((xw[k] >> (s & 31)) & 1u) != 0 : gbit(X2, s);  // self-loops: rare
+            if (ok) lds_set(tl, off(k));
+        }
+    };
+    auto flush = [&](int j) { pool_flush(tl, C, j, gwords, cmask); };
+    auto begin = [&](int j) {
+        if (cmask.full) return;
+        const int64_t w0 = (int64_t)j * kSliceWords;
+        for (int i = threadIdx.x; i < kSliceWords; i += kPoolBlock)
+            tl[i] = w0 + i < gwords ? ~cmask.w[w0 + i] : 0xFFFFFFFFu;
+    };
+    if (SPLIT) {
+        walk_chunks_st<kPoolBlock>(
+            cw,
+            [&](const uint32_t (&sw)[kWalkItems], const uint32_t (&tw)[kWalkItems], uint32_t valid, int j) {
+                const uint32_t tbase = (uint32_t)j << kSliceBits;
+                step([&](int k) { return sw[k]; },
+                     [&](int k) { return (tw[k] - tbase) & ((1u << kSliceBits) - 1u); },  // drops the loop bit too
+                     [&](int k) { return (tw[k] & kLoopBit) != 0; }, valid);
+            },
+            flush, begin);
+    } else {
+        walk_chunks_n<kPoolBlock>(
+            cw,
+            [&](const uint2 (&pr)[kWalkItems], uint32_t valid, int j) {
+                const uint32_t tbase = (uint32_t)j << kSliceBits;
+                step([&](int k) { return pr[k].x; },
+                     [&](int k) { return (pr[k].y - tbase) & ((1u << kSliceBits) - 1u); },
+                     [&](int k) { return pr[k].x == pr[k].y; }, valid);
+            },
+            flush, begin);
+    }
 }
 
 }  // namespace part
@@ -1233,13 +1306,21 @@ static void allow_lds(K kernel, size_t bytes) {
 }
 
 void chunk_partition(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
-                     int nt, bool swap, const part::Layout& L, int64_t g2_want, ChunkPart& cp, bool want_hist) {
+                     int nt, bool swap, const part::Layout& L, int64_t g2_want, ChunkPart& cp, bool want_hist,
+                     bool want_split) {
     using namespace part;
     hipStream_t st = s->stream;
     cp.L = L;
     // the whole-line variant where its LDS fits with the cell counts (the choice does not follow want_hist:
     // the pool of a layout is the same whoever asks for it)
     const bool lines = scatter1l_lds(L.nt, L.ns, true, kP1Block, kP1Tile) <= (size_t)160 * 1024;
+    // the split pool: the whole-line pass 1 without cell counts, where its 32-pair holds fit too; else pairs
+    const bool split = want_split && lines && !want_hist &&
+                       scatter1l_lds(L.nt, L.ns, false, kP1Block, kP1Tile, true) <= (size_t)160 * 1024;
+    if (split)
+        REQUIRE((uint64_t)(L.hi - L.lo) <= (uint64_t(1) << 30), CAPSMI_ERR_UNSUPPORTED,
+                "the split pool keeps a flag in bit 31 of its target words: at most 2^30 ids");
+    cp.split = split;
     // pass 1 grid: one 1024-lane block per CU, fewer for small inputs so the open chunks
     // (blocks x slices) stay within a few times the filled ones
     std::vector<int> g1(nt, 0);
@@ -1273,8 +1354,9 @@ void chunk_partition(capsmi_session* s, const int64_t* const* srcs, const int64_
     if (want_hist) cp.chist = dev_alloc(sizeof(uint32_t) * hw * (size_t)npool, s);
     // (clearing each block's metadata range inside pass 1 instead measured 5.25 -> 5.39 ms at C3: the fill stays)
     HIP_CHECK(hipMemsetAsync(P<void>(cp.meta), 0, sizeof(unsigned long long) * npool, st));
-    const size_t lds1 = lines ? scatter1l_lds(L.nt, L.ns, want_hist, kP1Block, kP1Tile) : scatter1_lds(L.nt, L.ns, want_hist);
-    auto k1 = lines ? (want_hist ? k_scatter_l<kP1Block, kItems, 4, true> : k_scatter_l<kP1Block, kItems, 4, false>)
+    const size_t lds1 = lines ? scatter1l_lds(L.nt, L.ns, want_hist, kP1Block, kP1Tile, split) : scatter1_lds(L.nt, L.ns, want_hist);
+    auto k1 = split ? k_scatter_l<kP1Block, kItems, 4, false, true>
+              : lines ? (want_hist ? k_scatter_l<kP1Block, kItems, 4, true> : k_scatter_l<kP1Block, kItems, 4, false>)
                     : (want_hist ? k_scatter_c<kP1Block, kItems, 4, kP1NT, true>
                                  : k_scatter_c<kP1Block, kItems, 4, kP1NT, false>);
     allow_lds(k1, lds1);
@@ -1287,6 +1369,7 @@ void chunk_partition(capsmi_session* s, const int64_t* const* srcs, const int64_
     }
     HIP_CHECK(hipGetLastError());
     cp.mtot = mtot;
+    if (split) s->routes["pool_split"] += 1;
     chunk_order(s, L.nt, pool_chunks, g2_want, cp);
 }
 
@@ -1400,16 +1483,20 @@ void relpart_build(capsmi_session* s, const int64_t* const* srcs, const int64_t*
     // 5.58 ms, pass 2 + hop 1 3.76 -> 4.45 ms at C3; both passes are bound by their LDS / VALU phases)
     // the pool hops read no cell counts: pass 1 leaves them out, and a later reader of the cells has
     // k_chunk_hist make them (cells_build)
-    chunk_partition(s, srcs, dsts, ms, nt, false, L, (int64_t)s->num_cus * (fuse ? 1 : 2), cp, !pool_hop);
+    // and hop 1 reads no sources: the pool is split (CAPSMI_POOL), so it streams the target words alone
+    chunk_partition(s, srcs, dsts, ms, nt, false, L, (int64_t)s->num_cus * (fuse ? 1 : 2), cp, !pool_hop,
+                    pool_hop && s->cfg.pool_split);
     rp.cells = false;
     rp.sel = -1;
     rp.kept = -1;  // known on the device (boff[ncells]); read only when asked (relpart_kept)
     rp.rows = cp.mtot;
     if (pool_hop) {
         const size_t lds = sizeof(uint32_t) * kSliceWords;
-        allow_lds(k_pool_hop1, lds);
-        KernelTimer kt(s, "hop1");
-        hipLaunchKernelGGL(k_pool_hop1, dim3(pool_grid(s, cp)), dim3(kPoolBlock), lds, st, chunk_walk(cp),
+        auto k = cp.split ? k_pool_hop1<true> : k_pool_hop1<false>;
+        allow_lds(k, lds);
+        // split: 4 B per pair and M written, declared since the caller's own figure is the pair format's
+        KernelTimer kt(s, "hop1", cp.split ? 4.0 * (double)cp.mtot + 4.0 * (double)h1->b->nwords : 0.0);
+        hipLaunchKernelGGL(k, dim3(pool_grid(s, cp)), dim3(kPoolBlock), lds, st, chunk_walk(cp),
                            BitV{P<uint32_t>(h1->b->words), h1->b->full ? 1 : 0}, h1->M, h1->S1, h1->S2, h1->b->nwords);
         HIP_CHECK(hipGetLastError());
         return;
@@ -1443,7 +1530,8 @@ static void cells_build(capsmi_session* s, RelPart& rp, const RelPartHop1* h1) {
             1, std::min<int64_t>((int64_t)s->num_cus * 8, (cp.pool_chunks + kHistBlock / 64 - 1) / (kHistBlock / 64)));
         KernelTimer kt(s, "part_chunk_hist");
         hipLaunchKernelGGL(k_chunk_hist, dim3(hg), dim3(kHistBlock), 0, st, P<uint2>(cp.pool),
-                           P<unsigned long long>(cp.meta), cp.pool_chunks, L.ns, L.sbits, P<uint32_t>(cp.chist));
+                           P<unsigned long long>(cp.meta), cp.pool_chunks, L.ns, L.sbits, cp.split ? 1 : 0,
+                           P<uint32_t>(cp.chist));
         HIP_CHECK(hipGetLastError());
         cp.has_hist = true;
         s->routes["chunk_hist"] += 1;
@@ -1467,7 +1555,9 @@ static void cells_build(capsmi_session* s, RelPart& rp, const RelPartHop1* h1) {
     const size_t lds2 = sizeof(uint2) * (size_t)kTile + s2_hold_bytes(L.ns, L.packed) +
                         sizeof(uint32_t) * (4 * L.ns + kSBlock / 64) + (fuse ? sizeof(uint32_t) * kSliceWords : 0);
     REQUIRE(lds2 <= (size_t)160 * 1024, CAPSMI_ERR_INTERNAL, "pass-2 LDS");
-    auto k2 = L.packed ? k_scatter_s2<false, true> : fuse ? k_scatter_s2<true, false> : k_scatter_s2<false, false>;
+    REQUIRE(!cp.split || !(L.packed || fuse), CAPSMI_ERR_INTERNAL, "a split pool feeds the plain pass 2 only");
+    auto k2 = cp.split ? k_scatter_s2<false, false, true>
+              : L.packed ? k_scatter_s2<false, true> : fuse ? k_scatter_s2<true, false> : k_scatter_s2<false, false>;
     allow_lds(k2, lds2);
     {
         KernelTimer kt(s, fuse ? "part_scatter2_hop1" : "part_scatter2");
@@ -1524,9 +1614,10 @@ void relpart_hop2(capsmi_session* s, RelPart& rp, const capsmi_bitmap* c, const 
         if (rp.sel == 0) {
             using namespace part;
             const size_t lds = sizeof(uint32_t) * kSliceWords;
-            allow_lds(k_pool_hop2, lds);
+            auto k = rp.cp.split ? k_pool_hop2<true> : k_pool_hop2<false>;
+            allow_lds(k, lds);
             KernelTimer kt(s, "hop2");
-            hipLaunchKernelGGL(k_pool_hop2, dim3(pool_grid(s, rp.cp)), dim3(kPoolBlock), lds, s->stream, chunk_walk(rp.cp),
+            hipLaunchKernelGGL(k, dim3(pool_grid(s, rp.cp)), dim3(kPoolBlock), lds, s->stream, chunk_walk(rp.cp),
                                X1, X2, cv, C, c->nwords);
             HIP_CHECK(hipGetLastError());
             s->routes["hop2_pool"] += 1;

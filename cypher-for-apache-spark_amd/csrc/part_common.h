@@ -250,23 +250,24 @@ struct NoBegin {
 // (G, the chunks in flight of the former block-per-chunk walk, is kept for the callers.)
 constexpr int kWalkItems = 8;  // pairs per lane per walk step (four 16-byte loads)
 
-// The walk below with the visit taking a lane's whole step: visit(pr, valid, j), pr[k] valid where
-// bit k of `valid` is set (entries past a chunk's fill read as zero pairs).  Lets a visit issue the
-// gathers of all its items before it uses any (a per-item visit waits for each in turn).
-template <int BLK, int G = 1, class VisitN, class Flush, class Begin = NoBegin>
-__device__ void walk_chunks_n(const ChunkWalk& cw, VisitN visit, Flush flush, Begin begin = Begin()) {
-    constexpr int kLd = kWalkItems / 2;    // 16-byte loads per lane per step
-    constexpr uint32_t kStep = 64 * kLd * 2;  // pairs per wave step
+// The slice visits of a block's chunk share: chunk(phys, fill, j) is called wave-uniformly, once per chunk a
+// wave takes, and walks that chunk in whatever format the pool has; flush and begin as above.
+template <int BLK, class Chunk, class Flush, class Begin = NoBegin>
+__device__ void walk_chunks_by(const ChunkWalk& cw, Chunk chunk, Flush flush, Begin begin = Begin()) {
     __shared__ uint32_t qn;                // next chunk of the slice visit
     const int64_t w = blockIdx.x, blocks = gridDim.x;
     const SegSplit S(cw.jst, cw.nt, blocks);
     const int64_t qb = w * S.per, qe = min(qb + S.per, S.nch);
     if (qb >= qe) return;  // block-uniform
     const int lane = threadIdx.x & 63;
-    auto grab = [&]() -> uint32_t {  // wave-uniform
+    // Wave-uniform values, held in scalar registers: the chunk's id and fill, and so the buffer descriptors the
+    // chunk lambdas make from them (from lane registers the compiler wraps every buffer load in a loop over the
+    // distinct descriptors and waits for each load before it issues the next).
+    auto uni = [](uint32_t x) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
+    auto grab = [&]() -> uint32_t {
         uint32_t t = 0;
         if (lane == 0) t = atomicAdd(&qn, 1u);
-        return __shfl(t, 0, 64);
+        return uni(t);
     };
     int cur_j = slice_of(cw.jst, cw.nt, qb);
     for (;;) {  // block-uniform: one visit per slice of the share
@@ -277,16 +278,42 @@ __device__ void walk_chunks_n(const ChunkWalk& cw, VisitN visit, Flush flush, Be
         const int j = cur_j;
         uint32_t t = grab(), phys = 0, fill = 0;
         if (c0 + t < c1) {
-            phys = cw.order[c0 + t];
-            fill = (uint32_t)(cw.meta[phys] >> 32);
+            phys = uni(cw.order[c0 + t]);
+            fill = uni((uint32_t)(cw.meta[phys] >> 32));
         }
         while (c0 + t < c1) {  // wave-uniform
             const uint32_t tn = grab();
             uint32_t pn = 0, fn = 0;
             if (c0 + tn < c1) {
-                pn = cw.order[c0 + tn];
-                fn = (uint32_t)(cw.meta[pn] >> 32);
+                pn = uni(cw.order[c0 + tn]);
+                fn = uni((uint32_t)(cw.meta[pn] >> 32));
             }
+            chunk(phys, fill, j);
+            t = tn;
+            phys = pn;
+            fill = fn;
+        }
+        __syncthreads();
+        flush(cur_j);
+        if (c1 >= qe) break;
+        do {
+            ++cur_j;
+        } while (cw.jst[cur_j + 1] <= cw.jst[cur_j]);  // empty slices are skipped
+        __syncthreads();
+    }
+}
+
+// The walk over a pool of pairs with the visit taking a lane's whole step: visit(pr, valid, j), pr[k] valid
+// where bit k of `valid` is set (entries past a chunk's fill read as zero pairs).  Lets a visit issue the
+// gathers of all its items before it uses any (a per-item visit waits for each in turn).
+template <int BLK, int G = 1, class VisitN, class Flush, class Begin = NoBegin>
+__device__ void walk_chunks_n(const ChunkWalk& cw, VisitN visit, Flush flush, Begin begin = Begin()) {
+    constexpr int kLd = kWalkItems / 2;    // 16-byte loads per lane per step
+    constexpr uint32_t kStep = 64 * kLd * 2;  // pairs per wave step
+    const int lane = threadIdx.x & 63;
+    walk_chunks_by<BLK>(
+        cw,
+        [&](uint32_t phys, uint32_t fill, int j) {
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
                 const_cast<uint2*>(cw.pool + (size_t)phys * kCh), (short)0, (int)(fill * sizeof(uint2)), 0x00020000);
             for (uint32_t o = 0; o < fill; o += kStep) {  // wave-uniform
@@ -304,18 +331,91 @@ __device__ void walk_chunks_n(const ChunkWalk& cw, VisitN visit, Flush flush, Be
                     valid |= (o + 2u * (uint32_t)((k >> 1) * 64 + lane) + (uint32_t)(k & 1) < fill ? 1u : 0u) << k;
                 visit(pr, valid, j);
             }
-            t = tn;
-            phys = pn;
-            fill = fn;
-        }
-        __syncthreads();
-        flush(cur_j);
-        if (c1 >= qe) break;
-        do {
-            ++cur_j;
-        } while (cw.jst[cur_j + 1] <= cw.jst[cur_j]);  // empty slices are skipped
-        __syncthreads();
-    }
+        },
+        flush, begin);
+}
+
+// ---- the split pool (ChunkPart::split) ----------------------------------------------------------------
+// Chunk q is two arrays of kCh words instead of kCh pairs: T[i] = y | (x == y) << 31 at the chunk's base and
+// S[i] = x behind it (ids below 2^30, so bit 31 is free).  A consumer that needs only the bucket side and the
+// x == y flag (hop 1 with a full a_ok) reads half the bytes.
+constexpr uint32_t kLoopBit = 1u << 31;
+
+__device__ __forceinline__ const uint32_t* split_t(const uint2* pool, size_t q) {
+    return reinterpret_cast<const uint32_t*>(pool + q * kCh);
+}
+__device__ __forceinline__ const uint32_t* split_s(const uint2* pool, size_t q) { return split_t(pool, q) + kCh; }
+
+// this lane's item k of a step of 16-byte word loads starting at word o: four consecutive words per load
+__device__ __forceinline__ uint32_t word_item(uint32_t o, int k, int lane) {
+    return o + 4u * (uint32_t)((k >> 2) * 64 + lane) + (uint32_t)(k & 3);
+}
+
+constexpr int kWalkWords = 16;  // T words per lane per step of the T-only walk (four 16-byte loads)
+
+// The T arrays alone: visit(tw, valid, j), tw[k] = T word (bit 31: x == y) valid where bit k of `valid` is set.
+template <int BLK, class VisitN, class Flush, class Begin = NoBegin>
+__device__ void walk_chunks_t(const ChunkWalk& cw, VisitN visit, Flush flush, Begin begin = Begin()) {
+    constexpr int kLd = kWalkWords / 4;
+    constexpr uint32_t kStep = 64 * kWalkWords;  // words per wave step
+    const int lane = threadIdx.x & 63;
+    walk_chunks_by<BLK>(
+        cw,
+        [&](uint32_t phys, uint32_t fill, int j) {
+            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<uint32_t*>(split_t(cw.pool, phys)), (short)0, (int)(fill * sizeof(uint32_t)), 0x00020000);
+            for (uint32_t o = 0; o < fill; o += kStep) {  // wave-uniform
+                uint32_t tw[kWalkWords];
+#pragma unroll
+                for (int k = 0; k < kLd; ++k) {
+                    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, word_item(o, 4 * k, lane) * 4u, 0, 2);  // nt
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) tw[4 * k + e] = v[e];
+                }
+                uint32_t valid = 0;
+#pragma unroll
+                for (int k = 0; k < kWalkWords; ++k) valid |= (word_item(o, k, lane) < fill ? 1u : 0u) << k;
+                visit(tw, valid, j);
+            }
+        },
+        flush, begin);
+}
+
+// Both arrays, kWalkItems pairs per lane per step (two 16-byte loads from each array, all issued before the
+// visit): visit(sw, tw, valid, j) with sw[k] = x and tw[k] = the T word of pair k.
+template <int BLK, class VisitN, class Flush, class Begin = NoBegin>
+__device__ void walk_chunks_st(const ChunkWalk& cw, VisitN visit, Flush flush, Begin begin = Begin()) {
+    constexpr int kLd = kWalkItems / 4;
+    constexpr uint32_t kStep = 64 * kWalkItems;  // pairs per wave step
+    const int lane = threadIdx.x & 63;
+    walk_chunks_by<BLK>(
+        cw,
+        [&](uint32_t phys, uint32_t fill, int j) {
+            const int bytes = (int)(fill * sizeof(uint32_t));
+            const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<uint32_t*>(split_t(cw.pool, phys)), (short)0, bytes, 0x00020000);
+            const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<uint32_t*>(split_s(cw.pool, phys)), (short)0, bytes, 0x00020000);
+            for (uint32_t o = 0; o < fill; o += kStep) {  // wave-uniform
+                uint32_t sw[kWalkItems], tw[kWalkItems];
+#pragma unroll
+                for (int k = 0; k < kLd; ++k) {
+                    const uint32_t at = word_item(o, 4 * k, lane) * 4u;
+                    const auto a = __builtin_amdgcn_raw_buffer_load_b128(rt, at, 0, 2);  // nt
+                    const auto b = __builtin_amdgcn_raw_buffer_load_b128(rx, at, 0, 2);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        tw[4 * k + e] = a[e];
+                        sw[4 * k + e] = b[e];
+                    }
+                }
+                uint32_t valid = 0;
+#pragma unroll
+                for (int k = 0; k < kWalkItems; ++k) valid |= (word_item(o, k, lane) < fill ? 1u : 0u) << k;
+                visit(sw, tw, valid, j);
+            }
+        },
+        flush, begin);
 }
 
 template <int BLK, int G = 1, class Visit, class Flush, class Begin = NoBegin>
@@ -342,8 +442,11 @@ __device__ __forceinline__ bool owns_slice(const ChunkWalk& cw, int j) {
 // ChunkPart (capsmi_impl.h): pass 1 of the partition, the chunk ordering and the segment split.
 // want_hist: pass 1 also counts every chunk's pairs per source slice (cp.chist, read by pass 2 of the 2-D
 // layout); callers whose consumers walk the pool pass false.
+// want_split: ask for the split pool (part::split_t; cp.split says whether the build took it: only without the
+// cell counts and where the whole-line pass 1 fits with 32-pair lines)
 void chunk_partition(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
-                     int nt, bool swap, const part::Layout& L, int64_t g2, ChunkPart& cp, bool want_hist);
+                     int nt, bool swap, const part::Layout& L, int64_t g2, ChunkPart& cp, bool want_hist,
+                     bool want_split = false);
 // the ordering half of chunk_partition for a pool another kernel filled (cp.meta: bucket | fill << 32)
 void chunk_order(capsmi_session* s, int nt, int64_t pool_chunks, int64_t g2, ChunkPart& cp);
 
