@@ -1190,10 +1190,16 @@ __global__ void __launch_bounds__(kPoolBlock) k_pool_hop1(ChunkWalk cw, BitV tma
 // are preset so their pairs skip too, and the flush masks them off again.  A lane tests its step's targets
 // first, then issues the X1 gathers of the unset ones together (buffer loads: a lane that needs none gives an
 // offset past the bitmap, which reads as zero without a memory request) and only then sets bits.
+// Over a split pool the steps run as a software pipeline (part::walk_chunks_st_pipe): the target test of step
+// i + 1 and the T loads of step i + 2 are issued while step i waits for its gathers, and a lane loads the
+// source words of four pairs only if one of them needs its source (about two thirds of the 128-byte source
+// lines at C3).  A target tested in step i + 1 may be set a moment later by step i - 1 or i: that costs one
+// gather too many and never a wrong bit, since C is an OR.  Four waves per SIMD is what one block per CU uses,
+// so the split instantiation may take 128 VGPRs for its three steps in flight.
 template <bool SPLIT>
-__global__ void __launch_bounds__(kPoolBlock, 8) k_pool_hop2(ChunkWalk cw, const uint32_t* __restrict__ X1,
-                                                             const uint32_t* __restrict__ X2, BitV cmask,
-                                                             uint32_t* __restrict__ C, int64_t gwords) {
+__global__ void __launch_bounds__(kPoolBlock, SPLIT ? 4 : 8)
+    k_pool_hop2(ChunkWalk cw, const uint32_t* __restrict__ X1, const uint32_t* __restrict__ X2, BitV cmask,
+                uint32_t* __restrict__ C, int64_t gwords) {
     extern __shared__ __attribute__((aligned(16))) uint32_t tl[];
     for (int k = threadIdx.x; k < kSliceWords; k += kPoolBlock) tl[k] = 0;
     __syncthreads();
@@ -1229,13 +1235,44 @@ __global__ void __launch_bounds__(kPoolBlock, 8) k_pool_hop2(ChunkWalk cw, const
             tl[i] = w0 + i < gwords ? ~cmask.w[w0 + i] : 0xFFFFFFFFu;
     };
     if (SPLIT) {
-        walk_chunks_st<kPoolBlock>(
+        constexpr uint32_t kOff = (1u << kSliceBits) - 1u;  // (T word - slice base) & kOff drops the loop bit too
+        walk_chunks_st_pipe<kPoolBlock>(
             cw,
-            [&](const uint32_t (&sw)[kWalkItems], const uint32_t (&tw)[kWalkItems], uint32_t valid, int j) {
+            [&](const uint32_t (&tw)[kWalkItems], uint32_t valid, int j) {
                 const uint32_t tbase = (uint32_t)j << kSliceBits;
-                step([&](int k) { return sw[k]; },
-                     [&](int k) { return (tw[k] - tbase) & ((1u << kSliceBits) - 1u); },  // drops the loop bit too
-                     [&](int k) { return (tw[k] & kLoopBit) != 0; }, valid);
+                uint32_t cbits[kWalkItems], need = 0;  // all eight LDS reads before any is used
+#pragma unroll
+                for (int k = 0; k < kWalkItems; ++k) cbits[k] = tl[((tw[k] - tbase) & kOff) >> 5];
+#pragma unroll
+                for (int k = 0; k < kWalkItems; ++k) need |= (~(cbits[k] >> (tw[k] & 31)) & 1u) << k;
+                return need & valid;
+            },
+            [&](const uint32_t (&sw)[kWalkItems], const uint32_t (&tw)[kWalkItems], uint32_t need,
+                uint32_t (&xw)[kWalkItems]) {
+#pragma unroll
+                for (int k = 0; k < kWalkItems; ++k) {
+                    const bool ld = ((need >> k) & 1u) && !(tw[k] & kLoopBit);
+                    xw[k] = __builtin_amdgcn_raw_buffer_load_b32(xr, ld ? (sw[k] >> 5) * 4u : 0xFFFFFFF0u, 0, 0);
+                }
+            },
+            [&](const uint32_t (&sw)[kWalkItems], const uint32_t (&tw)[kWalkItems], const uint32_t (&xw)[kWalkItems],
+                uint32_t need, int j) {
+                const uint32_t tbase = (uint32_t)j << kSliceBits;
+                uint32_t loops = 0;
+#pragma unroll
+                for (int k = 0; k < kWalkItems; ++k) {
+                    if (!((need >> k) & 1u)) continue;
+                    if (tw[k] & kLoopBit)
+                        loops |= 1u << k;
+                    else if ((xw[k] >> (sw[k] & 31)) & 1u)
+                        lds_set(tl, (tw[k] - tbase) & kOff);
+                }
+                // self-loops: rare.  A wave-uniform branch, so that the X2 read and its wait stay off the common path
+                if (__builtin_amdgcn_ballot_w64(loops != 0) != 0) {
+#pragma unroll
+                    for (int k = 0; k < kWalkItems; ++k)
+                        if (((loops >> k) & 1u) && gbit(X2, sw[k])) lds_set(tl, (tw[k] - tbase) & kOff);
+                }
             },
             flush, begin);
     } else {
@@ -1430,11 +1467,12 @@ static part::ChunkWalk chunk_walk(const ChunkPart& cp) {
 }
 
 // Grid of the pool hops: one 1024-lane block per CU (64 KiB of LDS), fewer for small tables so that a
-// block's share stays at 16 chunks or more.  More blocks would hide the X gathers' latency but cut the slices
-// into more shares, each of which meets a target for the first time once more (scripts/pool_reads_model.py:
-// 0.05 X reads per relationship at 256 shares of C3, 0.08 at 512), and every share pays a 64 KiB flush per
+// block's share stays at 16 chunks or more.  More blocks cut the slices into more shares, each of which meets a
+// target for the first time once more (scripts/pool_reads_model.py: 0.05 X reads per relationship and 0.65-0.68
+// of the source lines at 256 shares of C3, 0.08 and 0.81-0.84 at 512), and every share pays a 64 KiB flush per
 // slice it touches.  Measured at C3 (plain bench, alternating libraries on one box): two blocks per CU 8.89 /
-// 8.99 ms per step, one 8.70 / 8.67 ms.
+// 8.99 ms per step, one 8.70 / 8.67 ms.  The X gathers' latency is hidden inside the one block instead: hop 2
+// over a split pool keeps three steps per wave in flight (part::walk_chunks_st_pipe).
 constexpr int kPoolBlocksPerCU = 1;
 constexpr int64_t kPoolMinShare = 16 * (int64_t)part::kCh;  // pairs
 static unsigned pool_grid(const capsmi_session* s, const ChunkPart& cp) {

@@ -381,41 +381,156 @@ __device__ void walk_chunks_t(const ChunkWalk& cw, VisitN visit, Flush flush, Be
         flush, begin);
 }
 
-// Both arrays, kWalkItems pairs per lane per step (two 16-byte loads from each array, all issued before the
-// visit): visit(sw, tw, valid, j) with sw[k] = x and tw[k] = the T word of pair k.
-template <int BLK, class VisitN, class Flush, class Begin = NoBegin>
-__device__ void walk_chunks_st(const ChunkWalk& cw, VisitN visit, Flush flush, Begin begin = Begin()) {
+// A wave-uniform word of a list no kernel on the stream writes while this one runs (the chunk order, the chunks'
+// fills), read through the scalar cache: it counts on lgkmcnt, so fetching it waits for no vector load in flight.
+__device__ __forceinline__ uint32_t uniform_word(const void* p, int64_t i) {
+    typedef const __attribute__((address_space(4))) uint32_t* cptr;
+    return ((cptr)p)[i];
+}
+
+// Both arrays as a software pipeline, for a consumer that tests its targets before it needs a source and then
+// gathers by the sources it needs (hop 2).  A wave's steps of kWalkItems pairs per lane go through four stages:
+//   T(n)   the two 16-byte T loads of step n
+//   S(n)   need = test(tw, valid, j); each of the two 16-byte S loads only if one of its four pairs is in `need`
+//          (otherwise an offset past the array: no memory request, the words read as zero)
+//   X(n)   gather(sw, tw, need, xw): the consumer issues its gathers
+//   Set(n) set(sw, tw, xw, need, j): the consumer uses them
+// and the wave runs X(i), S(i+1), T(i+2), Set(i) per iteration: every wait is for the oldest load outstanding,
+// so the younger steps' loads stay in flight across it (vector loads return in order).  The steps run on across
+// the chunks a wave takes inside a slice visit and are drained before the visit's closing barrier.  A step's
+// chunk id, fill and offset are wave-uniform (scalar registers, as in walk_chunks_by) and the next chunk's come
+// through uniform_word, so a chunk change drains nothing.  Three register sets, the loop unrolled by three:
+// no load's destination is copied while the load is in flight.
+// `test` sees the consumer's state up to two steps old (S(i+1) runs before Set(i)): the consumer must be one for
+// which a stale "needed" costs work and never a wrong result.
+template <int BLK, class Test, class Gather, class Set, class Flush, class Begin = NoBegin>
+__device__ void walk_chunks_st_pipe(const ChunkWalk& cw, Test test, Gather gather, Set set, Flush flush,
+                                    Begin begin = Begin()) {
     constexpr int kLd = kWalkItems / 4;
     constexpr uint32_t kStep = 64 * kWalkItems;  // pairs per wave step
+    constexpr uint32_t kOut = 0x80000000u;       // byte offset past any chunk
+    __shared__ uint32_t qn;                      // next chunk of the slice visit
+    const int64_t w = blockIdx.x, blocks = gridDim.x;
+    const SegSplit Sg(cw.jst, cw.nt, blocks);
+    const int64_t qb = w * Sg.per, qe = min(qb + Sg.per, Sg.nch);
+    if (qb >= qe) return;  // block-uniform
     const int lane = threadIdx.x & 63;
-    walk_chunks_by<BLK>(
-        cw,
-        [&](uint32_t phys, uint32_t fill, int j) {
-            const int bytes = (int)(fill * sizeof(uint32_t));
-            const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<uint32_t*>(split_t(cw.pool, phys)), (short)0, bytes, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<uint32_t*>(split_s(cw.pool, phys)), (short)0, bytes, 0x00020000);
-            for (uint32_t o = 0; o < fill; o += kStep) {  // wave-uniform
-                uint32_t sw[kWalkItems], tw[kWalkItems];
-#pragma unroll
-                for (int k = 0; k < kLd; ++k) {
-                    const uint32_t at = word_item(o, 4 * k, lane) * 4u;
-                    const auto a = __builtin_amdgcn_raw_buffer_load_b128(rt, at, 0, 2);  // nt
-                    const auto b = __builtin_amdgcn_raw_buffer_load_b128(rx, at, 0, 2);
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        tw[4 * k + e] = a[e];
-                        sw[4 * k + e] = b[e];
+    auto uni = [](uint32_t x) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
+    auto grab = [&]() -> uint32_t {
+        uint32_t t = 0;
+        if (lane == 0) t = atomicAdd(&qn, 1u);
+        return uni(t);
+    };
+    struct Step {
+        uint32_t phys, fill, o;  // wave-uniform; a dead step (after the wave's last) has fill 0: its loads read zeros
+        bool live;
+    };
+    int cur_j = slice_of(cw.jst, cw.nt, qb);
+    for (;;) {  // block-uniform: one visit per slice of the share
+        const int64_t c0 = max(qb, cw.jst[cur_j]), c1 = min(qe, cw.jst[cur_j + 1]);
+        if (threadIdx.x == 0) qn = 0;
+        begin(cur_j);
+        __syncthreads();
+        const int j = cur_j;
+        const uint32_t nq = (uint32_t)(c1 - c0);
+        // the wave's steps in order: the current chunk (phys, fill) at offset o, the next one's id fetched when
+        // the current is entered and its fill one step later, both used only at the change
+        uint32_t phys = 0, fill = 0, o = 0, pn = 0, fn = 0;
+        bool fpend = false;
+        uint32_t tn = grab();
+        bool live = tn < nq, nlive = false;
+        if (live) {
+            phys = uniform_word(cw.order, c0 + tn);
+            fill = uniform_word(cw.meta, 2 * (int64_t)phys + 1);
+            tn = grab();
+            nlive = tn < nq;
+            if (nlive) {
+                pn = uniform_word(cw.order, c0 + tn);
+                fpend = true;
+            }
+        }
+        auto next = [&]() __attribute__((always_inline)) -> Step {
+            const Step r{phys, fill, o, live};
+            if (fpend) {
+                fn = uniform_word(cw.meta, 2 * (int64_t)pn + 1);
+                fpend = false;
+            }
+            if (live) {
+                if (o + kStep < fill) {
+                    o += kStep;
+                } else {
+                    phys = pn;
+                    fill = fn;
+                    o = 0;
+                    live = nlive;
+                    if (live) {
+                        tn = grab();
+                        nlive = tn < nq;
+                        if (nlive) {
+                            pn = uniform_word(cw.order, c0 + tn);
+                            fpend = true;
+                        }
                     }
                 }
-                uint32_t valid = 0;
-#pragma unroll
-                for (int k = 0; k < kWalkItems; ++k) valid |= (word_item(o, k, lane) < fill ? 1u : 0u) << k;
-                visit(sw, tw, valid, j);
             }
-        },
-        flush, begin);
+            if (!r.live) return Step{0u, 0u, 0u, false};
+            return r;
+        };
+        Step st[3];
+        uint32_t tw[3][kWalkItems], sw[3][kWalkItems], xw[3][kWalkItems], need[3];
+        auto T = [&](int s, Step g) __attribute__((always_inline)) {
+            g = Step{uni(g.phys), uni(g.fill), uni(g.o), g.live};  // scalar registers, whatever carried them here
+            st[s] = g;
+            const __amdgpu_buffer_rsrc_t rt = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<uint32_t*>(split_t(cw.pool, g.phys)), (short)0, (int)(g.fill * sizeof(uint32_t)), 0x00020000);
+#pragma unroll
+            for (int k = 0; k < kLd; ++k) {
+                const auto a = __builtin_amdgcn_raw_buffer_load_b128(rt, word_item(g.o, 4 * k, lane) * 4u, 0, 2);  // nt
+#pragma unroll
+                for (int e = 0; e < 4; ++e) tw[s][4 * k + e] = a[e];
+            }
+        };
+        auto S = [&](int s) __attribute__((always_inline)) {
+            const Step g{uni(st[s].phys), uni(st[s].fill), uni(st[s].o), st[s].live};
+            uint32_t valid = 0;
+#pragma unroll
+            for (int k = 0; k < kWalkItems; ++k) valid |= (word_item(g.o, k, lane) < g.fill ? 1u : 0u) << k;
+            const uint32_t nd = test(tw[s], valid, j);
+            need[s] = nd;
+            const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<uint32_t*>(split_s(cw.pool, g.phys)), (short)0, (int)(g.fill * sizeof(uint32_t)), 0x00020000);
+#pragma unroll
+            for (int k = 0; k < kLd; ++k) {
+                const bool ld = ((nd >> (4 * k)) & 0xFu) != 0;
+                const auto b =
+                    __builtin_amdgcn_raw_buffer_load_b128(rx, ld ? word_item(g.o, 4 * k, lane) * 4u : kOut, 0, 2);  // nt
+#pragma unroll
+                for (int e = 0; e < 4; ++e) sw[s][4 * k + e] = b[e];
+            }
+        };
+        auto X = [&](int s) __attribute__((always_inline)) { gather(sw[s], tw[s], need[s], xw[s]); };
+        auto Z = [&](int s) __attribute__((always_inline)) { set(sw[s], tw[s], xw[s], need[s], j); };
+        T(0, next());
+        if (st[0].live) {  // wave-uniform
+            S(0);
+            T(1, next());
+            for (;;) {  // Set(i) ends an iteration; a dead step i + 1 means every load issued since is dead too
+                X(0); S(1); T(2, next()); Z(0);
+                if (!st[1].live) break;
+                X(1); S(2); T(0, next()); Z(1);
+                if (!st[2].live) break;
+                X(2); S(0); T(1, next()); Z(2);
+                if (!st[0].live) break;
+            }
+        }
+        __syncthreads();
+        flush(cur_j);
+        if (c1 >= qe) break;
+        do {
+            ++cur_j;
+        } while (cw.jst[cur_j + 1] <= cw.jst[cur_j]);  // empty slices are skipped
+        __syncthreads();
+    }
 }
 
 template <int BLK, int G = 1, class Visit, class Flush, class Begin = NoBegin>

@@ -7,6 +7,11 @@ reads X(source); the ones whose source passes set the target.  Printed per share
 relationship, the first encounters per relationship (distinct targets per share: what k_pool_hop1 counts as
 R_est, the reads' lower bound) and the model's count(DISTINCT c) against the oracle's closed form.
 
+Over the split pool hop 2 reads the source words on demand: a lane's 16-byte S load covers four consecutive
+pairs of the step and is issued only if one of the four finds its target unset, and a 128-byte S line (32
+pairs, eight lanes) is fetched only if one of its eight loads is.  Printed too: the share of S loads issued and
+of S lines fetched.
+
 The share of the GPU's grid at scale 26 (2^30 relationships): 4 Mi pairs at 256 blocks, 2 Mi at 512 (the grid
 chosen, two blocks per CU).  The model keeps the share size, not the block count, when run at a smaller scale.
 
@@ -33,6 +38,12 @@ def frontier(n, src, dst):
     return M | (selfc >= 1), M | (selfc >= 2)
 
 
+def any_of(flags, width):
+    """per group of `width` consecutive pairs of a step: whether any is flagged"""
+    pad = (-len(flags)) % width
+    return np.concatenate([flags, np.zeros(pad, bool)]).reshape(-1, width).any(axis=1)
+
+
 def model(n, src, dst, share, step):
     X1, X2 = frontier(n, src, dst)
     ok = np.where(src == dst, X2[src], X1[src])
@@ -40,6 +51,7 @@ def model(n, src, dst, share, step):
     order = np.argsort(j, kind="stable")  # ingest order within a slice
     bounds = np.searchsorted(j[order], np.arange((n >> SLICE_BITS) + 2))
     reads = first = 0
+    s_loads = s_loads_all = s_lines = s_lines_all = 0
     C_all = np.zeros(n, bool)
     for a, b in zip(bounds[:-1], bounds[1:]):
         for s0 in range(a, b, share):
@@ -50,10 +62,15 @@ def model(n, src, dst, share, step):
                 tt = t[k:k + step]
                 unset = ~C[tt]
                 reads += int(unset.sum())
+                ld, ln = any_of(unset, 4), any_of(unset, 32)  # 16-byte loads (4 pairs), 128-byte lines (32)
+                s_loads += int(ld.sum())
+                s_loads_all += len(ld)
+                s_lines += int(ln.sum())
+                s_lines_all += len(ln)
                 C[tt[unset & p[k:k + step]]] = True
             first += len(np.unique(t))
             C_all |= C
-    return reads, first, int(C_all.sum())
+    return reads, first, int(C_all.sum()), s_loads / max(1, s_loads_all), s_lines / max(1, s_lines_all)
 
 
 def main():
@@ -72,8 +89,9 @@ def main():
           f"oracle distinct {want}")
     for share in (int(x) for x in args.shares.split(",")):
         for step in (int(x) for x in args.steps.split(",")):
-            reads, first, got = model(n, src, dst, share, step)
+            reads, first, got, loads, lines = model(n, src, dst, share, step)
             print(f"share {share} step {step}: X reads / rel {reads / m:.4f}, first encounters / rel {first / m:.4f}, "
+                  f"S loads issued {loads:.4f}, S lines fetched {lines:.4f}, "
                   f"distinct {got} ({'ok' if got == want else 'MISMATCH'})")
 
 
