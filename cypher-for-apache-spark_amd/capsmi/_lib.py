@@ -111,6 +111,7 @@ _SIGS = {
     "capsmi_session_kernel_time": (c_int32, [P, c_char_p, POINTER(c_int64), POINTER(ctypes.c_double)]),
     "capsmi_session_kernel_bytes": (c_int32, [P, c_char_p, POINTER(ctypes.c_double)]),
     "capsmi_session_set_params": (c_int32, [P, c_int32, P]),
+    "capsmi_session_set_strings": (c_int32, [P, c_int64, P, P, P]),
     "capsmi_table_from_host": (c_int32, [P, c_int32, POINTER(ColDesc), c_int64, PP]),
     "capsmi_table_from_device": (c_int32, [P, c_int32, POINTER(ColDesc), c_int64, PP]),
     "capsmi_table_retain": (c_int32, [P]),

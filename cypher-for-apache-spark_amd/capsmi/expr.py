@@ -20,6 +20,9 @@ Entity functions (:192-227): Labels and Keys, String lists built on the device f
 (``capsmi_with_mask_list_column``), and RelType, a Case over the type flags; startNode / endNode are the
 relationship's source and target columns.
 
+String matching (:152-157): StartsWith, EndsWith and Contains over String operands, matched byte-wise on the
+device against the session's string store (``Session.sync_strings``).
+
 ``compile_program`` lowers a tree to the postfix ``capsmi_expr`` program of include/capsmi.h.
 """
 from __future__ import annotations
@@ -39,6 +42,8 @@ X_COL, X_LIT, X_NULL, X_EQ, X_NEQ, X_LT, X_LE, X_GT, X_GE, X_NOT, X_AND, X_OR = 
 X_ISNULL, X_ISNOTNULL, X_IN, X_ADD, X_SUB, X_MUL, X_NEG, X_COALESCE = range(12, 20)
 X_BITAND, X_BITOR, X_SHL, X_SHRU, X_CASE, X_PARAM = range(20, 26)
 X_SIZE, X_INDEX, X_IN_LIST = range(26, 29)  # list operands: a Col of a list column
+X_STARTS_WITH, X_ENDS_WITH, X_CONTAINS = range(29, 32)  # String operands; they read the session's string store
+STRING_MATCH_OPS = (X_STARTS_WITH, X_ENDS_WITH, X_CONTAINS)
 
 BIN_OPS = {"=": X_EQ, "<>": X_NEQ, "<": X_LT, "<=": X_LE, ">": X_GT, ">=": X_GE, "+": X_ADD, "-": X_SUB, "*": X_MUL,
            "&": X_BITAND, "|": X_BITOR, "<<": X_SHL, ">>>": X_SHRU}
@@ -200,6 +205,36 @@ class Range(Expr):
     start: Expr
     end: Expr
     step: object = None
+
+
+@dataclass(frozen=True, eq=False)
+class StartsWith(Expr):
+    """StartsWith(lhs, rhs) (okapi-ir Expr.scala; SparkSQLExprMapper.scala:152-153, ``Column.startsWith``, Spark's
+    ``UTF8String.startsWith``): whether the String ``arg`` begins with the String ``pattern``, compared byte by byte
+    over UTF-8.  NULL when either operand is NULL (ExpressionBehaviour.scala:768-784); the empty pattern matches
+    every non-null string.  Both operands are String expressions (or a NULL literal)."""
+    arg: Expr
+    pattern: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class EndsWith(Expr):
+    """EndsWith(lhs, rhs) (SparkSQLExprMapper.scala:154-155, ``Column.endsWith``, ``UTF8String.endsWith``): whether
+    ``arg`` ends with ``pattern``; NULL when either operand is NULL (ExpressionBehaviour.scala:808-824)."""
+    arg: Expr
+    pattern: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class Contains(Expr):
+    """Contains(lhs, rhs) (SparkSQLExprMapper.scala:156-157, ``Column.contains``, ``UTF8String.contains``): whether
+    ``pattern`` occurs in ``arg`` as a run of bytes (UTF-8 is self-synchronising, so this is a run of characters);
+    NULL when either operand is NULL (ExpressionBehaviour.scala:848-864)."""
+    arg: Expr
+    pattern: Expr
+
+
+_STRING_MATCH = {StartsWith: X_STARTS_WITH, EndsWith: X_ENDS_WITH, Contains: X_CONTAINS}
 
 
 def _sorted_by_name(cols, names):
@@ -426,6 +461,10 @@ def compile_program(e: Expr, column_index: Callable[[str], int], encode_str: Cal
             go(x.arg)
             go(x.list)
             out.append((X_IN_LIST, 0, 0, 0))
+        elif type(x) in _STRING_MATCH:
+            go(x.arg)
+            go(x.pattern)
+            out.append((_STRING_MATCH[type(x)], 0, 0, 0))
         elif isinstance(x, RelType):
             go(x.to_case())
         elif isinstance(x, Case):

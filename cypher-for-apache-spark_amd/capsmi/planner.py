@@ -28,7 +28,7 @@ from typing import Dict, FrozenSet, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .expr import (BOOL, F64, I64, LIST, STR, Ands, BinOp, Col, Explode, Expr, In, IsNotNull, IsNull, ListLit, Lit, Not, Ors,
-                   Index, InList, Keys, Labels, Range, Size, ands, eq)
+                   Contains, EndsWith, Index, InList, Keys, Labels, Range, Size, StartsWith, ands, eq)
 from .table import ColumnData, decode_value
 
 
@@ -438,6 +438,7 @@ def _rel(m, names) -> RelPat:
 # expression DSL (JSON prefix lists) -> Expr over the current header
 # ---------------------------------------------------------------------------------------------
 _CMP = {"=", "<>", "<", "<=", ">", ">=", "+", "-", "*"}
+_STRING_MATCH = {"starts_with": StartsWith, "ends_with": EndsWith, "contains": Contains}
 
 
 def to_expr(spec, header: Sequence[str]) -> Expr:
@@ -477,6 +478,8 @@ def to_expr(spec, header: Sequence[str]) -> Expr:
         return Index(_list_operand(spec[1], header), to_expr(spec[2], header))
     if op == "in_list":
         return InList(to_expr(spec[1], header), _list_operand(spec[2], header))
+    if op in _STRING_MATCH:  # ["starts_with", s, p], ["ends_with", s, p], ["contains", s, p]
+        return _STRING_MATCH[op](to_expr(spec[1], header), to_expr(spec[2], header))
     if op == "range":
         if len(spec) not in (3, 4):
             raise PlanningError(f"range takes two or three operands: {spec!r}")

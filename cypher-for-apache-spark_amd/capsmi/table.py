@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _lib
 from .expr import (BOOL, F64, I64, LIST, STR, BinOp, CapsmiExpr, Case, Col, Explode, Expr, In, Index, InList, Keys, Labels, ListLit,
-                   Lit, Param, Range, Size, contains_range, needs_list_lowering, compile_program,
+                   Lit, Param, Range, Size, STRING_MATCH_OPS, contains_range, needs_list_lowering, compile_program,
                    contains_explode, mask_list_args, to_ctypes)
 
 _TLS = threading.local()
@@ -122,7 +122,10 @@ class StringDictionary:
     their codes (the first batch over [-2^62, 2^62]).  Equality and ordering on codes therefore equal
     equality and ordering on strings.  Every string that is encoded -- query literals included --
     is inserted, so two distinct strings never share a code.  A gap only runs out after ~60 nested
-    insertions at one spot; that raises instead of renumbering codes already on the device."""
+    insertions at one spot; that raises instead of renumbering codes already on the device.
+
+    ``growth`` counts the extensions that added a string: a caller that handed ``arrays()`` on (the session's
+    string store, ``Session.sync_strings``) compares it to know whether the dictionary has grown since."""
 
     LO, HI = -(1 << 62), 1 << 62
 
@@ -130,7 +133,19 @@ class StringDictionary:
         self._sorted: List[str] = []
         self._codes: List[int] = []
         self._by_code = {}
+        self.growth = 0
         self.extend(strings)
+
+    def arrays(self):
+        """``(codes int64[n], offsets int64[n + 1], bytes)`` of the n strings in code order -- which is string
+        order: string i has code ``codes[i]`` and the UTF-8 bytes ``bytes[offsets[i]:offsets[i + 1]]`` (the arrays
+        of include/capsmi.h capsmi_session_set_strings).  A string that carries bytes which are not UTF-8 as
+        surrogate escapes (PEP 383, ``bytes.decode("utf-8", "surrogateescape")``) is stored as those bytes."""
+        enc = [x.encode("utf-8", "surrogateescape") for x in self._sorted]
+        offsets = np.zeros(len(enc) + 1, dtype=np.int64)
+        if enc:
+            np.cumsum([len(b) for b in enc], out=offsets[1:])
+        return np.array(self._codes, dtype=np.int64), offsets, b"".join(enc)
 
     def extend(self, strings: Iterable[str]) -> None:
         new = sorted(set(strings) - set(self._by_code.values()))
@@ -152,6 +167,7 @@ class StringDictionary:
             placed += [(lo + (k + 1) * step, x) for k, x in enumerate(xs)]
         for c, x in placed:
             self._by_code[c] = x
+        self.growth += 1
         merged = sorted(list(zip(self._codes, self._sorted)) + placed)
         self._codes = [c for c, _ in merged]
         self._sorted = [x for _, x in merged]
@@ -182,6 +198,7 @@ class Session:
         self.device = device
         self.dictionary = dictionary or StringDictionary()
         self.params: List[object] = []  # the values of set_params (Explode of a list Param reads them)
+        self._strings_at = None  # the dictionary's growth counter at the last upload of the string store
 
     @property
     def handle(self):
@@ -259,6 +276,17 @@ class Session:
 
     def encode_str(self, s: str) -> int:
         return self.dictionary.encode(s)
+
+    def sync_strings(self) -> None:
+        """Register the dictionary's strings as the session's string store (include/capsmi.h
+        capsmi_session_set_strings), which StartsWith / EndsWith / Contains read on the device.  Uploads the whole
+        dictionary when it has grown since the last upload, else nothing; codes are stable, so every store is a
+        superset of the one before and programs compiled earlier stay valid."""
+        if self._strings_at == self.dictionary.growth:
+            return
+        codes, offsets, data = self.dictionary.arrays()
+        _lib.call("capsmi_session_set_strings", self._h, len(codes), codes.ctypes.data, offsets.ctypes.data, data)
+        self._strings_at = self.dictionary.growth
 
     def read_csv(self, paths: Sequence[str], names: Sequence[str], types: Sequence[int], delimiter: Optional[str] = ",",
                  comment: Optional[str] = None, row_id_col: Optional[str] = None) -> "GpuTable":
@@ -584,6 +612,8 @@ class GpuTable:
             return index[name]
 
         prog = compile_program(e, col, self.session.encode_str)
+        if any(p[0] in STRING_MATCH_OPS for p in prog):  # the literals are encoded by now: the store holds them
+            self.session.sync_strings()
         arr = to_ctypes(prog)
         if type(e) is Col:
             self._leaf[e.name] = arr

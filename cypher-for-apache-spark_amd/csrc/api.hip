@@ -533,6 +533,9 @@ bool apply(Config& c, const std::string& name, const char* v) {
     } else if (name == "CAPSMI_INGEST_THREADS") {
         if (!parse_int(v, 0, 1024, x)) return false;
         c.ingest_threads = (int)x;
+    } else if (name == "CAPSMI_STR_MATCH") {
+        if (!parse_choice(v, {"auto", "rows", "dict"}, k)) return false;
+        c.str_match = k;
     } else {
         return false;
     }
@@ -545,7 +548,7 @@ const std::pair<const char*, const char*> kKnobs[] = {
     {"CAPSMI_TRI_DEG_SAMPLE", "0"},  {"CAPSMI_TRI_SPLIT", "1"},      {"CAPSMI_TRI_VMODE_T", "256"},
     {"CAPSMI_UND", "part"},          {"CAPSMI_VL_BITS", "8"},        {"CAPSMI_VL_SUBLOG", "-1"},
     {"CAPSMI_VL_F2", "0"},           {"CAPSMI_COLL_CHUNK", "67108864"}, {"CAPSMI_INGEST_THREADS", "0"},
-    {"CAPSMI_HOP2", "auto"},         {"CAPSMI_POOL", "split"}};
+    {"CAPSMI_HOP2", "auto"},         {"CAPSMI_POOL", "split"},       {"CAPSMI_STR_MATCH", "auto"}};
 }  // namespace
 
 Config config_from_env() {
@@ -621,6 +624,7 @@ capsmi_status capsmi_session_destroy(capsmi_session* s) {
     use_device(s);
     (void)hipStreamSynchronize(s->stream);
     (void)hipStreamSynchronize(s->own_stream);
+    s->strings.reset();  // its blocks go back while the cache is open
     alloc_ctx_close(s);
     (void)hipStreamSynchronize(s->stream);
     (void)hipStreamSynchronize(s->own_stream);
@@ -696,6 +700,43 @@ capsmi_status capsmi_session_set_params(capsmi_session* s, int32_t nparams, cons
         ps[i].values.assign(p.values, p.values + p.count);
     }
     s->params = std::move(ps);
+    API_END
+}
+
+capsmi_status capsmi_session_set_strings(capsmi_session* s, int64_t nstrings, const int64_t* codes, const int64_t* offsets,
+                                         const char* bytes) {
+    API_BEGIN
+    need(s, "session");
+    REQUIRE(nstrings >= 0, CAPSMI_ERR_ILLEGAL_ARGUMENT, "string store: negative string count");
+    if (nstrings == 0) {
+        s->strings.reset();
+        return CAPSMI_OK;
+    }
+    need(codes, "codes");
+    need(offsets, "offsets");
+    REQUIRE(offsets[0] == 0, CAPSMI_ERR_ILLEGAL_ARGUMENT, "string store: offsets must start at 0");
+    for (int64_t i = 0; i < nstrings; ++i) {
+        REQUIRE(offsets[i + 1] >= offsets[i], CAPSMI_ERR_ILLEGAL_ARGUMENT,
+                "string store: offsets decrease at string " + std::to_string((long long)i));
+        REQUIRE(i == 0 || codes[i] > codes[i - 1], CAPSMI_ERR_ILLEGAL_ARGUMENT,
+                "string store: codes must ascend strictly (string " + std::to_string((long long)i) + ")");
+    }
+    const int64_t nbytes = offsets[nstrings];
+    REQUIRE(nbytes == 0 || bytes, CAPSMI_ERR_ILLEGAL_ARGUMENT, "string store: null bytes");
+    use_device(s);
+    auto st = std::make_shared<capsmi::StrStore>();
+    st->n = nstrings;
+    st->hcodes.assign(codes, codes + nstrings);
+    st->hoffsets.assign(offsets, offsets + nstrings + 1);
+    st->codes = dev_alloc(sizeof(int64_t) * nstrings, s);
+    st->offsets = dev_alloc(sizeof(int64_t) * (nstrings + 1), s);
+    st->bytes = dev_alloc(nbytes > 0 ? nbytes : 1, s);
+    HIP_CHECK(hipMemcpyAsync(P<void>(st->codes), codes, sizeof(int64_t) * nstrings, hipMemcpyHostToDevice, s->stream));
+    HIP_CHECK(hipMemcpyAsync(P<void>(st->offsets), offsets, sizeof(int64_t) * (nstrings + 1), hipMemcpyHostToDevice,
+                             s->stream));
+    if (nbytes > 0) HIP_CHECK(hipMemcpyAsync(P<void>(st->bytes), bytes, nbytes, hipMemcpyHostToDevice, s->stream));
+    HIP_CHECK(hipStreamSynchronize(s->stream));  // the caller's arrays are free again when the call returns
+    s->strings = std::move(st);
     API_END
 }
 

@@ -69,6 +69,15 @@ struct ListStore {
 };
 inline bool is_list_type(int32_t t) { return t >= CAPSMI_LIST_I64 && t <= CAPSMI_LIST_STR; }
 
+// The session's string store (capsmi_session_set_strings): string i has code codes[i] (strictly ascending) and
+// bytes[offsets[i] .. offsets[i+1]).  Replaced as a whole; a pass holds the one it started with.
+struct StrStore {
+    int64_t n = 0;                           // strings (> 0: an empty registration clears the store)
+    Buf codes, offsets, bytes;               // int64[n], int64[n + 1], uint8[offsets[n]]
+    std::vector<int64_t> hcodes, hoffsets;   // host copies: constant operands are resolved without the device
+};
+inline bool is_str_match(int32_t op) { return op >= CAPSMI_X_STARTS_WITH && op <= CAPSMI_X_CONTAINS; }
+
 struct Column {
     std::string name;
     int32_t type = CAPSMI_I64;
@@ -157,6 +166,9 @@ struct Config {
     bool vl_f2 = false;           // CAPSMI_VL_F2 = 1: the second-level filter in the T walk (the sharded form's)
     int64_t coll_chunk = int64_t(1) << 26;  // CAPSMI_COLL_CHUNK: elements per host collective call
     int ingest_threads = 0;       // CAPSMI_INGEST_THREADS (0: OMP_NUM_THREADS, else up to 16 hardware threads)
+    int str_match = 0;            // CAPSMI_STR_MATCH = auto | rows | dict (0..2): which side a string match with a constant
+                                  //   pattern runs on -- once per row, or once per entry of the string store with a
+                                  //   lookup per row (auto: the store when the table has at least as many rows; k_strmatch.hip)
 };
 // the environment's values over the defaults
 Config config_from_env();
@@ -174,6 +186,7 @@ struct capsmi_session {
         std::vector<capsmi_value> values;
     };
     std::vector<Param> params;  // query parameters (capsmi_session_set_params)
+    std::shared_ptr<const capsmi::StrStore> strings;  // the string store (capsmi_session_set_strings); null: none
     int device = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;  // current (own or external)
@@ -374,6 +387,20 @@ void explode_values(capsmi_session* s, int64_t n, int64_t count, const int64_t* 
 // (synchronises)
 void list_contains(capsmi_session* s, const int64_t* probe, const uint8_t* pvalid, int32_t ptype, const int64_t* word,
                    const uint8_t* lvalid, const ListStore& L, int64_t n, int64_t* out, uint8_t* out_valid);
+// string matching (k_strmatch.hip).  An operand is a constant (its code) or the rows' words (data, valid or null)
+struct StrOperand {
+    bool is_const = false;
+    int64_t code = 0;
+    const int64_t* data = nullptr;
+    const uint8_t* valid = nullptr;
+};
+// out / out_valid[r] = the three-valued CAPSMI_X_STARTS_WITH / ENDS_WITH / CONTAINS `op` of haystack h and pattern p,
+// not both constant, over the store registered now.  Throws ILLEGAL_ARGUMENT when none is, or when a non-null
+// operand's code is not in it (synchronises)
+void str_match(capsmi_session* s, int32_t op, const StrOperand& h, const StrOperand& p, int64_t n, int64_t* out,
+               uint8_t* out_valid);
+// the same for two constants, on the host (reads their bytes back; synchronises)
+bool str_match_fold(capsmi_session* s, int32_t op, int64_t hcode, int64_t pcode);
 // range(from, to, step) per row (step null: 1) as a store whose list r is row r's; `valid`: the rows none of
 // whose operands is null.  Throws ILLEGAL_ARGUMENT for a step 0, UNSUPPORTED for more elements than the device
 // holds (synchronises)

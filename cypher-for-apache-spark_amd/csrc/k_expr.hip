@@ -19,6 +19,8 @@
 //     reference to a list column pushes the row's list; size() and list[i] read the store's offsets and one value
 //     here; x IN list is lowered on the host (lower_in_list below) to a column that k_listexpr.hip computes over
 //     all the rows' elements before this interpreter runs.  No other opcode takes a list.
+//   - STARTS WITH / ENDS WITH / CONTAINS (SparkSQLExprMapper.scala:152-157) are lowered on the host the same way
+//     (lower_str_match below): k_strmatch.hip matches the bytes of the session's string store.
 #include "capsmi_impl.h"
 
 namespace capsmi {
@@ -232,6 +234,8 @@ int32_t infer_type(const capsmi_table* t, int32_t nn, const capsmi_expr* prog) {
             case CAPSMI_X_NOT: case CAPSMI_X_ISNULL: case CAPSMI_X_ISNOTNULL: pop(); st.push_back(CAPSMI_BOOL); break;
             case CAPSMI_X_NEG: break;
             case CAPSMI_X_SIZE: pop(); st.push_back(CAPSMI_I64); break;
+            case CAPSMI_X_STARTS_WITH: case CAPSMI_X_ENDS_WITH: case CAPSMI_X_CONTAINS:
+                pop(); pop(); st.push_back(CAPSMI_BOOL); break;
             case CAPSMI_X_INDEX: {
                 pop();
                 const int l = pop();
@@ -279,7 +283,8 @@ int expr_pops(const capsmi_expr& x) {
         case CAPSMI_X_EQ: case CAPSMI_X_NEQ: case CAPSMI_X_LT: case CAPSMI_X_LE: case CAPSMI_X_GT: case CAPSMI_X_GE:
         case CAPSMI_X_ADD: case CAPSMI_X_SUB: case CAPSMI_X_MUL:
         case CAPSMI_X_BITAND: case CAPSMI_X_BITOR: case CAPSMI_X_SHL: case CAPSMI_X_SHRU:
-        case CAPSMI_X_INDEX: case CAPSMI_X_IN_LIST: return 2;
+        case CAPSMI_X_INDEX: case CAPSMI_X_IN_LIST:
+        case CAPSMI_X_STARTS_WITH: case CAPSMI_X_ENDS_WITH: case CAPSMI_X_CONTAINS: return 2;
         default: return -1;
     }
 }
@@ -324,7 +329,7 @@ std::vector<capsmi_expr> bind_params(const capsmi_session* s, int32_t nn, const 
             continue;
         }
         const int pops = expr_pops(x);
-        if (pops < 0 && x.op > CAPSMI_X_IN_LIST) throw Error(CAPSMI_ERR_NOT_IMPLEMENTED, "unknown expression op " + std::to_string(x.op));
+        if (pops < 0 && x.op > CAPSMI_X_CONTAINS) throw Error(CAPSMI_ERR_NOT_IMPLEMENTED, "unknown expression op " + std::to_string(x.op));
         REQUIRE(pops >= 0 && (int)width.size() >= pops, CAPSMI_ERR_ILLEGAL_ARGUMENT,
                 "malformed expression program (stack underflow)");
         capsmi_expr y = x;
@@ -395,6 +400,13 @@ void validate_program(const capsmi_table* t, int32_t nn, const capsmi_expr* prog
                 res = x.op == CAPSMI_X_SIZE ? CAPSMI_I64 : (x.op == CAPSMI_X_IN_LIST ? CAPSMI_BOOL : (l < 0 ? -1 : l - CAPSMI_LIST));
                 break;
             }
+            case CAPSMI_X_STARTS_WITH: case CAPSMI_X_ENDS_WITH: case CAPSMI_X_CONTAINS:
+                for (int q = 0; q < 2; ++q)
+                    REQUIRE(opd[q] < 0 || opd[q] == CAPSMI_STR, CAPSMI_ERR_ILLEGAL_ARGUMENT,
+                            "STARTS WITH / ENDS WITH / CONTAINS take String operands (or a NULL literal that is untyped "
+                            "or typed String)");
+                res = CAPSMI_BOOL;
+                break;
             case CAPSMI_X_NEG: res = opd[0]; break;
             case CAPSMI_X_COALESCE: case CAPSMI_X_CASE:
                 for (int q = x.op == CAPSMI_X_CASE ? 1 : 0; q < pops; q += x.op == CAPSMI_X_CASE ? 2 : 1)
@@ -430,6 +442,28 @@ int subtree_start(const capsmi_expr* prog, int end) {
         if (want == 0) return i;
     }
     throw Error(CAPSMI_ERR_INTERNAL, "malformed expression program");
+}
+
+// The column `res` that a lowered node [p0 .. at] of prog left joins `view`; returns the reference that replaces
+// the node.
+capsmi_expr lend_column(capsmi_table& view, Column res, int32_t nn, const capsmi_expr* prog, int p0, int at,
+                        const char* what) {
+    capsmi_expr ref{};
+    ref.op = CAPSMI_X_COL;
+    if ((int)view.cols.size() < kMaxCols) {
+        ref.arg = (int32_t)view.cols.size();
+        view.cols.push_back(std::move(res));
+    } else {  // a table at the interpreter's column limit: the view lends a column the rest does not read
+        std::vector<bool> used(kMaxCols, false);
+        for (int i = 0; i < nn; ++i)
+            if ((i < p0 || i > at) && prog[i].op == CAPSMI_X_COL) used[prog[i].arg] = true;
+        int slot = 0;
+        while (slot < kMaxCols && used[slot]) ++slot;
+        REQUIRE(slot < kMaxCols, CAPSMI_ERR_NOT_IMPLEMENTED, std::string(what) + " in a program that reads 64 columns");
+        ref.arg = slot;
+        view.cols[slot] = std::move(res);
+    }
+    return ref;
 }
 
 // The program's first x IN list (node `at`; its list operand is the column reference before it) leaves the
@@ -469,19 +503,66 @@ void lower_in_list(capsmi_session* s, const capsmi_table* t, int32_t nn, const c
         res.valid = dev_alloc(n, s);
         list_contains(s, probe.d(), probe.v(), probe.type, lc.d(), lc.v(), *lc.list, n, P<int64_t>(res.data),
                       P<uint8_t>(res.valid));
-        ref.op = CAPSMI_X_COL;
-        if ((int)view.cols.size() < kMaxCols) {
-            ref.arg = (int32_t)view.cols.size();
-            view.cols.push_back(std::move(res));
-        } else {  // a table at the interpreter's column limit: the view lends a column the rest does not read
-            std::vector<bool> used(kMaxCols, false);
-            for (int i = 0; i < nn; ++i)
-                if ((i < p0 || i > at) && prog[i].op == CAPSMI_X_COL) used[prog[i].arg] = true;
-            int slot = 0;
-            while (slot < kMaxCols && used[slot]) ++slot;
-            REQUIRE(slot < kMaxCols, CAPSMI_ERR_NOT_IMPLEMENTED, "IN over a list column in a program that reads 64 columns");
-            ref.arg = slot;
-            view.cols[slot] = std::move(res);
+        ref = lend_column(view, std::move(res), nn, prog, p0, at, "IN over a list column");
+    }
+    low.push_back(ref);
+    low.insert(low.end(), prog + at + 1, prog + nn);
+    launch_eval(s, &view, (int32_t)low.size(), low.data(), out, out_valid, flags);
+}
+
+// The program's first string match (node `at`, stack [s, p]) leaves the interpreter as an IN_LIST does: an operand
+// that is a literal stays a constant, a plain column reference is read where it is, anything else is evaluated
+// into a temporary column; k_strmatch.hip's pass produces a temporary BOOL column, and the sub-range [s .. node]
+// becomes a reference to it.  A NULL literal operand: NULL without a kernel; two constants: a literal.
+void lower_str_match(capsmi_session* s, const capsmi_table* t, int32_t nn, const capsmi_expr* prog, int at, int64_t* out,
+                     uint8_t* out_valid, uint8_t* flags) {
+    const int64_t n = t->nrows;
+    const int p1 = at - 1, p0 = subtree_start(prog, p1);  // the pattern
+    const int h1 = p0 - 1, h0 = subtree_start(prog, h1);  // the string
+    capsmi_table view;
+    view.sess = s;
+    view.nrows = n;
+    view.cols = t->cols;
+    std::vector<capsmi_expr> low(prog, prog + h0);
+    capsmi_expr ref{};
+    const int span[2][2] = {{h0, h1}, {p0, p1}};
+    bool any_null = false;
+    for (const auto& sp : span) any_null = any_null || (sp[0] == sp[1] && prog[sp[0]].op == CAPSMI_X_NULL);
+    if (any_null) {
+        ref.op = CAPSMI_X_NULL;
+        ref.arg = CAPSMI_BOOL + 1;
+    } else {
+        StrOperand opd[2];
+        Column tmp[2];
+        for (int q = 0; q < 2; ++q) {
+            const int a = span[q][0], b = span[q][1];
+            if (a == b && prog[a].op == CAPSMI_X_LIT) {
+                opd[q].is_const = true;
+                opd[q].code = prog[a].ival;
+                continue;
+            }
+            if (a == b && prog[a].op == CAPSMI_X_COL) {
+                tmp[q] = t->cols[prog[a].arg];
+            } else {
+                tmp[q].data = dev_alloc(sizeof(int64_t) * n, s);
+                tmp[q].valid = dev_alloc(n, s);
+                launch_eval(s, t, b - a + 1, prog + a, P<int64_t>(tmp[q].data), P<uint8_t>(tmp[q].valid), nullptr);
+            }
+            opd[q].data = tmp[q].d();
+            opd[q].valid = tmp[q].v();
+        }
+        if (opd[0].is_const && opd[1].is_const) {
+            ref.op = CAPSMI_X_LIT;
+            ref.type = CAPSMI_BOOL;
+            ref.ival = str_match_fold(s, prog[at].op, opd[0].code, opd[1].code) ? 1 : 0;
+        } else {
+            Column res;
+            res.name = "__str_match";
+            res.type = CAPSMI_BOOL;
+            res.data = dev_alloc(sizeof(int64_t) * n, s);
+            res.valid = dev_alloc(n, s);
+            str_match(s, prog[at].op, opd[0], opd[1], n, P<int64_t>(res.data), P<uint8_t>(res.valid));
+            ref = lend_column(view, std::move(res), nn, prog, h0, at, "a string match");
         }
     }
     low.push_back(ref);
@@ -494,8 +575,10 @@ void launch_eval(capsmi_session* s, const capsmi_table* t, int32_t nn, const cap
     validate_program(t, nn, prog);
     const int64_t n = t->nrows;
     if (n == 0) return;
-    for (int i = 0; i < nn; ++i)
+    for (int i = 0; i < nn; ++i) {  // the first node that runs as a pass of its own; the recursion lowers the rest
         if (prog[i].op == CAPSMI_X_IN_LIST) return lower_in_list(s, t, nn, prog, i, out, out_valid, flags);
+        if (is_str_match(prog[i].op)) return lower_str_match(s, t, nn, prog, i, out, out_valid, flags);
+    }
     ColPtrs cp;
     for (int c = 0; c < kMaxCols; ++c) {
         cp.data[c] = nullptr;

@@ -145,13 +145,28 @@ enum {
                                is NULL or when i < 0 or i >= size (Spark's GetArrayItem: a negative index does
                                not count from the end); i must be Long, else CAPSMI_ERR_ILLEGAL_ARGUMENT;
                                ContainerIndex, :300-307 */
-    CAPSMI_X_IN_LIST = 28   /* stack [x, list]: BOOL, 3VL: NULL when x or the list is NULL; TRUE when some
+    CAPSMI_X_IN_LIST = 28,  /* stack [x, list]: BOOL, 3VL: NULL when x or the list is NULL; TRUE when some
                                element equals x under the interpreter's `=` (Long against Double as doubles,
                                NaN = NaN); NULL when the element type is not comparable with x (Long against
                                STR), as `=` gives; else FALSE (stores hold no element nulls).  In with a
                                list-valued right-hand side, array_contains, :138-145.  Each IN_LIST of a
                                program runs as one load-balanced pass over all the rows' elements before the
                                row-wise interpreter, which then reads its result as a column. */
+    /* String matching (StartsWith / EndsWith / Contains, :152-157: Column.startsWith / endsWith / contains,
+       Spark's UTF8String).  Stack [s, p], both CAPSMI_STR or a NULL literal (typed STR or untyped), else
+       CAPSMI_ERR_ILLEGAL_ARGUMENT when the node is built (a list value: CAPSMI_ERR_NOT_IMPLEMENTED); each
+       operand may be any scalar expression.  BOOL, 3VL: NULL when s or p is NULL, else TRUE or FALSE.  Bytes
+       of UTF-8 are compared (UTF-8 is self-synchronising, so nothing is decoded); the empty pattern matches
+       every non-null string, a pattern longer than the string never does.  The bytes come from the string
+       store that is registered when the action runs (capsmi_session_set_strings): without one the action
+       fails with CAPSMI_ERR_ILLEGAL_ARGUMENT ("no string store"), as it does when a non-null operand's code
+       is not registered in it.  A NULL literal operand gives NULL in every row without a kernel; two constants
+       are folded on the host.  Each of these nodes runs as a pass of its own before the row-wise interpreter
+       (k_strmatch.hip), which then reads its result as a column; CONTAINS is load-balanced over all the
+       rows' start positions. */
+    CAPSMI_X_STARTS_WITH = 29, /* stack [s, p]: s STARTS WITH p */
+    CAPSMI_X_ENDS_WITH = 30,   /* stack [s, p]: s ENDS WITH p */
+    CAPSMI_X_CONTAINS = 31     /* stack [s, p]: s CONTAINS p */
 };
 
 typedef struct {
@@ -241,7 +256,15 @@ capsmi_status capsmi_session_kernel_time(capsmi_session* s, const char* name, in
  * lengths / scan / compaction as "explode_starts"; "explode_values": 16 B per output row;
  * capsmi_with_mask_list_column's "mask_list_len": per row 9 B per nullable and 8 B per non-nullable column read
  * under CAPSMI_MASK_TRUE, 1 B per nullable column under CAPSMI_MASK_NOT_NULL, 17 B written, and "mask_list":
- * 8 B x (n starts + n masks read, M elements written), its scan and compaction timed as "mask_list_starts");
+ * 8 B x (n starts + n masks read, M elements written), its scan and compaction timed as "mask_list_starts";
+ * string matching's "str_index", code to store index: per row 16 B, 17 B for a nullable operand, plus 8 B per
+ * store entry; "str_match", the matching pass over n rows -- or over the store's entries on the dictionary side:
+ * 8 B per row and column operand (its index word) + 16 B per row and operand that is not constant (two offsets) +
+ * a constant pattern's bytes once + for CONTAINS 1 B per candidate slot (every start position is read at least
+ * once; the bytes behind a row's last slot, a column pattern's bytes and what STARTS / ENDS WITH compare depend
+ * on the data and are not counted); "str_match_lookup", the dictionary side's row gather: 18 B per row;
+ * CONTAINS's lengths / scan / compaction are timed as "str_match_starts" and the row side's three-valued finish as
+ * "str_match_finish", both without bytes);
  * 0 otherwise; then the counter resets. */
 capsmi_status capsmi_session_kernel_bytes(capsmi_session* s, const char* name, double* bytes);
 /* fused-path routing of lazy plans: enable / disable (default on; off = operator by operator, for
@@ -264,6 +287,15 @@ typedef struct {
     const capsmi_value* values;
 } capsmi_param;
 capsmi_status capsmi_session_set_params(capsmi_session* s, int32_t nparams, const capsmi_param* params);
+/* The string store: the bytes behind the codes of CAPSMI_STR values, which CAPSMI_X_STARTS_WITH / ENDS_WITH /
+ * CONTAINS read.  String i has code codes[i] and the UTF-8 bytes bytes[offsets[i] .. offsets[i+1]); codes are
+ * strictly ascending; offsets has nstrings + 1 entries, starts at 0 and never decreases.  The inputs are copied to
+ * the device (codes and offsets are kept on the host too); the call replaces the previous store as a whole, and
+ * nstrings == 0 clears it.  A program reads the store that is registered when its action runs, so a caller whose
+ * codes are stable registers supersets and nodes built earlier stay valid.  Malformed arrays or a null session
+ * are CAPSMI_ERR_ILLEGAL_ARGUMENT.  On several ranks each registers its own store (the operators are row-local). */
+capsmi_status capsmi_session_set_strings(capsmi_session* s, int64_t nstrings, const int64_t* codes,
+                                         const int64_t* offsets, const char* bytes);
 /* route "miss" counts materialisations in which a pattern over entity tables (joins of node and
  * relationship scans) matched no fused shape and ran operator by operator */
 capsmi_status capsmi_session_route_count(capsmi_session* s, const char* name, int64_t* count);

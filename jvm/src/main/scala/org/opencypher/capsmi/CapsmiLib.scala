@@ -68,6 +68,9 @@ object Capsmi {
   final val X_SIZE = 26     // [list]: element count, NULL for a NULL list
   final val X_INDEX = 27    // [list, i]: element i (0-based), NULL outside the list
   final val X_IN_LIST = 28  // [x, list]: x IN list-column, 3VL
+  final val X_STARTS_WITH = 29  // [s, p]: s STARTS WITH p over the session's string store, 3VL
+  final val X_ENDS_WITH = 30    // [s, p]: s ENDS WITH p
+  final val X_CONTAINS = 31     // [s, p]: s CONTAINS p
 
   // capsmi_with_mask_list_column: which columns of a row pass
   final val MASK_TRUE = 0     // labels(): the Boolean flag is non-null and TRUE
@@ -186,6 +189,7 @@ trait CapsmiLib extends Library {
   def capsmi_session_kernel_bytes(s: Pointer, name: String, bytes: DoubleByReference): Int
   def capsmi_session_set_fused(s: Pointer, enabled: Int): Int
   def capsmi_session_set_params(s: Pointer, nparams: Int, params: CapsmiParam): Int
+  def capsmi_session_set_strings(s: Pointer, nstrings: Long, codes: Array[Long], offsets: Array[Long], bytes: Array[Byte]): Int
   def capsmi_session_route_count(s: Pointer, name: String, count: LongByReference): Int
   def capsmi_session_set_unrouted_limit(s: Pointer, maxBytes: Long): Int
   def capsmi_session_set_csv_partitioning(s: Pointer, defaultParallelism: Long, maxPartitionBytes: Long,

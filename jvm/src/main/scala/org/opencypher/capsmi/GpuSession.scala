@@ -36,6 +36,16 @@ final class StringDictionary {
   private val Hi = 1L << 62
   private var byString = TreeMap.empty[String, Long]
   private var byCode = Map.empty[Long, String]
+  private var grown = 0L
+
+  /** Counts the strings added: a caller that handed `arrays` on compares it to know whether there are new ones. */
+  def growth: Long = synchronized(grown)
+
+  /** (codes, offsets, UTF-8 bytes) of the strings in code order, the arrays of capsmi_session_set_strings. */
+  def arrays: (Array[Long], Array[Long], Array[Byte]) = synchronized {
+    val enc = byString.keysIterator.map(_.getBytes(java.nio.charset.StandardCharsets.UTF_8)).toArray
+    (byString.valuesIterator.toArray, enc.scanLeft(0L)(_ + _.length), enc.flatten)
+  }
 
   def encode(s: String): Long = synchronized {
     byString.getOrElse(s, {
@@ -46,6 +56,7 @@ final class StringDictionary {
       val code = lo + step
       byString += s -> code
       byCode += code -> s
+      grown += 1
       code
     })
   }
@@ -79,6 +90,20 @@ final class GpuSession(device: Int = 0) extends RelationalCypherSession[GpuTable
   private[opencypher] override val records: GpuRecordsFactory = GpuRecordsFactory()
 
   private[opencypher] override val graphs: GpuGraphFactory = GpuGraphFactory()
+
+  private var stringsAt = -1L
+
+  /** Registers the dictionary as the session's string store (capsmi_session_set_strings) when it has grown since
+    * the last upload: ExprCompiler calls it for every program with a StartsWith / EndsWith / Contains, after the
+    * program's literals are encoded.  Codes are stable, so every store is a superset of the one before. */
+  def syncStrings(): Unit = synchronized {
+    if (stringsAt != dictionary.growth) {
+      val at = dictionary.growth
+      val (codes, offsets, bytes) = dictionary.arrays
+      check(I.capsmi_session_set_strings(handle, codes.length.toLong, codes, offsets, bytes))
+      stringsAt = at
+    }
+  }
 
   /** Query parameters for CAPSMI_X_PARAM (ExprCompiler binds the ones a program references). */
   /** Scalars of one type as (element type, capsmi_value array): the values of a parameter, or the list of

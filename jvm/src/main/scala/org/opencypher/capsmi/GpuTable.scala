@@ -377,8 +377,10 @@ final class GpuTable private (val handle: Pointer)(implicit val session: GpuSess
   * CAPSMI_X_SIZE / CAPSMI_X_INDEX / CAPSMI_X_IN_LIST.  `lists` names the temporary list columns that stand for
   * Range / Labels / Keys operands (GpuTable.withColumns).  The entity functions (:192-227): Type of a variable is
   * the CASE over the header's type flags (get_rel_type's headOption.orNull), StartNodeFunction / EndNodeFunction
-  * are column lookups; Labels and Keys are list columns built by GpuTable.  Shapes the device path does not
-  * evaluate (string matching, other functions, maps, size() of a string) raise NotImplementedException.
+  * are column lookups; Labels and Keys are list columns built by GpuTable.  StartsWith / EndsWith / Contains
+  * (:152-157) are CAPSMI_X_STARTS_WITH / ENDS_WITH / CONTAINS; a program that holds one uploads the session's
+  * string store first (GpuSession.syncStrings).  Shapes the device path does not
+  * evaluate (regular expressions, other functions, maps, size() of a string) raise NotImplementedException.
   */
 final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters: CypherMap,
                               lists: Map[Expr, String] = Map.empty) {
@@ -390,6 +392,8 @@ final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters:
     val out = mutable.ArrayBuffer.empty[Node]
     go(e, out)
     if (params.nonEmpty) bindParams()
+    // the literals and parameters are encoded by now, so the store holds every string the program names
+    if (out.exists(n => n._1 >= Capsmi.X_STARTS_WITH && n._1 <= Capsmi.X_CONTAINS)) table.session.syncStrings()
     out
   }
 
@@ -433,6 +437,9 @@ final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters:
     case Size(x) => list(x, out); out += ((Capsmi.X_SIZE, 0, 0, 0L))
     case ContainerIndex(container, index) => list(container, out); go(index, out); out += ((Capsmi.X_INDEX, 0, 0, 0L))
     case In(lhs, rhs) if listColumn(rhs) => go(lhs, out); list(rhs, out); out += ((Capsmi.X_IN_LIST, 0, 0, 0L))
+    case StartsWith(lhs, rhs) => go(lhs, out); go(rhs, out); out += ((Capsmi.X_STARTS_WITH, 0, 0, 0L))
+    case EndsWith(lhs, rhs) => go(lhs, out); go(rhs, out); out += ((Capsmi.X_ENDS_WITH, 0, 0, 0L))
+    case Contains(lhs, rhs) => go(lhs, out); go(rhs, out); out += ((Capsmi.X_CONTAINS, 0, 0, 0L))
     case p: Property if !header.contains(p) => out += nullOf(p.cypherType)
     case p: Param if !header.contains(p) =>
       out += ((Capsmi.X_PARAM, params.getOrElseUpdate(p.name, params.size), 0, 0L))
