@@ -1182,15 +1182,9 @@ capsmi_status eager_with_range_column(capsmi_table* t, const std::vector<capsmi_
     for (int i = 0; i < 3; ++i) {
         const std::vector<capsmi_expr>& p = *progs[i];
         if (p.empty()) continue;  // the step's literal 1
-        REQUIRE(infer_type(t, (int32_t)p.size(), p.data()) == CAPSMI_I64, CAPSMI_ERR_ILLEGAL_ARGUMENT,
+        REQUIRE(validate_program(t, (int32_t)p.size(), p.data()) == CAPSMI_I64, CAPSMI_ERR_ILLEGAL_ARGUMENT,
                 "range: operands must be Long");
-        if (p.size() == 1 && p[0].op == CAPSMI_X_COL && p[0].arg >= 0 && p[0].arg < (int)t->cols.size()) {
-            opd[i] = t->cols[p[0].arg];
-            continue;
-        }
-        opd[i].data = dev_alloc(sizeof(int64_t) * (n > 0 ? n : 1), s);
-        opd[i].valid = dev_alloc(n > 0 ? n : 1, s);
-        eval_expr(s, t, (int32_t)p.size(), p.data(), P<int64_t>(opd[i].data), P<uint8_t>(opd[i].valid), nullptr);
+        opd[i] = operand_column(s, t, p.data(), 0, (int)p.size() - 1);
     }
     Column c;
     c.name = name;

@@ -19,24 +19,17 @@
 #include <vector>
 
 #include "../../include/capsmi.h"
+#include "capsmi_error.h"
+#include "expr_prog.h"
 
 namespace capsmi {
 
-// ---- errors ---------------------------------------------------------------------
-struct Error : std::runtime_error {
-    capsmi_status code;
-    Error(capsmi_status c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
+// ---- errors (Error and REQUIRE: capsmi_error.h) ------------------------------------
 [[noreturn]] void throw_hip(hipError_t e, const char* what, const char* file, int line);
 #define HIP_CHECK(x)                                                     \
     do {                                                                 \
         hipError_t e__ = (x);                                            \
         if (e__ != hipSuccess) ::capsmi::throw_hip(e__, #x, __FILE__, __LINE__); \
-    } while (0)
-#define REQUIRE(cond, code, msg)                      \
-    do {                                              \
-        if (!(cond)) throw ::capsmi::Error((code), (msg)); \
     } while (0)
 
 // ---- device memory --------------------------------------------------------------
@@ -67,7 +60,6 @@ struct ListStore {
     Buf offsets;                // int64, nlists + 1
     Buf values;                 // int64 words, nvalues
 };
-inline bool is_list_type(int32_t t) { return t >= CAPSMI_LIST_I64 && t <= CAPSMI_LIST_STR; }
 
 // The session's string store (capsmi_session_set_strings): string i has code codes[i] (strictly ascending) and
 // bytes[offsets[i] .. offsets[i+1]).  Replaced as a whole; a pass holds the one it started with.
@@ -478,6 +470,9 @@ void cross_pairs(int64_t nl, int64_t nr, int64_t* out_l, int64_t* out_r, hipStre
 struct ExprArgs;
 void eval_expr(capsmi_session* s, const capsmi_table* t, int32_t nnodes, const capsmi_expr* prog,
                int64_t* out, uint8_t* out_valid, int32_t* out_type);
+// the operand prog[lo .. hi] of a validated program as a column over t's rows: a single COL is read in place,
+// anything else is evaluated into a temporary of the sub-program's static type
+Column operand_column(capsmi_session* s, const capsmi_table* t, const capsmi_expr* prog, int lo, int hi);
 // filter flags: 1 where the predicate is TRUE
 void eval_predicate(capsmi_session* s, const capsmi_table* t, int32_t nnodes, const capsmi_expr* prog,
                     uint8_t* flags);
@@ -657,14 +652,12 @@ void minmax_i64(capsmi_session* s, const int64_t* const* cols, int ncols, int64_
 // widen n input values of width `code` (CAPSMI_IN_* of include/capsmi.h) to 8-byte words
 void widen_words(const void* in, int code, int64_t* out, int64_t n, hipStream_t st);
 
-// expressions: static result type and validation of a postfix program over a table's schema (k_expr.hip)
-int32_t infer_type(const capsmi_table* t, int32_t nn, const capsmi_expr* prog);
+// expressions (k_expr.hip; the arity table, the sub-tree walk and check_program itself: expr_prog.h).
+// check_program over t's column types: throws what it refuses, returns the program's static type
+int32_t validate_program(const capsmi_table* t, int32_t nn, const capsmi_expr* prog);
 // a program with every CAPSMI_X_PARAM replaced by its literal(s) from the session's parameters
 std::vector<capsmi_expr> bind_params(const capsmi_session* s, int32_t nn, const capsmi_expr* prog);
 bool has_params(int32_t nn, const capsmi_expr* prog);
-void validate_program(const capsmi_table* t, int32_t nn, const capsmi_expr* prog);
-// operands the node pops: the one arity table of the opcodes (-1: an opcode the interpreter does not know)
-int expr_pops(const capsmi_expr& x);
 
 // lazy plans (plan.hip): run the plan (a fused kernel when the recogniser matches) and keep the result
 void materialize(capsmi_table* t);

@@ -27,9 +27,7 @@ namespace capsmi {
 
 namespace {
 
-constexpr int kMaxStack = 32;
-constexpr int kMaxCols = 64;
-constexpr int8_t kNull = -1;
+constexpr int8_t kNull = -1;  // kMaxStack, kMaxCols: expr_prog.h
 
 struct ColPtrs {
     const int64_t* data[kMaxCols];
@@ -219,74 +217,12 @@ __global__ void k_eval(const capsmi_expr* __restrict__ prog, int nn, ColPtrs cp,
 
 }  // namespace
 
-// static type of a program (host): literal / column types propagate, comparisons -> BOOL
-int32_t infer_type(const capsmi_table* t, int32_t nn, const capsmi_expr* prog) {
-    std::vector<int> st;
-    for (int i = 0; i < nn; ++i) {
-        const capsmi_expr& x = prog[i];
-        auto pop = [&]() { int v = st.empty() ? -1 : st.back(); if (!st.empty()) st.pop_back(); return v; };
-        switch (x.op) {
-            case CAPSMI_X_COL: st.push_back(t->cols[x.arg].type); break;
-            case CAPSMI_X_LIT: st.push_back(x.type); break;
-            case CAPSMI_X_NULL: st.push_back(x.arg > 0 ? x.arg - 1 : -1); break;  // arg = 1 + declared type
-            case CAPSMI_X_AND: case CAPSMI_X_OR: for (int k = 0; k < x.arg; ++k) pop(); st.push_back(CAPSMI_BOOL); break;
-            case CAPSMI_X_IN: for (int k = 0; k < x.arg + 1; ++k) pop(); st.push_back(CAPSMI_BOOL); break;
-            case CAPSMI_X_NOT: case CAPSMI_X_ISNULL: case CAPSMI_X_ISNOTNULL: pop(); st.push_back(CAPSMI_BOOL); break;
-            case CAPSMI_X_NEG: break;
-            case CAPSMI_X_SIZE: pop(); st.push_back(CAPSMI_I64); break;
-            case CAPSMI_X_STARTS_WITH: case CAPSMI_X_ENDS_WITH: case CAPSMI_X_CONTAINS:
-                pop(); pop(); st.push_back(CAPSMI_BOOL); break;
-            case CAPSMI_X_INDEX: {
-                pop();
-                const int l = pop();
-                st.push_back(l >= CAPSMI_LIST ? l - CAPSMI_LIST : -1);
-                break;
-            }
-            case CAPSMI_X_COALESCE: {
-                int ty = -1;
-                for (int k = 0; k < x.arg; ++k) { int v = pop(); if (v >= 0) ty = v; }
-                st.push_back(ty);
-                break;
-            }
-            case CAPSMI_X_ADD: case CAPSMI_X_SUB: case CAPSMI_X_MUL: {
-                int b = pop(), a = pop();
-                st.push_back((a == CAPSMI_F64 || b == CAPSMI_F64) ? CAPSMI_F64 : CAPSMI_I64);
-                break;
-            }
-            case CAPSMI_X_BITAND: case CAPSMI_X_BITOR: case CAPSMI_X_SHL: case CAPSMI_X_SHRU:
-                pop(); pop(); st.push_back(CAPSMI_I64); break;
-            case CAPSMI_X_CASE: {
-                int ty = pop();  // default, then the values (predicates are BOOL)
-                for (int k = 0; k < x.arg; ++k) {
-                    const int v = pop();
-                    pop();
-                    if (v >= 0) ty = v;
-                }
-                st.push_back(ty);
-                break;
-            }
-            default: pop(); pop(); st.push_back(CAPSMI_BOOL); break;
-        }
-    }
-    const int ty = st.empty() ? -1 : st.back();
-    return ty < 0 ? CAPSMI_I64 : ty;
-}
-
-// operands an opcode pops (-1: unknown opcode, CAPSMI_X_PARAM included: it is bound before anything counts)
-int expr_pops(const capsmi_expr& x) {
-    switch (x.op) {
-        case CAPSMI_X_COL: case CAPSMI_X_LIT: case CAPSMI_X_NULL: return 0;
-        case CAPSMI_X_NOT: case CAPSMI_X_ISNULL: case CAPSMI_X_ISNOTNULL: case CAPSMI_X_NEG: case CAPSMI_X_SIZE: return 1;
-        case CAPSMI_X_AND: case CAPSMI_X_OR: case CAPSMI_X_COALESCE: return x.arg;
-        case CAPSMI_X_IN: return x.arg + 1;
-        case CAPSMI_X_CASE: return 2 * x.arg + 1;
-        case CAPSMI_X_EQ: case CAPSMI_X_NEQ: case CAPSMI_X_LT: case CAPSMI_X_LE: case CAPSMI_X_GT: case CAPSMI_X_GE:
-        case CAPSMI_X_ADD: case CAPSMI_X_SUB: case CAPSMI_X_MUL:
-        case CAPSMI_X_BITAND: case CAPSMI_X_BITOR: case CAPSMI_X_SHL: case CAPSMI_X_SHRU:
-        case CAPSMI_X_INDEX: case CAPSMI_X_IN_LIST:
-        case CAPSMI_X_STARTS_WITH: case CAPSMI_X_ENDS_WITH: case CAPSMI_X_CONTAINS: return 2;
-        default: return -1;
-    }
+// check_program (expr_prog.h) over t's column types
+int32_t validate_program(const capsmi_table* t, int32_t nn, const capsmi_expr* prog) {
+    std::vector<int32_t> types;
+    types.reserve(t->cols.size());
+    for (const Column& c : t->cols) types.push_back(c.type);
+    return check_program(types.data(), (int)types.size(), nn, prog);
 }
 
 bool has_params(int32_t nn, const capsmi_expr* prog) {
@@ -329,7 +265,7 @@ std::vector<capsmi_expr> bind_params(const capsmi_session* s, int32_t nn, const 
             continue;
         }
         const int pops = expr_pops(x);
-        if (pops < 0 && x.op > CAPSMI_X_CONTAINS) throw Error(CAPSMI_ERR_NOT_IMPLEMENTED, "unknown expression op " + std::to_string(x.op));
+        if (pops < 0 && x.op > kLastExprOp) throw Error(CAPSMI_ERR_NOT_IMPLEMENTED, "unknown expression op " + std::to_string(x.op));
         REQUIRE(pops >= 0 && (int)width.size() >= pops, CAPSMI_ERR_ILLEGAL_ARGUMENT,
                 "malformed expression program (stack underflow)");
         capsmi_expr y = x;
@@ -350,234 +286,123 @@ std::vector<capsmi_expr> bind_params(const capsmi_session* s, int32_t nn, const 
     return out;
 }
 
-// Static checks of a program over t's schema: indices, arity, depth, and the operand types of the list opcodes.
-// The type of every stack entry is tracked as infer_type does (-1: unknown, an untyped NULL); a list value may
-// only be the list operand of SIZE / INDEX / IN_LIST, or the whole program (one COL: an alias).
-void validate_program(const capsmi_table* t, int32_t nn, const capsmi_expr* prog) {
-    int maxd = 0;
-    std::vector<int> ty;  // types of the stack entries
-    for (int i = 0; i < nn; ++i) {
-        const capsmi_expr& x = prog[i];
-        switch (x.op) {  // the operand counts of the n-ary opcodes first: they decide what is popped
-            case CAPSMI_X_COL:
-                REQUIRE(x.arg >= 0 && x.arg < (int)t->cols.size(), CAPSMI_ERR_ILLEGAL_ARGUMENT,
-                        "expression column index out of range");
-                REQUIRE(x.arg < kMaxCols, CAPSMI_ERR_NOT_IMPLEMENTED, "expression references column >= 64");
-                break;
-            case CAPSMI_X_AND: case CAPSMI_X_OR: case CAPSMI_X_COALESCE:
-                REQUIRE(x.arg >= 1, CAPSMI_ERR_ILLEGAL_ARGUMENT, "n-ary operator needs >= 1 operand");
-                break;
-            case CAPSMI_X_IN: REQUIRE(x.arg >= 0, CAPSMI_ERR_ILLEGAL_ARGUMENT, "IN arity"); break;
-            case CAPSMI_X_CASE: REQUIRE(x.arg >= 1, CAPSMI_ERR_ILLEGAL_ARGUMENT, "CASE needs >= 1 alternative"); break;
-            default: break;
-        }
-        const int pops = expr_pops(x);
-        if (pops < 0) throw Error(CAPSMI_ERR_NOT_IMPLEMENTED, "unknown expression op " + std::to_string(x.op));
-        REQUIRE((int)ty.size() >= pops, CAPSMI_ERR_ILLEGAL_ARGUMENT, "malformed expression program (stack underflow)");
-        const int* opd = ty.data() + (ty.size() - pops);  // the operands, first pushed first
-        const bool list_op = x.op == CAPSMI_X_SIZE || x.op == CAPSMI_X_INDEX || x.op == CAPSMI_X_IN_LIST;
-        const int list_at = x.op == CAPSMI_X_IN_LIST ? 1 : 0;  // which operand is the list
-        for (int q = 0; q < pops; ++q)
-            REQUIRE(!is_list_type(opd[q]) || (list_op && q == list_at), CAPSMI_ERR_NOT_IMPLEMENTED,
-                    "a list value as an operand of expression op " + std::to_string(x.op) +
-                        " on the device path (only size(), list[i] and IN over a list column take one)");
-        int res = -1;
-        switch (x.op) {
-            case CAPSMI_X_COL: res = t->cols[x.arg].type; break;
-            case CAPSMI_X_LIT: res = x.type; break;
-            case CAPSMI_X_NULL: res = x.arg > 0 ? x.arg - 1 : -1; break;
-            case CAPSMI_X_SIZE: case CAPSMI_X_INDEX: case CAPSMI_X_IN_LIST: {
-                const int l = opd[list_at];
-                REQUIRE(l != CAPSMI_STR, CAPSMI_ERR_NOT_IMPLEMENTED,
-                        "size() / index / IN of a string value is not implemented (string lengths live in the caller's "
-                        "dictionary)");
-                REQUIRE(l < 0 || is_list_type(l), CAPSMI_ERR_ILLEGAL_ARGUMENT, "the operand of a list opcode is not a list");
-                // nothing but a column (or a NULL) yields a list: the node before an IN_LIST is its list operand
-                REQUIRE(x.op != CAPSMI_X_IN_LIST || prog[i - 1].op == CAPSMI_X_COL || prog[i - 1].op == CAPSMI_X_NULL,
-                        CAPSMI_ERR_ILLEGAL_ARGUMENT, "the list operand of IN_LIST must be a list column");
-                if (x.op == CAPSMI_X_INDEX)
-                    REQUIRE(opd[1] < 0 || opd[1] == CAPSMI_I64, CAPSMI_ERR_ILLEGAL_ARGUMENT, "a list index must be a Long");
-                res = x.op == CAPSMI_X_SIZE ? CAPSMI_I64 : (x.op == CAPSMI_X_IN_LIST ? CAPSMI_BOOL : (l < 0 ? -1 : l - CAPSMI_LIST));
-                break;
-            }
-            case CAPSMI_X_STARTS_WITH: case CAPSMI_X_ENDS_WITH: case CAPSMI_X_CONTAINS:
-                for (int q = 0; q < 2; ++q)
-                    REQUIRE(opd[q] < 0 || opd[q] == CAPSMI_STR, CAPSMI_ERR_ILLEGAL_ARGUMENT,
-                            "STARTS WITH / ENDS WITH / CONTAINS take String operands (or a NULL literal that is untyped "
-                            "or typed String)");
-                res = CAPSMI_BOOL;
-                break;
-            case CAPSMI_X_NEG: res = opd[0]; break;
-            case CAPSMI_X_COALESCE: case CAPSMI_X_CASE:
-                for (int q = x.op == CAPSMI_X_CASE ? 1 : 0; q < pops; q += x.op == CAPSMI_X_CASE ? 2 : 1)
-                    if (opd[q] >= 0) res = opd[q];
-                if (x.op == CAPSMI_X_CASE && res < 0) res = opd[pops - 1];
-                break;
-            case CAPSMI_X_ADD: case CAPSMI_X_SUB: case CAPSMI_X_MUL:
-                res = (opd[0] == CAPSMI_F64 || opd[1] == CAPSMI_F64) ? CAPSMI_F64 : CAPSMI_I64;
-                break;
-            case CAPSMI_X_BITAND: case CAPSMI_X_BITOR: case CAPSMI_X_SHL: case CAPSMI_X_SHRU: res = CAPSMI_I64; break;
-            default: res = CAPSMI_BOOL; break;
-        }
-        ty.resize(ty.size() - pops);
-        ty.push_back(res);
-        if ((int)ty.size() > maxd) maxd = (int)ty.size();
-    }
-    REQUIRE(nn == 0 || ty.size() == 1, CAPSMI_ERR_ILLEGAL_ARGUMENT, "expression program must leave one value");
-    REQUIRE(maxd <= kMaxStack, CAPSMI_ERR_NOT_IMPLEMENTED, "expression too deep");
-    REQUIRE(nn <= 1 || !is_list_type(ty[0]), CAPSMI_ERR_NOT_IMPLEMENTED,
-            "an expression that yields a list on the device path (only a column reference does)");
-}
-
 namespace {
 
-void launch_eval(capsmi_session* s, const capsmi_table* t, int32_t nn, const capsmi_expr* prog, int64_t* out,
-                 uint8_t* out_valid, uint8_t* flags);
+int32_t launch_eval(capsmi_session* s, const capsmi_table* t, int32_t nn, const capsmi_expr* prog, int64_t* out,
+                    uint8_t* out_valid, uint8_t* flags);
 
-// first node of the complete sub-expression that ends at prog[end] (postfix)
-int subtree_start(const capsmi_expr* prog, int end) {
-    int want = 1;
-    for (int i = end; i >= 0; --i) {
-        want += expr_pops(prog[i]) - 1;
-        if (want == 0) return i;
-    }
-    throw Error(CAPSMI_ERR_INTERNAL, "malformed expression program");
+// What a node that ran as a pass of its own leaves in the program: a constant, or the BOOL column the pass wrote.
+struct Lowered {
+    int first;        // the node's sub-range of the program is [first .. at]
+    capsmi_expr ref;  // the constant, where there is no column
+    Column res;       // the column (res.data is set)
+};
+
+Lowered lowered_null(int first) {
+    Lowered l{first, {}, {}};
+    l.ref.op = CAPSMI_X_NULL;
+    l.ref.arg = CAPSMI_BOOL + 1;
+    return l;
 }
 
-// The column `res` that a lowered node [p0 .. at] of prog left joins `view`; returns the reference that replaces
-// the node.
-capsmi_expr lend_column(capsmi_table& view, Column res, int32_t nn, const capsmi_expr* prog, int p0, int at,
-                        const char* what) {
-    capsmi_expr ref{};
-    ref.op = CAPSMI_X_COL;
-    if ((int)view.cols.size() < kMaxCols) {
-        ref.arg = (int32_t)view.cols.size();
-        view.cols.push_back(std::move(res));
-    } else {  // a table at the interpreter's column limit: the view lends a column the rest does not read
-        std::vector<bool> used(kMaxCols, false);
-        for (int i = 0; i < nn; ++i)
-            if ((i < p0 || i > at) && prog[i].op == CAPSMI_X_COL) used[prog[i].arg] = true;
-        int slot = 0;
-        while (slot < kMaxCols && used[slot]) ++slot;
-        REQUIRE(slot < kMaxCols, CAPSMI_ERR_NOT_IMPLEMENTED, std::string(what) + " in a program that reads 64 columns");
-        ref.arg = slot;
-        view.cols[slot] = std::move(res);
-    }
-    return ref;
+Lowered lowered_column(capsmi_session* s, int first, int64_t n, const char* name) {
+    Lowered l{first, {}, {}};
+    l.res.name = name;
+    l.res.type = CAPSMI_BOOL;
+    l.res.data = dev_alloc(sizeof(int64_t) * n, s);
+    l.res.valid = dev_alloc(n, s);
+    return l;
 }
 
-// The program's first x IN list (node `at`; its list operand is the column reference before it) leaves the
-// interpreter: the probe sub-program is evaluated into a temporary column (a plain column reference is read
-// where it is), k_listexpr.hip's load-balanced pass produces a temporary BOOL column, and the sub-range
-// [probe .. IN_LIST] of the program becomes a reference to it, over a view of t with that column appended.
-// Further IN_LIST nodes are lowered by the recursion.
-void lower_in_list(capsmi_session* s, const capsmi_table* t, int32_t nn, const capsmi_expr* prog, int at, int64_t* out,
-                   uint8_t* out_valid, uint8_t* flags) {
-    const int64_t n = t->nrows;
+// The sub-range [l.first .. at] of prog becomes l's constant, or a reference to l's column in a view of t that holds
+// it, and the interpreter evaluates the rest over the view.  Further such nodes are lowered by the recursion.
+void replace_span_and_eval(capsmi_session* s, const capsmi_table* t, int32_t nn, const capsmi_expr* prog, int at,
+                           Lowered& l, int64_t* out, uint8_t* out_valid, uint8_t* flags) {
+    capsmi_table view;
+    view.sess = s;
+    view.nrows = t->nrows;
+    view.cols = t->cols;
+    if (l.res.data) {
+        l.ref.op = CAPSMI_X_COL;
+        l.ref.arg = (int32_t)view.cols.size();
+        if (l.ref.arg < kMaxCols) {
+            view.cols.push_back(std::move(l.res));
+        } else {  // a table at the interpreter's column limit: the view lends a column the rest does not read
+            std::vector<bool> used(kMaxCols, false);
+            for (int i = 0; i < nn; ++i)
+                if ((i < l.first || i > at) && prog[i].op == CAPSMI_X_COL) used[prog[i].arg] = true;
+            int slot = 0;
+            while (slot < kMaxCols && used[slot]) ++slot;
+            REQUIRE(slot < kMaxCols, CAPSMI_ERR_NOT_IMPLEMENTED,
+                    std::string(prog[at].op == CAPSMI_X_IN_LIST ? "IN over a list column" : "a string match") +
+                        " in a program that reads 64 columns");
+            l.ref.arg = slot;
+            view.cols[slot] = std::move(l.res);
+        }
+    }
+    std::vector<capsmi_expr> low(prog, prog + l.first);
+    low.push_back(l.ref);
+    low.insert(low.end(), prog + at + 1, prog + nn);
+    launch_eval(s, &view, (int32_t)low.size(), low.data(), out, out_valid, flags);
+}
+
+// x IN list (node `at`; its list operand is the column reference before it): the probe is an operand_column,
+// k_listexpr.hip's load-balanced pass produces the BOOL column.  A NULL list: NULL without a kernel.
+Lowered lower_in_list(capsmi_session* s, const capsmi_table* t, const capsmi_expr* prog, int at) {
+    const auto span = operand_spans(prog, at);  // the probe, the list
     const capsmi_expr& lx = prog[at - 1];
-    const int p1 = at - 2, p0 = subtree_start(prog, p1);
-    capsmi_table view;
-    view.sess = s;
-    view.nrows = n;
-    view.cols = t->cols;
-    std::vector<capsmi_expr> low(prog, prog + p0);
-    capsmi_expr ref{};
-    if (lx.op == CAPSMI_X_NULL) {  // a NULL list: NULL
-        ref.op = CAPSMI_X_NULL;
-        ref.arg = CAPSMI_BOOL + 1;
-    } else {
-        const Column& lc = t->cols[lx.arg];
-        Column probe;
-        if (p0 == p1 && prog[p0].op == CAPSMI_X_COL) {
-            probe = t->cols[prog[p0].arg];
-        } else {
-            probe.data = dev_alloc(sizeof(int64_t) * n, s);
-            probe.valid = dev_alloc(n, s);
-            probe.type = infer_type(t, p1 - p0 + 1, prog + p0);
-            launch_eval(s, t, p1 - p0 + 1, prog + p0, P<int64_t>(probe.data), P<uint8_t>(probe.valid), nullptr);
-        }
-        Column res;
-        res.name = "__in_list";
-        res.type = CAPSMI_BOOL;
-        res.data = dev_alloc(sizeof(int64_t) * n, s);
-        res.valid = dev_alloc(n, s);
-        list_contains(s, probe.d(), probe.v(), probe.type, lc.d(), lc.v(), *lc.list, n, P<int64_t>(res.data),
-                      P<uint8_t>(res.valid));
-        ref = lend_column(view, std::move(res), nn, prog, p0, at, "IN over a list column");
-    }
-    low.push_back(ref);
-    low.insert(low.end(), prog + at + 1, prog + nn);
-    launch_eval(s, &view, (int32_t)low.size(), low.data(), out, out_valid, flags);
+    if (lx.op == CAPSMI_X_NULL) return lowered_null(span[0].first);
+    const Column& lc = t->cols[lx.arg];
+    const Column probe = operand_column(s, t, prog, span[0].first, span[0].second);
+    Lowered l = lowered_column(s, span[0].first, t->nrows, "__in_list");
+    list_contains(s, probe.d(), probe.v(), probe.type, lc.d(), lc.v(), *lc.list, t->nrows, P<int64_t>(l.res.data),
+                  P<uint8_t>(l.res.valid));
+    return l;
 }
 
-// The program's first string match (node `at`, stack [s, p]) leaves the interpreter as an IN_LIST does: an operand
-// that is a literal stays a constant, a plain column reference is read where it is, anything else is evaluated
-// into a temporary column; k_strmatch.hip's pass produces a temporary BOOL column, and the sub-range [s .. node]
-// becomes a reference to it.  A NULL literal operand: NULL without a kernel; two constants: a literal.
-void lower_str_match(capsmi_session* s, const capsmi_table* t, int32_t nn, const capsmi_expr* prog, int at, int64_t* out,
-                     uint8_t* out_valid, uint8_t* flags) {
-    const int64_t n = t->nrows;
-    const int p1 = at - 1, p0 = subtree_start(prog, p1);  // the pattern
-    const int h1 = p0 - 1, h0 = subtree_start(prog, h1);  // the string
-    capsmi_table view;
-    view.sess = s;
-    view.nrows = n;
-    view.cols = t->cols;
-    std::vector<capsmi_expr> low(prog, prog + h0);
-    capsmi_expr ref{};
-    const int span[2][2] = {{h0, h1}, {p0, p1}};
-    bool any_null = false;
-    for (const auto& sp : span) any_null = any_null || (sp[0] == sp[1] && prog[sp[0]].op == CAPSMI_X_NULL);
-    if (any_null) {
-        ref.op = CAPSMI_X_NULL;
-        ref.arg = CAPSMI_BOOL + 1;
-    } else {
-        StrOperand opd[2];
-        Column tmp[2];
-        for (int q = 0; q < 2; ++q) {
-            const int a = span[q][0], b = span[q][1];
-            if (a == b && prog[a].op == CAPSMI_X_LIT) {
-                opd[q].is_const = true;
-                opd[q].code = prog[a].ival;
-                continue;
-            }
-            if (a == b && prog[a].op == CAPSMI_X_COL) {
-                tmp[q] = t->cols[prog[a].arg];
-            } else {
-                tmp[q].data = dev_alloc(sizeof(int64_t) * n, s);
-                tmp[q].valid = dev_alloc(n, s);
-                launch_eval(s, t, b - a + 1, prog + a, P<int64_t>(tmp[q].data), P<uint8_t>(tmp[q].valid), nullptr);
-            }
-            opd[q].data = tmp[q].d();
-            opd[q].valid = tmp[q].v();
+// A string match (node `at`, stack [s, p]): an operand that is a literal stays a constant, anything else is an
+// operand_column; k_strmatch.hip's pass produces the BOOL column.  A NULL literal operand: NULL without a kernel;
+// two constants: a literal.
+Lowered lower_str_match(capsmi_session* s, const capsmi_table* t, const capsmi_expr* prog, int at) {
+    const auto span = operand_spans(prog, at);  // the string, the pattern
+    const int first = span[0].first;
+    for (const auto& sp : span)
+        if (sp.first == sp.second && prog[sp.first].op == CAPSMI_X_NULL) return lowered_null(first);
+    StrOperand opd[2];
+    Column col[2];
+    for (int q = 0; q < 2; ++q) {
+        if (span[q].first == span[q].second && prog[span[q].first].op == CAPSMI_X_LIT) {
+            opd[q].is_const = true;
+            opd[q].code = prog[span[q].first].ival;
+            continue;
         }
-        if (opd[0].is_const && opd[1].is_const) {
-            ref.op = CAPSMI_X_LIT;
-            ref.type = CAPSMI_BOOL;
-            ref.ival = str_match_fold(s, prog[at].op, opd[0].code, opd[1].code) ? 1 : 0;
-        } else {
-            Column res;
-            res.name = "__str_match";
-            res.type = CAPSMI_BOOL;
-            res.data = dev_alloc(sizeof(int64_t) * n, s);
-            res.valid = dev_alloc(n, s);
-            str_match(s, prog[at].op, opd[0], opd[1], n, P<int64_t>(res.data), P<uint8_t>(res.valid));
-            ref = lend_column(view, std::move(res), nn, prog, h0, at, "a string match");
-        }
+        col[q] = operand_column(s, t, prog, span[q].first, span[q].second);
+        opd[q].data = col[q].d();
+        opd[q].valid = col[q].v();
     }
-    low.push_back(ref);
-    low.insert(low.end(), prog + at + 1, prog + nn);
-    launch_eval(s, &view, (int32_t)low.size(), low.data(), out, out_valid, flags);
+    if (opd[0].is_const && opd[1].is_const) {
+        Lowered l{first, {}, {}};
+        l.ref.op = CAPSMI_X_LIT;
+        l.ref.type = CAPSMI_BOOL;
+        l.ref.ival = str_match_fold(s, prog[at].op, opd[0].code, opd[1].code) ? 1 : 0;
+        return l;
+    }
+    Lowered l = lowered_column(s, first, t->nrows, "__str_match");
+    str_match(s, prog[at].op, opd[0], opd[1], t->nrows, P<int64_t>(l.res.data), P<uint8_t>(l.res.valid));
+    return l;
 }
 
-void launch_eval(capsmi_session* s, const capsmi_table* t, int32_t nn, const capsmi_expr* prog, int64_t* out,
-                 uint8_t* out_valid, uint8_t* flags) {
-    validate_program(t, nn, prog);
+// evaluates prog over t's rows; returns its static type
+int32_t launch_eval(capsmi_session* s, const capsmi_table* t, int32_t nn, const capsmi_expr* prog, int64_t* out,
+                    uint8_t* out_valid, uint8_t* flags) {
+    const int32_t type = validate_program(t, nn, prog);
     const int64_t n = t->nrows;
-    if (n == 0) return;
+    if (n == 0) return type;
     for (int i = 0; i < nn; ++i) {  // the first node that runs as a pass of its own; the recursion lowers the rest
-        if (prog[i].op == CAPSMI_X_IN_LIST) return lower_in_list(s, t, nn, prog, i, out, out_valid, flags);
-        if (is_str_match(prog[i].op)) return lower_str_match(s, t, nn, prog, i, out, out_valid, flags);
+        if (prog[i].op != CAPSMI_X_IN_LIST && !is_str_match(prog[i].op)) continue;
+        Lowered l = (prog[i].op == CAPSMI_X_IN_LIST ? lower_in_list : lower_str_match)(s, t, prog, i);
+        replace_span_and_eval(s, t, nn, prog, i, l, out, out_valid, flags);
+        return type;
     }
     ColPtrs cp;
     for (int c = 0; c < kMaxCols; ++c) {
@@ -604,14 +429,25 @@ void launch_eval(capsmi_session* s, const capsmi_table* t, int32_t nn, const cap
     hipLaunchKernelGGL(k_eval, dim3((unsigned)g), dim3(256), 0, s->stream, P<capsmi_expr>(dprog), nn, cp, n, out,
                        out_valid, flags);
     HIP_CHECK(hipGetLastError());
+    return type;
 }
 
 }  // namespace
 
+Column operand_column(capsmi_session* s, const capsmi_table* t, const capsmi_expr* prog, int lo, int hi) {
+    if (lo == hi && prog[lo].op == CAPSMI_X_COL) return t->cols[prog[lo].arg];
+    const int64_t n = t->nrows > 0 ? t->nrows : 1;
+    Column c;
+    c.data = dev_alloc(sizeof(int64_t) * n, s);
+    c.valid = dev_alloc(n, s);
+    c.type = launch_eval(s, t, hi - lo + 1, prog + lo, P<int64_t>(c.data), P<uint8_t>(c.valid), nullptr);
+    return c;
+}
+
 void eval_expr(capsmi_session* s, const capsmi_table* t, int32_t nnodes, const capsmi_expr* prog, int64_t* out,
                uint8_t* out_valid, int32_t* out_type) {
-    if (out_type) *out_type = infer_type(t, nnodes, prog);
-    launch_eval(s, t, nnodes, prog, out, out_valid, nullptr);
+    const int32_t type = launch_eval(s, t, nnodes, prog, out, out_valid, nullptr);
+    if (out_type) *out_type = type;
 }
 
 void eval_predicate(capsmi_session* s, const capsmi_table* t, int32_t nnodes, const capsmi_expr* prog, uint8_t* flags) {

@@ -678,25 +678,15 @@ bool compile_range_pred(const capsmi_table* t, int32_t nn, const capsmi_expr* pr
     if (nn <= 0) return false;
     for (int i = 0; i < nn; ++i)
         if (expr_pops(prog[i]) < 0) return false;  // an opcode the interpreter does not know
-    auto arity = [](const capsmi_expr& x) { return expr_pops(x); };
     // conjunct spans [lo, hi] of the root AND (or the root itself)
-    std::vector<std::pair<int, int>> spans;
-    const capsmi_expr& root = prog[nn - 1];
-    if (root.op == CAPSMI_X_AND) {
-        int end = nn - 2;
-        for (int k = 0; k < root.arg; ++k) {
-            int want = 1, i = end;
-            for (; i >= 0; --i) {
-                want += arity(prog[i]) - 1;
-                if (want == 0) break;
-            }
-            if (i < 0) return false;
-            spans.push_back({i, end});
-            end = i - 1;
+    std::vector<std::pair<int, int>> spans{{0, nn - 1}};
+    if (prog[nn - 1].op == CAPSMI_X_AND) {
+        try {
+            spans = operand_spans(prog, nn - 1);
+        } catch (const Error&) {  // a malformed program: not taken, and refused where it is validated
+            return false;
         }
-        if (end != -1) return false;
-    } else {
-        spans.push_back({0, nn - 1});
+        if (spans.empty() || spans.front().first != 0) return false;
     }
     for (const auto& sp : spans) {
         if (sp.second - sp.first != 2) return false;

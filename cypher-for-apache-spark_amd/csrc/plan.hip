@@ -129,7 +129,7 @@ std::vector<const char*> cstrs(const std::vector<std::string>& v) {
     return o;
 }
 
-// operands of a node of a validated program (the one table of k_expr.hip)
+// operands of a node of a validated program (the one table of expr_prog.h)
 int arity(const capsmi_expr& x) {
     const int k = expr_pops(x);
     REQUIRE(k >= 0, CAPSMI_ERR_NOT_IMPLEMENTED, "unknown expression op " + std::to_string(x.op));
@@ -1866,26 +1866,10 @@ struct Pred {                     // one conjunct; COL args index `names`
     Names names;
 };
 
-// first node of the complete sub-expression that ends at prog[end] (postfix)
-int subtree_start(const std::vector<capsmi_expr>& prog, int end) {
-    int want = 1;
-    for (int i = end; i >= 0; --i) {
-        want += arity(prog[i]) - 1;
-        if (want == 0) return i;
-    }
-    throw Error(CAPSMI_ERR_INTERNAL, "malformed expression program");
-}
-
+// the conjuncts of prog[lo .. hi], nested ANDs flattened, in the program's order
 void conjuncts(const std::vector<capsmi_expr>& prog, int lo, int hi, std::vector<std::vector<capsmi_expr>>& out) {
     if (prog[hi].op == CAPSMI_X_AND) {
-        std::vector<std::pair<int, int>> kids;
-        int end = hi - 1;
-        for (int k = 0; k < prog[hi].arg; ++k) {
-            const int st = subtree_start(prog, end);
-            kids.push_back({st, end});
-            end = st - 1;
-        }
-        for (auto it = kids.rbegin(); it != kids.rend(); ++it) conjuncts(prog, it->first, it->second, out);
+        for (const auto& kid : operand_spans(prog.data(), hi)) conjuncts(prog, kid.first, kid.second, out);
     } else {
         out.emplace_back(prog.begin() + lo, prog.begin() + hi + 1);
     }
@@ -2567,9 +2551,8 @@ capsmi_status capsmi_with_columns(capsmi_table* t, int32_t ncols, const capsmi_e
             REQUIRE(cols[i].nnodes == 0 || cols[i].prog, CAPSMI_ERR_ILLEGAL_ARGUMENT, "null program");
             std::vector<capsmi_expr> prog(cols[i].prog, cols[i].prog + cols[i].nnodes);
             if (has_params(cols[i].nnodes, cols[i].prog)) prog = bind_params(t->sess, cols[i].nnodes, cols[i].prog);
-            validate_program(t, (int32_t)prog.size(), prog.data());
             p->a.push_back(cols[i].name);
-            Column c = schema_col(cols[i].name, infer_type(t, (int32_t)prog.size(), prog.data()), true);
+            Column c = schema_col(cols[i].name, validate_program(t, (int32_t)prog.size(), prog.data()), true);
             p->progs.push_back(std::move(prog));
             int j = -1;
             for (size_t q = 0; q < sch.size(); ++q) if (sch[q].name == c.name) j = (int)q;
@@ -2638,8 +2621,7 @@ capsmi_status capsmi_with_range_column(capsmi_table* t, int32_t from_nnodes, con
             REQUIRE(nn[i] > 0 ? pr[i] != nullptr : i == 2, CAPSMI_ERR_ILLEGAL_ARGUMENT, "range: null or empty operand program");
             std::vector<capsmi_expr> prog(pr[i], pr[i] + nn[i]);
             if (has_params(nn[i], pr[i])) prog = bind_params(t->sess, nn[i], pr[i]);
-            validate_program(t, (int32_t)prog.size(), prog.data());
-            REQUIRE(prog.empty() || infer_type(t, (int32_t)prog.size(), prog.data()) == CAPSMI_I64,
+            REQUIRE(validate_program(t, (int32_t)prog.size(), prog.data()) == CAPSMI_I64,
                     CAPSMI_ERR_ILLEGAL_ARGUMENT, "range: operands must be Long");
             p->progs.push_back(std::move(prog));
         }

@@ -106,7 +106,13 @@ typedef struct {
  * that the pattern-matching path needs: column refs (Var/Property/HasLabel/HasType/StartNode/EndNode
  * resolve to columns, :97-105), literals and params (:86-92, :111-117), Equals (:120), Not (:121),
  * IsNull/IsNotNull (:122-123), Ands/Ors (:132-136), In (:138-145), < <= > >= (:147-150), arithmetic.
- * Evaluation follows SQL three-valued logic; Filter keeps rows whose value is TRUE. */
+ * Evaluation follows SQL three-valued logic; Filter keeps rows whose value is TRUE.
+ * Static types: a column or literal has its own, an untyped NULL none, comparisons and predicates are BOOL.
+ * CAPSMI_X_COALESCE and CAPSMI_X_CASE take the type of their first typed alternative (CASE: v1 .. v_arg, then
+ * the default); that is the type of a column computed from one.  Where the typed alternatives disagree the
+ * value is "mixed", as is + - * or NEG over it: accepted as a value or a comparison operand, but
+ * CAPSMI_ERR_ILLEGAL_ARGUMENT where one type is demanded, that is as an operand of CAPSMI_X_STARTS_WITH /
+ * ENDS_WITH / CONTAINS, as the index of CAPSMI_X_INDEX, or as the list operand of a list opcode. */
 enum {
     CAPSMI_X_COL = 0,      /* push column `arg` (index into the input table) */
     CAPSMI_X_LIT = 1,      /* push literal of type `type`, bits in `ival` */

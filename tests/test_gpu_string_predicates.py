@@ -220,6 +220,44 @@ def test_operands_that_are_expressions(session, knobs, mode):
     _assert_same(got["ca"], [ref_match("starts_with", x if r < 150 else "ba", y) for r, (x, y) in enumerate(zip(s, p))])
 
 
+def test_in_list_and_contains_in_a_table_at_the_column_limit(session):
+    """64 columns, the interpreter's limit, and 300 rows (one block of 256 and a part of one): x IN xs and s CONTAINS 'a'
+    under one AND whose third operand reads the other 61 columns.  Neither lowered node can append its result
+    column, so each borrows a slot the rest of the program does not read (its own operands' columns)."""
+    from functools import reduce
+    from capsmi import ColumnData, expr
+    from capsmi.expr import Ands, BinOp, Col, Contains, InList, Lit
+    from list_expr_ref import ref_in_list
+    rng = np.random.default_rng(64)
+    n = 300
+    s, _ = _random_rows()
+    s = s[:n]
+    pv = rng.random(n) >= 0.2
+    p = [int(x) if ok else None for x, ok in zip(rng.integers(0, 9, n), pv)]
+    lists = [rng.integers(0, 9, int(rng.integers(0, 6))).tolist() for _ in range(n)]
+    lv = rng.random(n) >= 0.2
+    offs = np.concatenate([[0], np.cumsum([len(x) for x in lists])]).astype(np.int64)
+    cols = [ColumnData("id", expr.I64, np.arange(n, dtype=np.int64)), _str_col(session, "s", s),
+            ColumnData("p", expr.I64, np.array([0 if x is None else x for x in p], dtype=np.int64), pv)]
+    cols += [ColumnData(f"f{k}", expr.I64, np.full(n, k, dtype=np.int64)) for k in range(60)]
+    t = session.table(cols).add_list_column_csr("xs", expr.I64, offs, np.array([v for x in lists for v in x], dtype=np.int64),
+                                                lv.astype(np.uint8))
+    assert len(t.physicalColumns) == 64
+    others = reduce(lambda a, b: BinOp("+", a, b), [Col("id")] + [Col(f"f{k}") for k in range(60)])  # id + 0 + .. + 59
+    pred = Ands((InList(Col("p"), Col("xs")), Contains(Col("s"), Lit("a")), BinOp(">=", others, Lit(1770 + 40))))
+
+    def and3(*v):
+        return False if False in v else None if None in v else True
+
+    want = [and3(ref_in_list(p[r], lists[r] if lv[r] else None, int), ref_match("contains", s[r], "a"), r >= 40)
+            for r in range(n)]
+    assert want.count(True) > 10 and want.count(None) > 10 and want[:40].count(False) == 40
+    out = t.withColumns((pred, "m"))
+    _assert_same(_values(session, out, "m"), want)
+    assert _values(session, out, "f59") == [59] * n and _values(session, out, "s") == s  # the lent slots are the view's
+    assert _values(session, t.filter(pred), "id") == [r for r in range(n) if want[r] is True]
+
+
 # ---- the side taken under auto ---------------------------------------------------------------------
 def test_auto_takes_the_dictionary_side_from_as_many_rows_as_strings(session):
     from capsmi import _lib
@@ -244,6 +282,20 @@ def test_auto_takes_the_dictionary_side_from_as_many_rows_as_strings(session):
 
 
 # ---- errors ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("op", OPS)
+def test_a_coalesce_of_string_and_long_is_no_string_operand(session, op):
+    """Whichever alternative comes first: the typed alternatives disagree, so the operand has no one type."""
+    from capsmi._lib import IllegalArgumentException
+    from capsmi.expr import Coalesce, Col, Lit
+    t = _table(session, s=["a", "b"])
+    for alts in ((Col("s"), Col("id")), (Col("id"), Col("s"))):
+        with pytest.raises(IllegalArgumentException):
+            t.withColumns((_cls(op)(Coalesce(alts), Lit("a")), "x"))
+        with pytest.raises(IllegalArgumentException):
+            t.filter(_cls(op)(Col("s"), Coalesce(alts)))
+    t.withColumns((Coalesce((Col("s"), Col("id"))), "x"))  # a value like any other where no type is demanded
+
+
 @pytest.mark.parametrize("op", OPS)
 def test_operand_types_are_checked_when_the_node_is_built(session, op):
     from capsmi import expr

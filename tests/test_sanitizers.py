@@ -2,9 +2,12 @@
 - the oracle's C restatement (oracle/rmat.c, closed.c) under AddressSanitizer + UndefinedBehaviorSanitizer,
   every closed form against enumeration (tests/sanitize/oracle_san.c);
 - the CSV reader's host half (csrc/csv_parse.h: chunking, the threaded parser, Spark row ids) under
-  ASan + UBSan and under ThreadSanitizer, 1 vs 2 / 3 / 8 threads equal (tests/sanitize/csv_san.cpp).
+  ASan + UBSan and under ThreadSanitizer, 1 vs 2 / 3 / 8 threads equal (tests/sanitize/csv_san.cpp);
+- the expression programs' host half (csrc/expr_prog.h: the arity table, the sub-tree walk, check_program) under
+  ASan + UBSan, replaying the programs recorded in tests/golden/expr_programs.json (tests/sanitize/expr_san.cpp).
 GPU code is not instrumented (GPU sanitizers are unavailable on this pool); the harnesses are built from the
 sources into a temporary directory, nothing is committed."""
+import json
 import os
 import shutil
 import subprocess
@@ -70,3 +73,20 @@ def test_csv_reader_under_tsan(tmp_path):
             "-o", exe], tmp_path)
     out = _run(exe, "60")
     assert "0 mismatches" in out, out
+
+
+def test_expression_programs_under_asan_ubsan(tmp_path):
+    """check_program reproduces, record for record and message for message, what validate_program and infer_type
+    gave when the fixture was recorded, but for the records in which a COALESCE / CASE of disagreeing types feeds
+    an operand that demands one type: every one of those is refused now, and nothing else differs."""
+    fixture = os.path.join(ROOT, "tests", "golden", "expr_programs.json")
+    with open(fixture) as f:
+        records = json.load(f)["records"]
+    mixed = sum(1 for r in records if r["mixed_demand"])
+    assert mixed > 0 and any(r["mixed_demand"] and r["status"] == 0 for r in records)
+    exe = str(tmp_path / "expr_san")
+    _build(["g++", *ASAN, "-std=c++17", os.path.join(SAN, "expr_san.cpp"), "-o", exe], tmp_path)
+    out = _run(exe, fixture)
+    assert f"{len(records)} records" in out, out
+    assert f"\n{mixed} mixed refused" in out, out
+    assert "\n0 mismatches" in out, out
