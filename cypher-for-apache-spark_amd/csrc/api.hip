@@ -503,6 +503,9 @@ bool apply(Config& c, const std::string& name, const char* v) {
     } else if (name == "CAPSMI_POOL") {
         if (!parse_choice(v, {"split", "pairs"}, k)) return false;
         c.pool_split = k == 0;
+    } else if (name == "CAPSMI_HOP2_EXCHANGE") {
+        if (!parse_choice(v, {"on", "off"}, k)) return false;
+        c.hop2_exchange = k == 0;
     } else if (name == "CAPSMI_TRI_BUILD") {
         if (!parse_choice(v, {"direct", "sorted"}, k)) return false;
         c.tri_sorted_build = k == 1;
@@ -548,7 +551,8 @@ const std::pair<const char*, const char*> kKnobs[] = {
     {"CAPSMI_TRI_DEG_SAMPLE", "0"},  {"CAPSMI_TRI_SPLIT", "1"},      {"CAPSMI_TRI_VMODE_T", "256"},
     {"CAPSMI_UND", "part"},          {"CAPSMI_VL_BITS", "8"},        {"CAPSMI_VL_SUBLOG", "-1"},
     {"CAPSMI_VL_F2", "0"},           {"CAPSMI_COLL_CHUNK", "67108864"}, {"CAPSMI_INGEST_THREADS", "0"},
-    {"CAPSMI_HOP2", "auto"},         {"CAPSMI_POOL", "split"},       {"CAPSMI_STR_MATCH", "auto"}};
+    {"CAPSMI_HOP2", "auto"},         {"CAPSMI_POOL", "split"},       {"CAPSMI_STR_MATCH", "auto"},
+    {"CAPSMI_HOP2_EXCHANGE", "on"}};
 }  // namespace
 
 Config config_from_env() {

@@ -147,6 +147,9 @@ struct Config {
     bool pool_split = true;       // CAPSMI_POOL = split | pairs: the format of the pass-1 pool that the pool hops walk --
                                   //   target and source words in two arrays per chunk, so hop 1 reads 4 B per
                                   //   relationship, or 8-byte pairs (every other pool is pairs)
+    bool hop2_exchange = true;    // CAPSMI_HOP2_EXCHANGE = on | off: hop 2 over the split pool lets the blocks that share a
+                                  //   target slice exchange their C bits through the global C while they walk (off: each
+                                  //   block finds every target of its share for itself; k_part.hip k_pool_hop2)
     bool tri_sorted_build = false;  // CAPSMI_TRI_BUILD = sorted: the sort-oriented trigraph build (above 2^24 ids)
     int tri_deg_sample = 0;       // CAPSMI_TRI_DEG_SAMPLE: 1 in k relationships for the degree order (0: auto)
     bool tri_split = true;        // CAPSMI_TRI_SPLIT = 0: the combined (not direction-split) triangle walks

@@ -1128,8 +1128,14 @@ __global__ void __launch_bounds__(kBlock) k_hop_2d(PairOut pairs, const int64_t*
 // The pool is grouped by target slice, so a block keeps the slice's target bitmap in LDS while it walks its
 // share of the slice's chunks (part::walk_chunks_n); several blocks may share a slice, so the flush ORs.
 constexpr int kPoolBlock = 1024;
+// Hop 2's exchange (k_pool_hop2<true, XW>): windows of 256 words a wave takes per chunk it enters.  1 = the block
+// covers its slice every 64 chunks, about 8 times per 4-Mi share.
+constexpr int kPoolXchgWindows = 1;
 
-// move the LDS slice j out through `mask` and clear it
+// move the LDS slice j out through `mask` and clear it.  SKIP: a word whose bits the global word already holds
+// (another block's, or this block's own exchange) costs a plain load instead of an atomic; a stale load lacks
+// bits and never has one too many (a set bit of an OR is final), so it costs the atomic and nothing else.
+template <bool SKIP = false>
 __device__ __forceinline__ void pool_flush(uint32_t* tl, uint32_t* g, int j, int64_t gwords, BitV mask) {
     const int64_t w0 = (int64_t)j * kSliceWords;
     for (int i = threadIdx.x; i < kSliceWords; i += kPoolBlock) {
@@ -1138,6 +1144,7 @@ __device__ __forceinline__ void pool_flush(uint32_t* tl, uint32_t* g, int j, int
         const int64_t gw = w0 + i;
         if (!v || gw >= gwords) continue;
         if (!mask.full) v &= mask.w[gw];
+        if (SKIP && v) v &= ~g[gw];
         if (v) atomicOr(&g[gw], v);
     }
 }
@@ -1196,10 +1203,23 @@ __global__ void __launch_bounds__(kPoolBlock) k_pool_hop1(ChunkWalk cw, BitV tma
 // lines at C3).  A target tested in step i + 1 may be set a moment later by step i - 1 or i: that costs one
 // gather too many and never a wrong bit, since C is an OR.  Four waves per SIMD is what one block per CU uses,
 // so the split instantiation may take 128 VGPRs for its three steps in flight.
-template <bool SPLIT>
+//
+// XW > 0 (split pool only, CAPSMI_HOP2_EXCHANGE): the blocks that walk one slice exchange their C bits through
+// the global C while they walk.  A block starts a share with an empty LDS slice and would gather once for every
+// distinct target of the share, also for the ones another block has long resolved; at C3 about 37 of the 256
+// blocks walk slice 0.  A set bit of the global C is final and true, so a block may OR global words into its
+// LDS slice and publish its own new bits at any moment, with no barrier and no ordering: a stale read costs a
+// gather and never a wrong bit.  The walker hands a wave XW windows of 256 words per chunk it enters
+// (part::walk_chunks_st_pipe); per word the lane ORs the global word into LDS and publishes what LDS holds
+// beyond it.  The loads carry sc1 (what an agent-scope relaxed atomic load compiles to), so a word is not
+// served for the rest of the kernel from a line the XCD's L2 took before other XCDs' atomics.  LDS also holds
+// bits that are no results (the preset ~c_ok): everything that leaves, leaves through cmask.  A visit also
+// starts from the global words (begin), and its flush skips the words that are already out.
+template <bool SPLIT, int XW = 0>
 __global__ void __launch_bounds__(kPoolBlock, SPLIT ? 4 : 8)
     k_pool_hop2(ChunkWalk cw, const uint32_t* __restrict__ X1, const uint32_t* __restrict__ X2, BitV cmask,
                 uint32_t* __restrict__ C, int64_t gwords) {
+    static_assert(SPLIT || XW == 0, "the exchange rides on the pipelined walk of the split pool");
     extern __shared__ __attribute__((aligned(16))) uint32_t tl[];
     for (int k = threadIdx.x; k < kSliceWords; k += kPoolBlock) tl[k] = 0;
     __syncthreads();
@@ -1227,16 +1247,57 @@ __global__ void __launch_bounds__(kPoolBlock, SPLIT ? 4 : 8)
             if (ok) lds_set(tl, off(k));
         }
     };
-    auto flush = [&](int j) { pool_flush(tl, C, j, gwords, cmask); };
+    auto flush = [&](int j) { pool_flush<(XW > 0)>(tl, C, j, gwords, cmask); };
     auto begin = [&](int j) {
+        if constexpr (XW > 0) {  // the preset, and what is out already: free and exact, for a block that comes late
+            const int64_t w0 = (int64_t)j * kSliceWords;
+            for (int i = threadIdx.x; i < kSliceWords; i += kPoolBlock) {
+                const int64_t gw = w0 + i;
+                uint32_t v = cmask.full ? 0u : 0xFFFFFFFFu;
+                if (gw < gwords) v = (cmask.full ? 0u : ~cmask.w[gw]) | C[gw];
+                tl[i] = v;
+            }
+            return;
+        }
         if (cmask.full) return;
         const int64_t w0 = (int64_t)j * kSliceWords;
         for (int i = threadIdx.x; i < kSliceWords; i += kPoolBlock)
             tl[i] = w0 + i < gwords ? ~cmask.w[w0 + i] : 0xFFFFFFFFu;
     };
+    // The exchange: the lane's four words of the window in flight (xg), of c_ok too where it is partial (xm), and
+    // the window they belong to.  Buffer loads, so the words past the bitmap's end in the last slice read as zero.
+    typedef uint32_t v4u32 __attribute__((ext_vector_type(4)));
+    [[maybe_unused]] v4u32 xg = {0u, 0u, 0u, 0u}, xm = {0u, 0u, 0u, 0u};
+    [[maybe_unused]] uint32_t xcur = 0;
+    auto xword = [&]() { return xcur * (uint32_t)kXchgWords + 4u * (threadIdx.x & 63u); };  // in the slice
+    auto xissue = [&](uint32_t win, int j) {
+        const __amdgpu_buffer_rsrc_t cr = __builtin_amdgcn_make_buffer_rsrc(
+            C, (short)0, (int)(gwords * (int64_t)sizeof(uint32_t)), 0x00020000);
+        xcur = win;
+        const uint32_t off = ((uint32_t)j * (uint32_t)kSliceWords + xword()) * 4u;
+        xg = __builtin_amdgcn_raw_buffer_load_b128(cr, off, 0, 16);  // sc1: not from the L1, nor a stale L2 line
+        if (!cmask.full) {
+            const __amdgpu_buffer_rsrc_t mr = __builtin_amdgcn_make_buffer_rsrc(
+                const_cast<uint32_t*>(cmask.w), (short)0, (int)(gwords * (int64_t)sizeof(uint32_t)), 0x00020000);
+            xm = __builtin_amdgcn_raw_buffer_load_b128(mr, off, 0, 0);
+        }
+    };
+    auto xconsume = [&](int j) {
+        const uint32_t w = xword();
+        const int64_t gw = (int64_t)j * kSliceWords + w;
+        const v4u32 l = *reinterpret_cast<const v4u32*>(&tl[w]);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const uint32_t in = xg[e] & ~l[e];
+            if (in) atomicOr(&tl[w + e], in);
+            uint32_t out = l[e] & ~xg[e];  // may hold preset bits: out through c_ok only
+            if (!cmask.full) out &= xm[e];
+            if (out && gw + e < gwords) atomicOr(&C[gw + e], out);
+        }
+    };
     if (SPLIT) {
         constexpr uint32_t kOff = (1u << kSliceBits) - 1u;  // (T word - slice base) & kOff drops the loop bit too
-        walk_chunks_st_pipe<kPoolBlock>(
+        walk_chunks_st_pipe<kPoolBlock, XW>(
             cw,
             [&](const uint32_t (&tw)[kWalkItems], uint32_t valid, int j) {
                 const uint32_t tbase = (uint32_t)j << kSliceBits;
@@ -1274,7 +1335,7 @@ __global__ void __launch_bounds__(kPoolBlock, SPLIT ? 4 : 8)
                         if (((loops >> k) & 1u) && gbit(X2, sw[k])) lds_set(tl, (tw[k] - tbase) & kOff);
                 }
             },
-            flush, begin);
+            flush, begin, xissue, xconsume);
     } else {
         walk_chunks_n<kPoolBlock>(
             cw,
@@ -1467,12 +1528,15 @@ static part::ChunkWalk chunk_walk(const ChunkPart& cp) {
 }
 
 // Grid of the pool hops: one 1024-lane block per CU (64 KiB of LDS), fewer for small tables so that a
-// block's share stays at 16 chunks or more.  More blocks cut the slices into more shares, each of which meets a
-// target for the first time once more (scripts/pool_reads_model.py: 0.05 X reads per relationship and 0.65-0.68
-// of the source lines at 256 shares of C3, 0.08 and 0.81-0.84 at 512), and every share pays a 64 KiB flush per
-// slice it touches.  Measured at C3 (plain bench, alternating libraries on one box): two blocks per CU 8.89 /
-// 8.99 ms per step, one 8.70 / 8.67 ms.  The X gathers' latency is hidden inside the one block instead: hop 2
-// over a split pool keeps three steps per wave in flight (part::walk_chunks_st_pipe).
+// block's share stays at 16 chunks or more.  Two blocks per CU, measured at C3 (plain bench, libraries alternating
+// on one box, six runs each, profiles/r15_c3_ab.json): 7.445 ms per step against 7.247 ms for one, and 7.380 ms
+// for the parent without the exchange.  Round 7 measured the same loss (8.89 / 8.99 against 8.70 / 8.67 ms) and
+// put it down to the first encounters, of which a slice cut into twice the shares has more.  With hop 2's
+// exchange (k_pool_hop2<true, XW>) a share no longer pays for the targets other shares have resolved, and two
+// blocks per CU still lose 0.2 ms: so it is not the first encounters alone.  What is left, not told apart: a 64 KiB
+// begin and flush per share and slice, twice the open ends, and hop 2's 128 VGPRs, which let one block run per
+// CU, so the second half of the grid runs as a second round and not beside the first.  The X gathers' latency is
+// hidden inside the one block: three steps per wave in flight (part::walk_chunks_st_pipe).
 constexpr int kPoolBlocksPerCU = 1;
 constexpr int64_t kPoolMinShare = 16 * (int64_t)part::kCh;  // pairs
 static unsigned pool_grid(const capsmi_session* s, const ChunkPart& cp) {
@@ -1652,13 +1716,15 @@ void relpart_hop2(capsmi_session* s, RelPart& rp, const capsmi_bitmap* c, const 
         if (rp.sel == 0) {
             using namespace part;
             const size_t lds = sizeof(uint32_t) * kSliceWords;
-            auto k = rp.cp.split ? k_pool_hop2<true> : k_pool_hop2<false>;
+            const bool xchg = rp.cp.split && s->cfg.hop2_exchange;
+            auto k = xchg ? k_pool_hop2<true, kPoolXchgWindows> : rp.cp.split ? k_pool_hop2<true> : k_pool_hop2<false>;
             allow_lds(k, lds);
             KernelTimer kt(s, "hop2");
             hipLaunchKernelGGL(k, dim3(pool_grid(s, rp.cp)), dim3(kPoolBlock), lds, s->stream, chunk_walk(rp.cp),
                                X1, X2, cv, C, c->nwords);
             HIP_CHECK(hipGetLastError());
             s->routes["hop2_pool"] += 1;
+            if (xchg) s->routes["hop2_exchange"] += 1;
             return;
         }
         relpart_cells(s, rp);

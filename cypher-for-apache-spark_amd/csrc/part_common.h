@@ -403,9 +403,30 @@ __device__ __forceinline__ uint32_t uniform_word(const void* p, int64_t i) {
 // no load's destination is copied while the load is in flight.
 // `test` sees the consumer's state up to two steps old (S(i+1) runs before Set(i)): the consumer must be one for
 // which a stale "needed" costs work and never a wrong result.
-template <int BLK, class Test, class Gather, class Set, class Flush, class Begin = NoBegin>
+//
+// XW > 0: the blocks that share a slice exchange their state while they walk it, without a barrier.  The slice's
+// words are cut into kXchgWins windows of kXchgWords (four per lane).  A wave that enters a new chunk (a
+// wave-uniform event, once per 16 steps of a full chunk) takes XW windows, starting at XW times its grab index
+// less the waves' first grabs, so the block's grabs rotate over the whole slice every kXchgWins / XW chunks, from
+// window 0 at every visit (a wave that grabs twice before another's first starts elsewhere: any window is good).
+// More windows for the short visits of a shard or a small table (8 * kXchgWins / chunks of the visit, up to 8)
+// were measured and not kept: DESIGN §9 round 15.
+// One window per step: xissue(win, j) loads at the end of an iteration, behind the step's own loads, and
+// xconsume(j) runs at the end of the next one, behind Set's wait for gathers that were issued later -- vector
+// loads return in order, so the window has arrived and the consumer's loads add no wait of their own.  A
+// window still pending when the wave's steps end is dropped (the flush publishes everything anyway).  XW == 0
+// compiles to the walk without any of this.
+struct NoXchg {
+    __device__ void operator()(uint32_t, int) const {}
+    __device__ void operator()(int) const {}
+};
+constexpr int kXchgWords = 64 * 4;                      // one 16-byte load per lane
+constexpr int kXchgWins = kSliceWords / kXchgWords;     // 64
+template <int BLK, int XW = 0, class Test, class Gather, class Set, class Flush, class Begin = NoBegin,
+          class XIssue = NoXchg, class XConsume = NoXchg>
 __device__ void walk_chunks_st_pipe(const ChunkWalk& cw, Test test, Gather gather, Set set, Flush flush,
-                                    Begin begin = Begin()) {
+                                    Begin begin = Begin(), XIssue xissue = XIssue(), XConsume xconsume = XConsume()) {
+    static_assert(XW >= 0 && XW <= kXchgWins && (kXchgWins % (XW ? XW : 1)) == 0, "windows per grab");
     constexpr int kLd = kWalkItems / 4;
     constexpr uint32_t kStep = 64 * kWalkItems;  // pairs per wave step
     constexpr uint32_t kOut = 0x80000000u;       // byte offset past any chunk
@@ -437,6 +458,8 @@ __device__ void walk_chunks_st_pipe(const ChunkWalk& cw, Test test, Gather gathe
         // the current is entered and its fill one step later, both used only at the change
         uint32_t phys = 0, fill = 0, o = 0, pn = 0, fn = 0;
         bool fpend = false;
+        [[maybe_unused]] uint32_t xwin = 0, xleft = 0;  // XW: the next window to take, how many of this grab's are left
+        [[maybe_unused]] bool xpend = false;            //     a window is in flight
         uint32_t tn = grab();
         bool live = tn < nq, nlive = false;
         if (live) {
@@ -464,6 +487,10 @@ __device__ void walk_chunks_st_pipe(const ChunkWalk& cw, Test test, Gather gathe
                     o = 0;
                     live = nlive;
                     if (live) {
+                        if constexpr (XW > 0) {  // entering the chunk of grab tn (the waves' first grabs enter none)
+                            xwin = ((tn - (uint32_t)(BLK / 64)) * (uint32_t)XW) & (uint32_t)(kXchgWins - 1);
+                            xleft = XW;
+                        }
                         tn = grab();
                         nlive = tn < nq;
                         if (nlive) {
@@ -510,16 +537,30 @@ __device__ void walk_chunks_st_pipe(const ChunkWalk& cw, Test test, Gather gathe
         };
         auto X = [&](int s) __attribute__((always_inline)) { gather(sw[s], tw[s], need[s], xw[s]); };
         auto Z = [&](int s) __attribute__((always_inline)) { set(sw[s], tw[s], xw[s], need[s], j); };
+        auto E = [&]() __attribute__((always_inline)) {  // wave-uniform branches
+            if constexpr (XW > 0) {
+                if (xpend) {
+                    xconsume(j);
+                    xpend = false;
+                }
+                if (xleft) {
+                    xissue(uni(xwin), j);
+                    xwin = (xwin + 1u) & (uint32_t)(kXchgWins - 1);
+                    --xleft;
+                    xpend = true;
+                }
+            }
+        };
         T(0, next());
         if (st[0].live) {  // wave-uniform
             S(0);
             T(1, next());
             for (;;) {  // Set(i) ends an iteration; a dead step i + 1 means every load issued since is dead too
-                X(0); S(1); T(2, next()); Z(0);
+                X(0); S(1); T(2, next()); Z(0); E();
                 if (!st[1].live) break;
-                X(1); S(2); T(0, next()); Z(1);
+                X(1); S(2); T(0, next()); Z(1); E();
                 if (!st[2].live) break;
-                X(2); S(0); T(1, next()); Z(2);
+                X(2); S(0); T(1, next()); Z(2); E();
                 if (!st[0].live) break;
             }
         }
