@@ -23,11 +23,17 @@ relationship's source and target columns.
 String matching (:152-157): StartsWith, EndsWith and Contains over String operands, matched byte-wise on the
 device against the session's string store (``Session.sync_strings``).
 
+Numeric functions: Divide (:186, ``BinOp("/")``), Sqrt / Log / Log10 / Exp / Abs / Ceil / Floor / Round / Sign
+(:249-260), ToFloat and ToInteger over numbers (:229-231), and ``E`` (:253), the literal ``Math.E``.  A NULL operand
+gives NULL; the rules are those of the Spark 2.2.1 Column calls the mapper makes (include/capsmi.h, CAPSMI_X_DIV ..
+CAPSMI_X_TO_INTEGER).
+
 ``compile_program`` lowers a tree to the postfix ``capsmi_expr`` program of include/capsmi.h.
 """
 from __future__ import annotations
 
 import ctypes
+import math
 import struct
 from dataclasses import dataclass
 from typing import Callable, Sequence, Tuple, Union
@@ -44,9 +50,12 @@ X_BITAND, X_BITOR, X_SHL, X_SHRU, X_CASE, X_PARAM = range(20, 26)
 X_SIZE, X_INDEX, X_IN_LIST = range(26, 29)  # list operands: a Col of a list column
 X_STARTS_WITH, X_ENDS_WITH, X_CONTAINS = range(29, 32)  # String operands; they read the session's string store
 STRING_MATCH_OPS = (X_STARTS_WITH, X_ENDS_WITH, X_CONTAINS)
+# 32..39 are unassigned; the numeric block starts at 40
+(X_DIV, X_SQRT, X_LOG, X_LOG10, X_EXP, X_ABS, X_CEIL, X_FLOOR, X_ROUND, X_SIGN, X_TO_FLOAT,
+ X_TO_INTEGER) = range(40, 52)
 
 BIN_OPS = {"=": X_EQ, "<>": X_NEQ, "<": X_LT, "<=": X_LE, ">": X_GT, ">=": X_GE, "+": X_ADD, "-": X_SUB, "*": X_MUL,
-           "&": X_BITAND, "|": X_BITOR, "<<": X_SHL, ">>>": X_SHRU}
+           "/": X_DIV, "&": X_BITAND, "|": X_BITOR, "<<": X_SHL, ">>>": X_SHRU}
 
 
 class Expr:
@@ -237,6 +246,88 @@ class Contains(Expr):
 _STRING_MATCH = {StartsWith: X_STARTS_WITH, EndsWith: X_ENDS_WITH, Contains: X_CONTAINS}
 
 
+@dataclass(frozen=True, eq=False)
+class Sqrt(Expr):
+    """Sqrt(expr) (SparkSQLExprMapper.scala:249, ``functions.sqrt``): the correctly rounded square root as a Double;
+    a Long operand is converted first.  A negative operand gives NaN, not NULL; NULL gives NULL."""
+    arg: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class Log(Expr):
+    """Log(expr) (SparkSQLExprMapper.scala:250, ``functions.log``): the natural logarithm as a Double; NULL when the
+    operand is NULL or <= 0 (Spark's UnaryLogExpression), NaN for NaN."""
+    arg: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class Log10(Expr):
+    """Log10(expr) (SparkSQLExprMapper.scala:251, ``functions.log(10.0, expr)``, Spark's Logarithm):
+    ``log(x) / log(10.0)``, not ``log10(x)`` -- log10(1000) is 2.9999999999999996; NULL when the operand is NULL
+    or <= 0."""
+    arg: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class Exp(Expr):
+    """Exp(expr) (SparkSQLExprMapper.scala:252, ``functions.exp``): e to the operand, a Double."""
+    arg: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class Abs(Expr):
+    """Abs(expr) (SparkSQLExprMapper.scala:254, ``functions.abs``): of the operand's type; Long wraps
+    (abs(Long.MIN) = Long.MIN), Double clears the sign bit."""
+    arg: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class Ceil(Expr):
+    """Ceil(expr) (SparkSQLExprMapper.scala:255, ``functions.ceil(..).cast(DoubleType)``): Spark's Ceil yields a Long
+    that the mapper casts back, so the Double result is saturated to the Long range, NaN gives 0.0 and a zero is
+    +0.0."""
+    arg: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class Floor(Expr):
+    """Floor(expr) (SparkSQLExprMapper.scala:256, ``functions.floor(..).cast(DoubleType)``): as Ceil."""
+    arg: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class Round(Expr):
+    """Round(expr) (SparkSQLExprMapper.scala:258, ``functions.round``): to an integral Double, halves away from zero
+    (HALF_UP); NaN and the infinities stay; a zero result is +0.0."""
+    arg: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class Sign(Expr):
+    """Sign(expr) (SparkSQLExprMapper.scala:259, ``functions.signum(..).cast(IntegerType)``): the Long -1, 0 or 1;
+    NaN and both zeros give 0."""
+    arg: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class ToFloat(Expr):
+    """ToFloat(expr) (SparkSQLExprMapper.scala:229, ``cast(DoubleType)``) of a number: a Long is converted (round to
+    nearest), a Double stays.  String operands are not implemented on the device path."""
+    arg: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class ToInteger(Expr):
+    """ToInteger(expr) (SparkSQLExprMapper.scala:231, ``cast(IntegerType)``, 32 bits) of a number, held as a Long: the
+    low 32 bits of a Long, sign-extended; a Double truncated toward zero and saturated to the Int range, NaN 0.
+    String operands are not implemented on the device path."""
+    arg: Expr
+
+
+_MATH_FUNCS = {Sqrt: X_SQRT, Log: X_LOG, Log10: X_LOG10, Exp: X_EXP, Abs: X_ABS, Ceil: X_CEIL, Floor: X_FLOOR,
+               Round: X_ROUND, Sign: X_SIGN, ToFloat: X_TO_FLOAT, ToInteger: X_TO_INTEGER}
+
+
 def _sorted_by_name(cols, names):
     cols, names = tuple(cols), tuple(names)
     if len(cols) != len(names):
@@ -343,6 +434,7 @@ def contains_explode(e: Expr) -> bool:
 TRUE = Lit(True)
 FALSE = Lit(False)
 NULL = Lit(None)
+E = Lit(math.e)  # E() (SparkSQLExprMapper.scala:253, functions.lit(Math.E)): no opcode
 
 
 def eq(a: Expr, b: Expr) -> Expr:
@@ -465,6 +557,9 @@ def compile_program(e: Expr, column_index: Callable[[str], int], encode_str: Cal
             go(x.arg)
             go(x.pattern)
             out.append((_STRING_MATCH[type(x)], 0, 0, 0))
+        elif type(x) in _MATH_FUNCS:
+            go(x.arg)
+            out.append((_MATH_FUNCS[type(x)], 0, 0, 0))
         elif isinstance(x, RelType):
             go(x.to_case())
         elif isinstance(x, Case):

@@ -28,7 +28,8 @@ from typing import Dict, FrozenSet, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .expr import (BOOL, F64, I64, LIST, STR, Ands, BinOp, Col, Explode, Expr, In, IsNotNull, IsNull, ListLit, Lit, Not, Ors,
-                   Contains, EndsWith, Index, InList, Keys, Labels, Range, Size, StartsWith, ands, eq)
+                   Contains, EndsWith, Index, InList, Keys, Labels, Range, Size, StartsWith, ands, eq,
+                   Abs, Ceil, E, Exp, Floor, Log, Log10, Round, Sign, Sqrt, ToFloat, ToInteger)
 from .table import ColumnData, decode_value
 
 
@@ -437,8 +438,10 @@ def _rel(m, names) -> RelPat:
 # ---------------------------------------------------------------------------------------------
 # expression DSL (JSON prefix lists) -> Expr over the current header
 # ---------------------------------------------------------------------------------------------
-_CMP = {"=", "<>", "<", "<=", ">", ">=", "+", "-", "*"}
+_CMP = {"=", "<>", "<", "<=", ">", ">=", "+", "-", "*", "/"}
 _STRING_MATCH = {"starts_with": StartsWith, "ends_with": EndsWith, "contains": Contains}
+_MATH = {"sqrt": Sqrt, "log": Log, "log10": Log10, "exp": Exp, "abs": Abs, "ceil": Ceil, "floor": Floor,
+         "round": Round, "sign": Sign, "tofloat": ToFloat, "tointeger": ToInteger}
 
 
 def to_expr(spec, header: Sequence[str]) -> Expr:
@@ -480,6 +483,10 @@ def to_expr(spec, header: Sequence[str]) -> Expr:
         return InList(to_expr(spec[1], header), _list_operand(spec[2], header))
     if op in _STRING_MATCH:  # ["starts_with", s, p], ["ends_with", s, p], ["contains", s, p]
         return _STRING_MATCH[op](to_expr(spec[1], header), to_expr(spec[2], header))
+    if op in _MATH:  # ["sqrt", x] .. ["sign", x], ["tofloat", x], ["tointeger", x]
+        return _MATH[op](to_expr(spec[1], header))
+    if op == "e":  # ["e"]
+        return E
     if op == "range":
         if len(spec) not in (3, 4):
             raise PlanningError(f"range takes two or three operands: {spec!r}")
@@ -561,14 +568,21 @@ class Planner:
                 cur = self._optional(cur, clause["optional_match"], clause.get("where"), varlen)
             else:
                 cur = self._match(cur, clause["match"], clause.get("where"), varlen)
+        if cur is None:  # no clause (RETURN sqrt(12.96)): one row; RETURN selects its items, so the helper goes
+            cur = self._unit()
         return self._return(cur, query["return"], varlen)
+
+    def _unit(self) -> _Op:
+        """The unit table: one row, one helper column."""
+        unit = self.names.fresh("unit")
+        return _Op(self.g.backend.table([ColumnData(unit, I64, np.zeros(1, dtype=np.int64))]), [unit], set(), [])
 
     # Unwind: RelationalPlanner.scala:94-96 -- in.add(Explode(list) as item), a Table.withColumns
     def _unwind(self, cur: Optional[_Op], spec, name: str, params: dict) -> _Op:
         unit = None
         if cur is None:  # a standalone UNWIND starts from the unit table (one row; the helper column is dropped)
-            unit = self.names.fresh("unit")
-            cur = _Op(self.g.backend.table([ColumnData(unit, I64, np.zeros(1, dtype=np.int64))]), [unit], set(), [])
+            cur = self._unit()
+            unit = cur.header[0]
         if name in cur.header:
             raise PlanningError(f"variable {name} is already bound")
         kind = spec[0]

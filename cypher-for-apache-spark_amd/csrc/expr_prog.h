@@ -19,15 +19,26 @@ constexpr int kMaxCols = 64;   // columns a program may address
 
 inline bool is_list_type(int32_t t) { return t >= CAPSMI_LIST_I64 && t <= CAPSMI_LIST_STR; }
 
-// The highest opcode of include/capsmi.h; a new opcode moves this and gets a row in expr_pops and check_program.
-constexpr int32_t kLastExprOp = CAPSMI_X_CONTAINS;
+// A new opcode of include/capsmi.h gets a row in expr_pops and check_program.  The numbers are not contiguous
+// (32..39 are unassigned): an opcode is unknown exactly when expr_pops has no row for it (known_expr_op below).
+
+// the numeric block (DIV .. TO_INTEGER): what k_expr.hip's math instantiation adds to the interpreter
+constexpr bool is_math_op(int32_t op) { return op >= CAPSMI_X_DIV && op <= CAPSMI_X_TO_INTEGER; }
+inline const char* math_op_name(int32_t op) {
+    static const char* const names[] = {"DIV", "SQRT", "LOG", "LOG10", "EXP", "ABS", "CEIL", "FLOOR", "ROUND", "SIGN",
+                                        "TO_FLOAT", "TO_INTEGER"};
+    return names[op - CAPSMI_X_DIV];
+}
 
 // operands an opcode pops: the one arity table (-1: unknown opcode, CAPSMI_X_PARAM included: it is bound before
 // anything counts)
 inline int expr_pops(const capsmi_expr& x) {
     switch (x.op) {
         case CAPSMI_X_COL: case CAPSMI_X_LIT: case CAPSMI_X_NULL: return 0;
-        case CAPSMI_X_NOT: case CAPSMI_X_ISNULL: case CAPSMI_X_ISNOTNULL: case CAPSMI_X_NEG: case CAPSMI_X_SIZE: return 1;
+        case CAPSMI_X_NOT: case CAPSMI_X_ISNULL: case CAPSMI_X_ISNOTNULL: case CAPSMI_X_NEG: case CAPSMI_X_SIZE:
+        case CAPSMI_X_SQRT: case CAPSMI_X_LOG: case CAPSMI_X_LOG10: case CAPSMI_X_EXP: case CAPSMI_X_ABS:
+        case CAPSMI_X_CEIL: case CAPSMI_X_FLOOR: case CAPSMI_X_ROUND: case CAPSMI_X_SIGN: case CAPSMI_X_TO_FLOAT:
+        case CAPSMI_X_TO_INTEGER: return 1;
         case CAPSMI_X_AND: case CAPSMI_X_OR: case CAPSMI_X_COALESCE: return x.arg;
         case CAPSMI_X_IN: return x.arg + 1;
         case CAPSMI_X_CASE: return 2 * x.arg + 1;
@@ -35,9 +46,17 @@ inline int expr_pops(const capsmi_expr& x) {
         case CAPSMI_X_ADD: case CAPSMI_X_SUB: case CAPSMI_X_MUL:
         case CAPSMI_X_BITAND: case CAPSMI_X_BITOR: case CAPSMI_X_SHL: case CAPSMI_X_SHRU:
         case CAPSMI_X_INDEX: case CAPSMI_X_IN_LIST:
-        case CAPSMI_X_STARTS_WITH: case CAPSMI_X_ENDS_WITH: case CAPSMI_X_CONTAINS: return 2;
+        case CAPSMI_X_STARTS_WITH: case CAPSMI_X_ENDS_WITH: case CAPSMI_X_CONTAINS: case CAPSMI_X_DIV: return 2;
         default: return -1;
     }
+}
+
+// whether expr_pops has a row for op (a negative operand count of an n-ary opcode is another matter: malformed)
+inline bool known_expr_op(int32_t op) {
+    capsmi_expr x{};
+    x.op = op;
+    x.arg = 1;
+    return expr_pops(x) >= 0;
 }
 
 // first node of the complete sub-expression that ends at prog[end] (postfix)
@@ -74,6 +93,8 @@ inline std::vector<std::pair<int, int>> operand_spans(const capsmi_expr* prog, i
 //     An entry whose typed alternatives disagree is `mixed`, as is arithmetic over one; it is a value like any
 //     other, but no operand of which one type is demanded (a string match's operands, INDEX's index, a list
 //     operand): CAPSMI_ERR_ILLEGAL_ARGUMENT.
+//   - The numeric block takes numbers: an operand typed BOOL or STR is CAPSMI_ERR_NOT_IMPLEMENTED; an untyped NULL
+//     and a mixed entry pass (a row that holds no number yields NULL, as for ADD).
 inline int32_t check_program(const int32_t* col_types, int ncols, int32_t nn, const capsmi_expr* prog) {
     struct Entry {
         int32_t t;
@@ -100,6 +121,11 @@ inline int32_t check_program(const int32_t* col_types, int ncols, int32_t nn, co
             REQUIRE(!is_list_type(opd[q].t) || (list_op && q == list_at), CAPSMI_ERR_NOT_IMPLEMENTED,
                     "a list value as an operand of expression op " + std::to_string(x.op) +
                         " on the device path (only size(), list[i] and IN over a list column take one)");
+        if (is_math_op(x.op))
+            for (int q = 0; q < pops; ++q)
+                REQUIRE(opd[q].mixed || (opd[q].t != CAPSMI_BOOL && opd[q].t != CAPSMI_STR), CAPSMI_ERR_NOT_IMPLEMENTED,
+                        std::string(opd[q].t == CAPSMI_BOOL ? "a BOOL" : "a STR") + " operand of CAPSMI_X_" +
+                            math_op_name(x.op) + " (division, the math functions, toFloat and toInteger take numbers)");
         Entry res{-1, false};
         switch (x.op) {
             case CAPSMI_X_COL:
@@ -133,7 +159,7 @@ inline int32_t check_program(const int32_t* col_types, int ncols, int32_t nn, co
                 }
                 res.t = CAPSMI_BOOL;
                 break;
-            case CAPSMI_X_NEG: res = opd[0]; break;
+            case CAPSMI_X_NEG: case CAPSMI_X_ABS: res = opd[0]; break;
             case CAPSMI_X_COALESCE: case CAPSMI_X_CASE: {  // CASE: [p1, v1, .., default]; the predicates are BOOL
                 const bool is_case = x.op == CAPSMI_X_CASE;
                 for (int q = is_case ? 1 : 0; q < pops; q += (is_case && q < pops - 2) ? 2 : 1) {
@@ -142,11 +168,14 @@ inline int32_t check_program(const int32_t* col_types, int ncols, int32_t nn, co
                 }
                 break;
             }
-            case CAPSMI_X_ADD: case CAPSMI_X_SUB: case CAPSMI_X_MUL:
+            case CAPSMI_X_ADD: case CAPSMI_X_SUB: case CAPSMI_X_MUL: case CAPSMI_X_DIV:
                 res.t = (opd[0].t == CAPSMI_F64 || opd[1].t == CAPSMI_F64) ? CAPSMI_F64 : CAPSMI_I64;
                 res.mixed = opd[0].mixed || opd[1].mixed;
                 break;
-            case CAPSMI_X_BITAND: case CAPSMI_X_BITOR: case CAPSMI_X_SHL: case CAPSMI_X_SHRU: res.t = CAPSMI_I64; break;
+            case CAPSMI_X_BITAND: case CAPSMI_X_BITOR: case CAPSMI_X_SHL: case CAPSMI_X_SHRU:
+            case CAPSMI_X_SIGN: case CAPSMI_X_TO_INTEGER: res.t = CAPSMI_I64; break;
+            case CAPSMI_X_SQRT: case CAPSMI_X_LOG: case CAPSMI_X_LOG10: case CAPSMI_X_EXP: case CAPSMI_X_CEIL:
+            case CAPSMI_X_FLOOR: case CAPSMI_X_ROUND: case CAPSMI_X_TO_FLOAT: res.t = CAPSMI_F64; break;
             case CAPSMI_X_EQ: case CAPSMI_X_NEQ: case CAPSMI_X_LT: case CAPSMI_X_LE: case CAPSMI_X_GT: case CAPSMI_X_GE:
             case CAPSMI_X_NOT: case CAPSMI_X_AND: case CAPSMI_X_OR: case CAPSMI_X_ISNULL: case CAPSMI_X_ISNOTNULL:
             case CAPSMI_X_IN: res.t = CAPSMI_BOOL; break;

@@ -21,6 +21,10 @@
 //     all the rows' elements before this interpreter runs.  No other opcode takes a list.
 //   - STARTS WITH / ENDS WITH / CONTAINS (SparkSQLExprMapper.scala:152-157) are lowered on the host the same way
 //     (lower_str_match below): k_strmatch.hip matches the bytes of the session's string store.
+//   - Divide (:186), Sqrt .. Sign (:249-260), ToFloat / ToInteger (:229-231): eval_math below, with the rules of the
+//     Spark 2.2.1 Column calls the mapper makes (include/capsmi.h states them per opcode).  Double log and exp are
+//     library code of some size, so these cases exist only in the kMath instantiation of the interpreter, which
+//     launch_eval takes for a program that holds one of them; every other program runs the code it ran before.
 #include "capsmi_impl.h"
 
 namespace capsmi {
@@ -65,6 +69,57 @@ __device__ __forceinline__ int cmp3(const Val& a, const Val& b) {
 __device__ __forceinline__ Val mk_bool(bool x) { return Val{x ? 1 : 0, (int8_t)CAPSMI_BOOL}; }
 __device__ __forceinline__ Val mk_null() { return Val{0, kNull}; }
 
+// Java's (long) d, which Spark's casts and its Long-valued Ceil / Floor apply: 0 for NaN, saturating, else toward
+// zero.  (A bare C++ cast is undefined outside the Long range.)
+__device__ __forceinline__ int64_t sat_i64(double d) {
+    if (d != d) return 0;
+    if (d >= 9223372036854775808.0) return INT64_MAX;
+    if (d <= -9223372036854775808.0) return INT64_MIN;
+    return (int64_t)d;
+}
+
+__device__ __forceinline__ Val mk_f64(double d) { return Val{__double_as_longlong(d), (int8_t)CAPSMI_F64}; }
+__device__ __forceinline__ Val mk_i64(int64_t v) { return Val{v, (int8_t)CAPSMI_I64}; }
+
+// CAPSMI_X_DIV (a / b) and the one-operand numeric opcodes (a).  A NULL or non-numeric operand: NULL.
+__device__ Val eval_math(int32_t op, const Val& a, const Val& b) {
+    if (!numeric(a.t) || (op == CAPSMI_X_DIV && !numeric(b.t))) return mk_null();
+    const bool is_long = a.t == CAPSMI_I64;
+    const double x = as_f64(a);
+    switch (op) {
+        case CAPSMI_X_DIV: {  // Spark's Division works on doubles; a zero divisor (either sign) is NULL
+            const double q = as_f64(b);
+            if (q == 0.0) return mk_null();
+            const double d = x / q;
+            return is_long && b.t == CAPSMI_I64 ? mk_i64(sat_i64(d)) : mk_f64(d);
+        }
+        case CAPSMI_X_SQRT: return mk_f64(sqrt(x));
+        case CAPSMI_X_LOG: return x <= 0.0 ? mk_null() : mk_f64(log(x));
+        case CAPSMI_X_LOG10: return x <= 0.0 ? mk_null() : mk_f64(log(x) / 2.302585092994046);  // Logarithm(10.0, x)
+        case CAPSMI_X_EXP: return mk_f64(exp(x));
+        case CAPSMI_X_ABS:
+            if (is_long) return mk_i64(a.b < 0 ? (int64_t)(0ULL - (uint64_t)a.b) : a.b);  // wraps at Long.MIN
+            return Val{a.b & INT64_MAX, (int8_t)CAPSMI_F64};
+        case CAPSMI_X_CEIL: return mk_f64(is_long ? x : (double)sat_i64(ceil(x)));
+        case CAPSMI_X_FLOOR: return mk_f64(is_long ? x : (double)sat_i64(floor(x)));
+        case CAPSMI_X_ROUND: {  // HALF_UP through BigDecimal: no signed zero; NaN and the infinities stay
+            if (is_long || x != x || x - x != 0.0) return mk_f64(x);
+            const double r2 = round(x);
+            return mk_f64(r2 == 0.0 ? 0.0 : r2);
+        }
+        case CAPSMI_X_SIGN: return mk_i64((x > 0.0) - (x < 0.0));
+        case CAPSMI_X_TO_FLOAT: return mk_f64(x);
+        default: {  // CAPSMI_X_TO_INTEGER: Spark's 32-bit IntegerType, held as a Long
+            if (is_long) return mk_i64((int64_t)(int32_t)(uint32_t)(uint64_t)a.b);
+            if (x != x) return mk_i64(0);
+            if (x >= 2147483647.0) return mk_i64(INT32_MAX);
+            if (x <= -2147483648.0) return mk_i64(INT32_MIN);
+            return mk_i64((int64_t)(int32_t)x);
+        }
+    }
+}
+
+template <bool kMath>
 __device__ Val eval_row(const capsmi_expr* __restrict__ prog, int nn, const ColPtrs& cp, int64_t r) {
     Val st[kMaxStack];
     int sp = 0;
@@ -199,16 +254,26 @@ __device__ Val eval_row(const capsmi_expr* __restrict__ prog, int nn, const ColP
                 st[sp++] = Val{cp.lval[a.c][lo + i.b], (int8_t)(a.t - CAPSMI_LIST)};
                 break;
             }
-            default: st[sp++] = mk_null(); break;
+            default:
+                if constexpr (kMath) {
+                    if (is_math_op(x.op)) {
+                        const Val b = x.op == CAPSMI_X_DIV ? st[--sp] : mk_null(), a = st[--sp];
+                        st[sp++] = eval_math(x.op, a, b);
+                        break;
+                    }
+                }
+                st[sp++] = mk_null();
+                break;
         }
     }
     return sp > 0 ? st[sp - 1] : mk_null();
 }
 
+template <bool kMath>
 __global__ void k_eval(const capsmi_expr* __restrict__ prog, int nn, ColPtrs cp, int64_t n, int64_t* __restrict__ out,
                        uint8_t* __restrict__ out_valid, uint8_t* __restrict__ flags) {
     for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x) {
-        const Val v = eval_row(prog, nn, cp, r);
+        const Val v = eval_row<kMath>(prog, nn, cp, r);
         if (flags) flags[r] = (v.t == CAPSMI_BOOL && v.b != 0) ? 1 : 0;
         if (out) out[r] = v.t == kNull ? 0 : v.b;
         if (out_valid) out_valid[r] = v.t == kNull ? 0 : 1;
@@ -265,7 +330,7 @@ std::vector<capsmi_expr> bind_params(const capsmi_session* s, int32_t nn, const 
             continue;
         }
         const int pops = expr_pops(x);
-        if (pops < 0 && x.op > kLastExprOp) throw Error(CAPSMI_ERR_NOT_IMPLEMENTED, "unknown expression op " + std::to_string(x.op));
+        REQUIRE(known_expr_op(x.op), CAPSMI_ERR_NOT_IMPLEMENTED, "unknown expression op " + std::to_string(x.op));
         REQUIRE(pops >= 0 && (int)width.size() >= pops, CAPSMI_ERR_ILLEGAL_ARGUMENT,
                 "malformed expression program (stack underflow)");
         capsmi_expr y = x;
@@ -425,9 +490,11 @@ int32_t launch_eval(capsmi_session* s, const capsmi_table* t, int32_t nn, const 
         HIP_CHECK(hipMemcpyAsync(P<void>(dprog), prog, sizeof(capsmi_expr) * nn, hipMemcpyHostToDevice, s->stream));
     int64_t g = (n + 255) / 256;
     if (g > 8192) g = 8192;
+    bool math = false;  // the instantiation with the numeric block, exactly when the program holds one of its opcodes
+    for (int i = 0; i < nn; ++i) math = math || is_math_op(prog[i].op);
     KernelTimer kt(s, "expr_eval");  // counts interpreter launches (a scan whose predicate ran inline has none)
-    hipLaunchKernelGGL(k_eval, dim3((unsigned)g), dim3(256), 0, s->stream, P<capsmi_expr>(dprog), nn, cp, n, out,
-                       out_valid, flags);
+    hipLaunchKernelGGL(math ? k_eval<true> : k_eval<false>, dim3((unsigned)g), dim3(256), 0, s->stream,
+                       P<capsmi_expr>(dprog), nn, cp, n, out, out_valid, flags);
     HIP_CHECK(hipGetLastError());
     return type;
 }

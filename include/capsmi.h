@@ -110,7 +110,7 @@ typedef struct {
  * Static types: a column or literal has its own, an untyped NULL none, comparisons and predicates are BOOL.
  * CAPSMI_X_COALESCE and CAPSMI_X_CASE take the type of their first typed alternative (CASE: v1 .. v_arg, then
  * the default); that is the type of a column computed from one.  Where the typed alternatives disagree the
- * value is "mixed", as is + - * or NEG over it: accepted as a value or a comparison operand, but
+ * value is "mixed", as is + - * / NEG or ABS over it: accepted as a value or a comparison operand, but
  * CAPSMI_ERR_ILLEGAL_ARGUMENT where one type is demanded, that is as an operand of CAPSMI_X_STARTS_WITH /
  * ENDS_WITH / CONTAINS, as the index of CAPSMI_X_INDEX, or as the list operand of a list opcode. */
 enum {
@@ -172,7 +172,46 @@ enum {
        rows' start positions. */
     CAPSMI_X_STARTS_WITH = 29, /* stack [s, p]: s STARTS WITH p */
     CAPSMI_X_ENDS_WITH = 30,   /* stack [s, p]: s ENDS WITH p */
-    CAPSMI_X_CONTAINS = 31     /* stack [s, p]: s CONTAINS p */
+    CAPSMI_X_CONTAINS = 31,    /* stack [s, p]: s CONTAINS p */
+    /* 32..39 are unassigned: CAPSMI_ERR_NOT_IMPLEMENTED "unknown expression op N", as every other number. */
+    /* Numeric functions (Divide, :186; Sqrt .. Sign, :249-260; ToFloat / ToInteger, :229-231).  A NULL operand
+       gives NULL.  An operand whose static type is BOOL or STR is CAPSMI_ERR_NOT_IMPLEMENTED when the node is
+       built (a list value too); an untyped NULL and a "mixed" value are accepted, and a row that holds a
+       non-numeric value yields NULL, as + - * do.  A Long operand of a Double-valued function is converted to
+       double first (round to nearest).  sat(d) below is Java's (long) d: 0 for NaN, Long.MAX for d >= 2^63,
+       Long.MIN for d <= -2^63, else d truncated toward zero.  The rules are those of the Spark 2.2.1 Column
+       calls the mapper makes, stated from knowledge of Spark's source, not from a run.  E() (:253) has no
+       opcode: the front ends push the Double literal Math.E. */
+    CAPSMI_X_DIV = 40,        /* stack [a, b]: both as doubles (Spark's Division coercion), p / q correctly
+                                 rounded; NULL when b is zero (-0.0 and Long 0 included).  Long / Long is Long:
+                                 sat(p / q), so -7 / 2 = -3, Long.MIN / -1 = Long.MAX and (2^53 + 1) / 1 = 2^53
+                                 (the reference's own precision loss); any Double operand makes the result
+                                 Double (mixed propagates, as for +), NaN and infinities propagate; Divide, :186 */
+    CAPSMI_X_SQRT = 41,       /* stack [x]: Double sqrt(x), correctly rounded; NaN (not NULL) for x < 0, -0.0 for
+                                 -0.0; functions.sqrt, :249 */
+    CAPSMI_X_LOG = 42,        /* stack [x]: Double log(x); NULL when x <= 0 (UnaryLogExpression; -0.0 included),
+                                 NaN for NaN; functions.log, :250 */
+    CAPSMI_X_LOG10 = 43,      /* stack [x]: Double log(x) / log(10.0), the divisor the double 2.302585092994046
+                                 (Spark's Logarithm, not log10: 1000 gives 2.9999999999999996); NULL when
+                                 x <= 0; functions.log(10.0, e), :251 */
+    CAPSMI_X_EXP = 44,        /* stack [x]: Double exp(x); functions.exp, :252 */
+    CAPSMI_X_ABS = 45,        /* stack [x]: of x's type; Long wraps (abs(Long.MIN) = Long.MIN), Double clears the
+                                 sign bit; functions.abs, :254 */
+    CAPSMI_X_CEIL = 46,       /* stack [x]: Double (double) sat(ceil(x)): Spark's Ceil is a Long that the mapper
+                                 casts back, so ceil(-0.5) = +0.0, ceil(1e300) = 2^63 and NaN gives 0.0; a Long
+                                 operand is only converted; functions.ceil(e).cast(DoubleType), :255 */
+    CAPSMI_X_FLOOR = 47,      /* stack [x]: Double (double) sat(floor(x)), as CEIL (floor(-0.0) = +0.0); :256 */
+    CAPSMI_X_ROUND = 48,      /* stack [x]: Double round(x, 0), HALF_UP: halves away from zero; NaN and the
+                                 infinities stay; a zero result is +0.0 (round(-0.4) = +0.0: BigDecimal has no
+                                 signed zero); a Long operand is only converted; functions.round, :258 */
+    CAPSMI_X_SIGN = 49,       /* stack [x]: Long -1, 0 or 1 (signum(double) cast to Int); NaN and both zeros give
+                                 0; functions.signum(e).cast(IntegerType), :259 */
+    CAPSMI_X_TO_FLOAT = 50,   /* stack [x]: Double; a Long is converted, a Double stays; cast(DoubleType), :229.
+                                 String operands are not implemented */
+    CAPSMI_X_TO_INTEGER = 51  /* stack [x]: Long holding Spark's 32-bit IntegerType: from Long the low 32 bits,
+                                 sign-extended (2^31 gives -2^31, 2^32 + 5 gives 5); from Double truncated
+                                 toward zero and saturated to [-2^31, 2^31 - 1], NaN 0; cast(IntegerType),
+                                 :231.  String operands are not implemented */
 };
 
 typedef struct {

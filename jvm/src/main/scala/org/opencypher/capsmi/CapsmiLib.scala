@@ -71,6 +71,19 @@ object Capsmi {
   final val X_STARTS_WITH = 29  // [s, p]: s STARTS WITH p over the session's string store, 3VL
   final val X_ENDS_WITH = 30    // [s, p]: s ENDS WITH p
   final val X_CONTAINS = 31     // [s, p]: s CONTAINS p
+  // 32..39 are unassigned.  Numeric functions: NULL in, NULL out; the rules of Spark 2.2.1 (include/capsmi.h)
+  final val X_DIV = 40         // [a, b]: a / b as doubles, NULL for a zero divisor; Long / Long saturates to Long
+  final val X_SQRT = 41        // [x]: Double
+  final val X_LOG = 42         // [x]: Double, NULL for x <= 0
+  final val X_LOG10 = 43       // [x]: Double log(x) / log(10.0), NULL for x <= 0
+  final val X_EXP = 44         // [x]: Double
+  final val X_ABS = 45         // [x]: of x's type
+  final val X_CEIL = 46        // [x]: Double, through Long
+  final val X_FLOOR = 47       // [x]: Double, through Long
+  final val X_ROUND = 48       // [x]: Double, HALF_UP
+  final val X_SIGN = 49        // [x]: Long -1, 0, 1
+  final val X_TO_FLOAT = 50    // [x]: Double
+  final val X_TO_INTEGER = 51  // [x]: Long holding a 32-bit Int
 
   // capsmi_with_mask_list_column: which columns of a row pass
   final val MASK_TRUE = 0     // labels(): the Boolean flag is non-null and TRUE

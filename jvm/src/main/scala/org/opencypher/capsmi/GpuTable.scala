@@ -379,8 +379,10 @@ final class GpuTable private (val handle: Pointer)(implicit val session: GpuSess
   * the CASE over the header's type flags (get_rel_type's headOption.orNull), StartNodeFunction / EndNodeFunction
   * are column lookups; Labels and Keys are list columns built by GpuTable.  StartsWith / EndsWith / Contains
   * (:152-157) are CAPSMI_X_STARTS_WITH / ENDS_WITH / CONTAINS; a program that holds one uploads the session's
-  * string store first (GpuSession.syncStrings).  Shapes the device path does not
-  * evaluate (regular expressions, other functions, maps, size() of a string) raise NotImplementedException.
+  * string store first (GpuSession.syncStrings).  Divide (:186), Sqrt / Log / Log10 / Exp / Abs / Ceil / Floor /
+  * Round / Sign (:249-260) and ToFloat / ToInteger of numbers (:229-231) are CAPSMI_X_DIV .. CAPSMI_X_TO_INTEGER,
+  * E() the literal Math.E.  Shapes the device path does not evaluate (regular expressions, other functions, maps,
+  * size() / toFloat() / toInteger() of a string, rand()) raise NotImplementedException.
   */
 final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters: CypherMap,
                               lists: Map[Expr, String] = Map.empty) {
@@ -466,6 +468,24 @@ final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters:
     case Add(l, r) => bin(Capsmi.X_ADD, l, r, out)
     case Subtract(l, r) => bin(Capsmi.X_SUB, l, r, out)
     case Multiply(l, r) => bin(Capsmi.X_MUL, l, r, out)
+    // Divide (:186) and the numeric functions (:229-231, :249-260); E() is the literal Math.E (:253)
+    case Divide(l, r) => bin(Capsmi.X_DIV, l, r, out)
+    case _: E => out += lit(Capsmi.F64, java.lang.Double.doubleToLongBits(Math.E))
+    case Sqrt(x) => go(x, out); out += ((Capsmi.X_SQRT, 0, 0, 0L))
+    case Log(x) => go(x, out); out += ((Capsmi.X_LOG, 0, 0, 0L))
+    case Log10(x) => go(x, out); out += ((Capsmi.X_LOG10, 0, 0, 0L))
+    case Exp(x) => go(x, out); out += ((Capsmi.X_EXP, 0, 0, 0L))
+    case Abs(x) => go(x, out); out += ((Capsmi.X_ABS, 0, 0, 0L))
+    case Ceil(x) => go(x, out); out += ((Capsmi.X_CEIL, 0, 0, 0L))
+    case Floor(x) => go(x, out); out += ((Capsmi.X_FLOOR, 0, 0, 0L))
+    case Round(x) => go(x, out); out += ((Capsmi.X_ROUND, 0, 0, 0L))
+    case Sign(x) => go(x, out); out += ((Capsmi.X_SIGN, 0, 0, 0L))
+    case ToFloat(x) if x.cypherType.material == CTString =>
+      throw NotImplementedException("toFloat() of a string on the device path: the bytes live in the caller's dictionary")
+    case ToFloat(x) => go(x, out); out += ((Capsmi.X_TO_FLOAT, 0, 0, 0L))
+    case ToInteger(x) if x.cypherType.material == CTString =>
+      throw NotImplementedException("toInteger() of a string on the device path: the bytes live in the caller's dictionary")
+    case ToInteger(x) => go(x, out); out += ((Capsmi.X_TO_INTEGER, 0, 0, 0L))
     case BitwiseAnd(l, r) => bin(Capsmi.X_BITAND, l, r, out)
     case BitwiseOr(l, r) => bin(Capsmi.X_BITOR, l, r, out)
     case ShiftLeft(v, bits) => bin(Capsmi.X_SHL, v, bits, out)
