@@ -217,6 +217,18 @@ __device__ __forceinline__ uint32_t wave_incl_scan(uint32_t x) {
     return x;
 }
 
+// This lane's index for wave 0's bookkeeping (p1l_settle, p1l_plan), opaque to the optimiser.  From a plain
+// `threadIdx.x & 63` the per-lane constants of the bookkeeping loops (slice ranges, LDS addresses) are hoisted out
+// of the tile loop, where the prefetched tile and the tile being ranked leave them no registers: they were
+// spilled (36 B of scratch per lane), and every reload inside wave 0's section waited on vmcnt, in order, behind
+// the next tile's loads, with 15 waves at the barrier.  Recomputed per tile they cost a few VALU instructions,
+// the kernel has no scratch and wave 0's section waits for no vector memory.
+__device__ __forceinline__ int p1l_lane() {
+    int lane = threadIdx.x & 63;
+    asm volatile("" : "+v"(lane));
+    return lane;
+}
+
 // Pass 1 writing whole 128-byte lines only.  A slice's run is appended behind the items its open
 // chunk still holds back (fewer than kLine, kept in LDS): the combined sequence is staged, every
 // complete line of it is stored, and the tail is held back again.  A line is then written once,
@@ -237,7 +249,7 @@ __device__ __forceinline__ void p1l_settle(const Layout& L, int hw, const uint2*
                                            const uint32_t* loc, uint32_t* ph, uint32_t* fl, const uint32_t* p1,
                                            const uint32_t* opened, uint32_t* misc, unsigned long long* cmeta,
                                            uint32_t* chist) {
-    const int nb = L.nt, lane = threadIdx.x & 63;
+    const int nb = L.nt, lane = p1l_lane();
     const uint32_t nop = misc[0];
     if (HIST) {
         for (uint32_t x = lane; x < nop * (uint32_t)hw; x += 64) {
@@ -296,7 +308,7 @@ template <int LN>
 __device__ __forceinline__ void p1l_plan(int nb, const uint32_t* cn, uint32_t* loc, const uint32_t* ph,
                                          const uint32_t* fl, uint32_t* p1, uint32_t* opened, uint32_t* misc,
                                          uint32_t* base, uint4* Q) {
-    const int lane = threadIdx.x & 63;
+    const int lane = p1l_lane();
     const int per = (nb + 63) / 64, b0 = lane * per, b1 = min(b0 + per, nb);
     uint32_t sum = 0, need = 0;
     for (int i = b0; i < b1; ++i) {

@@ -126,15 +126,16 @@ int main(int argc, char** argv) {
         const char* name;
         const void* fn;
         int block, tile, gmul, floor;  // floor: 0 k_scatter_c, 1 copy floor, 2 k_scatter_l
+        bool hist, split;
     };
+    // the library's instantiations (chunk_partition) and the copy floors
     const V vs[] = {
-        {"sc_1024x8", (const void*)k_scatter_c<1024, 8, 4, false>, 1024, 8192, 1, 0},
-        {"sl_1024x8", (const void*)k_scatter_l<1024, 8, 4>, 1024, 8192, 1, 2},
-        {"sl_ntl", (const void*)k_scatter_l<1024, 8, 4, true, false>, 1024, 8192, 1, 2},
-        {"sl_nts", (const void*)k_scatter_l<1024, 8, 4, false, true>, 1024, 8192, 1, 2},
-        {"sl_ntl_nts", (const void*)k_scatter_l<1024, 8, 4, true, true>, 1024, 8192, 1, 2},
-        {"floor", (const void*)k_floor<false, false>, 1024, 8192, 1, 1},
-        {"floor_ntls", (const void*)k_floor<true, true>, 1024, 8192, 1, 1},
+        {"sc_hist", (const void*)k_scatter_c<1024, 8, 4, false, true>, 1024, 8192, 1, 0, true, false},
+        {"sl_hist", (const void*)k_scatter_l<1024, 8, 4, true>, 1024, 8192, 1, 2, true, false},
+        {"sl_pairs", (const void*)k_scatter_l<1024, 8, 4, false>, 1024, 8192, 1, 2, false, false},
+        {"sl_split", (const void*)k_scatter_l<1024, 8, 4, false, true>, 1024, 8192, 1, 2, false, true},
+        {"floor", (const void*)k_floor<false, false>, 1024, 8192, 1, 1, false, false},
+        {"floor_ntls", (const void*)k_floor<true, true>, 1024, 8192, 1, 1, false, false},
     };
     const int nv = sizeof(vs) / sizeof(vs[0]);
     int64_t npool = 1;
@@ -158,7 +159,8 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&dcount, 8));
     for (int v = 0; v < nv; ++v) {
         const int64_t g = (int64_t)dev_cus * vs[v].gmul;
-        const size_t lds = vs[v].floor == 1 ? 0 : vs[v].floor == 2 ? scatter1l_lds(L.nt, L.ns, vs[v].block, vs[v].tile) : scatter1_lds(L.nt, L.ns, vs[v].block, vs[v].tile);
+        const size_t lds = vs[v].floor == 1 ? 0 : vs[v].floor == 2 ? scatter1l_lds(L.nt, L.ns, vs[v].hist, vs[v].block, vs[v].tile, vs[v].split)
+                                                                : scatter1_lds(L.nt, L.ns, vs[v].hist, vs[v].block, vs[v].tile);
         if (lds) CK(hipFuncSetAttribute(vs[v].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         float best = 1e30f, sum = 0;
         for (int r = 0; r < 6; ++r) {
@@ -192,7 +194,7 @@ int main(int argc, char** argv) {
         }
         // check: total fill over chunk metadata == m; chunks consistent with their histograms
         unsigned long long tot = 0, nbad = 0, sig = 0;
-        if (vs[v].floor != 1) {
+        if (vs[v].floor != 1 && vs[v].hist) {  // k_check reads pairs and their histogram rows
             unsigned long long* d;
             CK(hipMalloc(&d, 8 * (2 * L.nt + 1)));
             CK(hipMemset(d, 0, 8 * (2 * L.nt + 1)));
@@ -202,6 +204,8 @@ int main(int argc, char** argv) {
             nbad = hs[2 * L.nt];
             for (int j = 0; j < 2 * L.nt; ++j) sig = sig * 0x100000001B3ull + hs[j];
             CK(hipFree(d));
+        }
+        if (vs[v].floor != 1) {
             std::vector<unsigned long long> h(npool);
             CK(hipMemcpy(h.data(), meta, 8 * npool, hipMemcpyDeviceToHost));
             for (auto x : h) tot += x >> 32;
