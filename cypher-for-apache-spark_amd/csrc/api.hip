@@ -536,6 +536,9 @@ bool apply(Config& c, const std::string& name, const char* v) {
     } else if (name == "CAPSMI_INGEST_THREADS") {
         if (!parse_int(v, 0, 1024, x)) return false;
         c.ingest_threads = (int)x;
+    } else if (name == "CAPSMI_NARROW") {
+        if (!parse_choice(v, {"auto", "off"}, k)) return false;
+        c.narrow = k == 0;
     } else if (name == "CAPSMI_STR_MATCH") {
         if (!parse_choice(v, {"auto", "rows", "dict"}, k)) return false;
         c.str_match = k;
@@ -552,7 +555,7 @@ const std::pair<const char*, const char*> kKnobs[] = {
     {"CAPSMI_UND", "part"},          {"CAPSMI_VL_BITS", "8"},        {"CAPSMI_VL_SUBLOG", "-1"},
     {"CAPSMI_VL_F2", "0"},           {"CAPSMI_COLL_CHUNK", "67108864"}, {"CAPSMI_INGEST_THREADS", "0"},
     {"CAPSMI_HOP2", "auto"},         {"CAPSMI_POOL", "split"},       {"CAPSMI_STR_MATCH", "auto"},
-    {"CAPSMI_HOP2_EXCHANGE", "on"}};
+    {"CAPSMI_HOP2_EXCHANGE", "on"},  {"CAPSMI_NARROW", "auto"}};
 }  // namespace
 
 Config config_from_env() {
@@ -1861,14 +1864,16 @@ static void build_part(capsmi_session* s, int32_t nrels, capsmi_table* const* re
                        const char* dst_col, int64_t lo, int64_t hi, RelPart& rp, const RelPartHop1* h1 = nullptr) {
     std::vector<const int64_t*> srcs, dsts;
     std::vector<int64_t> ms;
+    std::vector<NarrowRel> nar;  // pass 1 reads a table's 32-bit endpoint copies where it carries them
     for (int i = 0; i < nrels; ++i) {
         need(rels[i], "rels[i]");
         M(rels[i]);
         srcs.push_back(rel_col(rels[i], src_col).d());
         dsts.push_back(rel_col(rels[i], dst_col).d());
+        nar.push_back(narrow_rel(s, rel_col(rels[i], src_col), rel_col(rels[i], dst_col)));
         ms.push_back(rels[i]->nrows);
     }
-    relpart_build(s, srcs.data(), dsts.data(), ms.data(), nrels, lo, hi, rp, h1);
+    relpart_build(s, srcs.data(), dsts.data(), ms.data(), nrels, lo, hi, rp, h1, false, nar.data());
 }
 
 // hop 1 on a partitioned layout into X1 (= M | S1) and X2 (= M | S2); S1 scratch
@@ -2056,16 +2061,18 @@ capsmi_status capsmi_var_length_count(capsmi_session* s, int32_t nrels, capsmi_t
     use_device(s);
     std::vector<const int64_t*> srcs, dsts;
     std::vector<int64_t> ms;
+    std::vector<NarrowRel> nar;  // for the two partitions' pass 1 (the other passes read the int64 words)
     for (int i = 0; i < nrels; ++i) {
         need(rels[i], "rels[i]");
         M(rels[i]);
         srcs.push_back(rel_col(rels[i], src_col).d());
         dsts.push_back(rel_col(rels[i], dst_col).d());
+        nar.push_back(narrow_rel(s, rel_col(rels[i], src_col), rel_col(rels[i], dst_col)));
         ms.push_back(rels[i]->nrows);
     }
     Buf ids, cnt;
-    const int64_t rows =
-        var_length_count(s, srcs.data(), dsts.data(), ms.data(), nrels, a_ok, b_ok, lower, upper, ids, cnt);
+    const int64_t rows = var_length_count(s, srcs.data(), dsts.data(), ms.data(), nrels, a_ok, b_ok, lower, upper, ids,
+                                          cnt, nar.data());
     auto* o = new_table(s, rows);
     Column a, c;
     a.name = id_name;

@@ -81,7 +81,15 @@ struct Column {
     // host copy of the words of a column built from host values (the fused routes' count rows):
     // exports read it without a device round trip
     std::shared_ptr<const std::vector<int64_t>> host;
+    // optional 32-bit copy of `data`, made when a relationship table is registered (narrow_endpoints, plan.hip):
+    // narrow[i] = data[i] - narrow_base over the rows the table had then, under the same row `offset`.  The
+    // words are immutable and shared, so a copy of the Column carries them along; `narrow_of` names the words
+    // they were made from, so a Column whose `data` was replaced since no longer offers them (n32).
+    Buf narrow;
+    const DevBuf* narrow_of = nullptr;
+    int64_t narrow_base = 0;
     const int64_t* d() const { return P<int64_t>(data) + offset; }
+    const uint32_t* n32() const { return narrow && narrow_of == data.get() ? P<uint32_t>(narrow) + offset : nullptr; }
     const uint8_t* v() const { return valid ? P<uint8_t>(valid) + offset : nullptr; }
     bool nullable() const { return valid != nullptr || lazy_nullable; }
 };
@@ -161,6 +169,10 @@ struct Config {
     bool vl_f2 = false;           // CAPSMI_VL_F2 = 1: the second-level filter in the T walk (the sharded form's)
     int64_t coll_chunk = int64_t(1) << 26;  // CAPSMI_COLL_CHUNK: elements per host collective call
     int ingest_threads = 0;       // CAPSMI_INGEST_THREADS (0: OMP_NUM_THREADS, else up to 16 hardware threads)
+    bool narrow = true;           // CAPSMI_NARROW = auto | off: registering a relationship table whose endpoints span at most
+                                  //   2^32 ids keeps a 32-bit copy of both endpoint columns (8 B per relationship of device
+                                  //   memory), which pass 1 of the chunk partition reads instead of the int64 words; off
+                                  //   builds none and reads none
     int str_match = 0;            // CAPSMI_STR_MATCH = auto | rows | dict (0..2): which side a string match with a constant
                                   //   pattern runs on -- once per row, or once per entry of the string store with a
                                   //   lookup per row (auto: the store when the table has at least as many rows; k_strmatch.hip)
@@ -525,6 +537,15 @@ struct ChunkPart {
     int* ja = nullptr;           // first bucket per block
     uint32_t* order = nullptr;   // used chunks grouped by bucket
 };
+// The 32-bit form of one table's endpoint columns as pass 1 reads it (Column::narrow of both columns, one base):
+// s[i] = source[i] - base, d[i] = target[i] - base.  s == nullptr: the table is read as int64.
+struct NarrowRel {
+    const uint32_t* s = nullptr;
+    const uint32_t* d = nullptr;
+    int64_t base = 0;
+};
+// the narrow form of (source column sc, target column dc) if both carry one with one base and the knob allows
+NarrowRel narrow_rel(const capsmi_session* s, const Column& sc, const Column& dc);
 struct RelPart {
     PartLayout L;
     // The build has two stages.  Stage 1 (pass 1) leaves the chunk partition `cp`: pairs grouped by target
@@ -553,8 +574,10 @@ struct RelPartHop1 {
     uint32_t *M, *S1, *S2;
 };
 // unpacked: keep 8-byte pairs whatever the domain (a layout walked by kernels that read uint2 pairs only)
+// nar: per table its 32-bit endpoint form (NarrowRel; null: none has one)
 void relpart_build(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms, int nt,
-                   int64_t lo, int64_t hi, RelPart& rp, const RelPartHop1* h1 = nullptr, bool unpacked = false);
+                   int64_t lo, int64_t hi, RelPart& rp, const RelPartHop1* h1 = nullptr, bool unpacked = false,
+                   const NarrowRel* nar = nullptr);
 // stage 2 of the build on a handle that kept its pool (no-op when the cells are there)
 void relpart_cells(capsmi_session* s, RelPart& rp);
 void relpart_hop1(capsmi_session* s, RelPart& rp, const capsmi_bitmap* a, const capsmi_bitmap* b, uint32_t* M,
@@ -637,7 +660,7 @@ bool grouped_two_hop(capsmi_session* s, const int64_t* const* srcs, const int64_
 // fused var-length grouped count (k_varlen.hip)
 int64_t var_length_count(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
                          int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower, int upper,
-                         Buf& out_ids, Buf& out_cnt);
+                         Buf& out_ids, Buf& out_cnt, const NarrowRel* nar = nullptr);
 
 // sharded var-length grouped count (multi-GPU C5; k_varlen.hip): begin -> caller sums od over ranks
 // -> mid -> caller sums Y -> finish (rows of owned ids)
@@ -652,6 +675,10 @@ void varlen_shard_free(VarlenShard* v);
 
 // [min, max] over `ncols` int64 columns of n rows into out[0], out[1] (synchronises); n > 0
 void minmax_i64(capsmi_session* s, const int64_t* const* cols, int ncols, int64_t n, int64_t* out);
+// oa[i] = a[i] - base and ob[i] = b[i] - base as 32-bit words for n rows, one pass on the session's stream
+// (the endpoint columns' narrow copies; the caller has checked that every difference fits)
+void narrow_pair_i64(capsmi_session* s, const int64_t* a, const int64_t* b, int64_t n, int64_t base, uint32_t* oa,
+                     uint32_t* ob);
 // widen n input values of width `code` (CAPSMI_IN_* of include/capsmi.h) to 8-byte words
 void widen_words(const void* in, int code, int64_t* out, int64_t n, hipStream_t st);
 

@@ -339,7 +339,39 @@ __global__ void k_widen(const void* __restrict__ in, int code, int64_t* __restri
     }
 }
 
+// The endpoint columns' 32-bit copies (Column::narrow): oa[i] = a[i] - base, ob[i] = b[i] - base.  Both columns are
+// read once and both copies written in the one pass; `vec`: all four arrays 16-byte aligned, four rows per lane
+// and step (two 16-byte loads and one 16-byte store per column), the rows past the last whole four one each.
+__global__ void __launch_bounds__(256) k_narrow_pair(const int64_t* __restrict__ a, const int64_t* __restrict__ b,
+                                                     int64_t n, int64_t base, int vec, uint32_t* __restrict__ oa,
+                                                     uint32_t* __restrict__ ob) {
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+    const int64_t n4 = vec ? n / 4 : 0;
+    for (int64_t q = tid; q < n4; q += nth) {
+        const longlong2 a0 = reinterpret_cast<const longlong2*>(a)[2 * q], a1 = reinterpret_cast<const longlong2*>(a)[2 * q + 1];
+        const longlong2 b0 = reinterpret_cast<const longlong2*>(b)[2 * q], b1 = reinterpret_cast<const longlong2*>(b)[2 * q + 1];
+        reinterpret_cast<uint4*>(oa)[q] = make_uint4((uint32_t)(a0.x - base), (uint32_t)(a0.y - base),
+                                                     (uint32_t)(a1.x - base), (uint32_t)(a1.y - base));
+        reinterpret_cast<uint4*>(ob)[q] = make_uint4((uint32_t)(b0.x - base), (uint32_t)(b0.y - base),
+                                                     (uint32_t)(b1.x - base), (uint32_t)(b1.y - base));
+    }
+    for (int64_t i = 4 * n4 + tid; i < n; i += nth) {
+        oa[i] = (uint32_t)(a[i] - base);
+        ob[i] = (uint32_t)(b[i] - base);
+    }
+}
+
 }  // namespace
+
+void narrow_pair_i64(capsmi_session* s, const int64_t* a, const int64_t* b, int64_t n, int64_t base, uint32_t* oa,
+                     uint32_t* ob) {
+    if (n <= 0) return;
+    const bool vec = (((uintptr_t)a | (uintptr_t)b | (uintptr_t)oa | (uintptr_t)ob) & 15) == 0;
+    KernelTimer kt(s, "narrow_build", 24.0 * (double)n);
+    hipLaunchKernelGGL(k_narrow_pair, dim3(grid_for(vec ? (n + 3) / 4 : n)), dim3(256), 0, s->stream, a, b, n, base,
+                       vec ? 1 : 0, oa, ob);
+    HIP_CHECK(hipGetLastError());
+}
 
 void minmax_i64(capsmi_session* s, const int64_t* const* cols, int ncols, int64_t n, int64_t* out) {
     Buf d = dev_alloc(2 * sizeof(long long), s);

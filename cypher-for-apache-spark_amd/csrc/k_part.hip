@@ -61,8 +61,9 @@ __device__ __forceinline__ void hist_add(uint32_t* H, int hw, int b, uint32_t i)
 }
 
 // HIST = false: no cell counts (no H, no chist rows); k_chunk_hist makes the rows when something asks for them
-template <int B, int IT, int MINW, bool NTS, bool HIST>  // MINW: waves per SIMD to fit
-__global__ void __launch_bounds__(B, MINW) k_scatter_c(const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
+// IdT: int64_t columns, or uint32_t for their narrow copies (then L is the window shifted by the copies' base)
+template <int B, int IT, int MINW, bool NTS, bool HIST, typename IdT = int64_t>  // MINW: waves per SIMD to fit
+__global__ void __launch_bounds__(B, MINW) k_scatter_c(const IdT* __restrict__ src, const IdT* __restrict__ dst,
                                                        int64_t m, Layout L, int swap, int64_t chunk0, size_t trash,
                                                        uint2* __restrict__ pool, unsigned long long* __restrict__ cmeta,
                                                        uint32_t* __restrict__ chist) {
@@ -93,7 +94,7 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_c(const int64_t* __restrict
     const uint64_t range = (uint64_t)(L.hi - L.lo);
     const bool vec = (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
     const int64_t stride = (int64_t)gridDim.x * T;
-    int64_t sr[IT], tr[IT];
+    IdT sr[IT], tr[IT];
     int64_t t0 = (int64_t)blockIdx.x * T;
     if (t0 < m) load_tile<B>(src, dst, t0, m, vec, sr, tr);
     for (; t0 < m; t0 += stride) {  // block-uniform
@@ -104,8 +105,8 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_c(const int64_t* __restrict
         uint32_t valid = 0;
 #pragma unroll
         for (int u = 0; u < IT; ++u) {
-            const int64_t e = t0 + item_off<B>(u);
-            const uint64_t s = (uint64_t)(sr[u] - L.lo), t = (uint64_t)(tr[u] - L.lo);
+            const int64_t e = t0 + tile_item_off<B, IdT>(u);
+            const uint64_t s = rel_id(sr[u], L.lo), t = rel_id(tr[u], L.lo);
             const bool ok = e < m && s < range && t < range;
             pr[u] = swap ? make_uint2((uint32_t)t, (uint32_t)s) : make_uint2((uint32_t)s, (uint32_t)t);
             valid |= (ok ? 1u : 0u) << u;
@@ -344,8 +345,10 @@ __host__ __device__ constexpr size_t scatter1l_lds(int nb, int ns, bool hist, in
            sizeof(uint32_t) * ((hist ? (size_t)nb * hist_words(ns) : 0) + 12 * (size_t)nb + block / 64 + 4);
 }
 
-template <int B, int IT, int MINW, bool HIST, bool SPLIT = false, bool NTL = false, bool NTS = false>
-__global__ void __launch_bounds__(B, MINW) k_scatter_l(const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
+// IdT as in k_scatter_c: the narrow form holds the prefetched tile (sr, tr) in 2 * IT registers, not 4 * IT.
+template <int B, int IT, int MINW, bool HIST, bool SPLIT = false, bool NTL = false, bool NTS = false,
+          typename IdT = int64_t>
+__global__ void __launch_bounds__(B, MINW) k_scatter_l(const IdT* __restrict__ src, const IdT* __restrict__ dst,
                                                       int64_t m, Layout L, int swap, int64_t chunk0, size_t trash,
                                                       uint2* __restrict__ pool, unsigned long long* __restrict__ cmeta,
                                                       uint32_t* __restrict__ chist) {
@@ -396,7 +399,7 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_l(const int64_t* __restrict
     const uint64_t range = (uint64_t)(L.hi - L.lo);
     const bool vec = (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
     const int64_t stride = (int64_t)gridDim.x * T;
-    int64_t sr[IT], tr[IT];
+    IdT sr[IT], tr[IT];
     int64_t t0 = (int64_t)blockIdx.x * T;
     if (t0 < m) load_tile<B, NTL>(src, dst, t0, m, vec, sr, tr);
     int par = 0;
@@ -408,8 +411,8 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_l(const int64_t* __restrict
         uint32_t valid = 0;
 #pragma unroll
         for (int u = 0; u < IT; ++u) {
-            const int64_t e = t0 + item_off<B>(u);
-            const uint64_t s = (uint64_t)(sr[u] - L.lo), t = (uint64_t)(tr[u] - L.lo);
+            const int64_t e = t0 + tile_item_off<B, IdT>(u);
+            const uint64_t s = rel_id(sr[u], L.lo), t = rel_id(tr[u], L.lo);
             const bool ok = e < m && s < range && t < range;
             pr[u] = swap ? make_uint2((uint32_t)t, (uint32_t)s) : make_uint2((uint32_t)s, (uint32_t)t);
             valid |= (ok ? 1u : 0u) << u;
@@ -507,13 +510,6 @@ __global__ void __launch_bounds__(kHistBlock) k_chunk_hist(const uint2* __restri
         if (lane < hw) chist[(size_t)q * hw + lane] = h[lane];
         wave_lds_order();
     }
-}
-
-// this lane's item u of a 4-items-per-load walk starting at the 4-aligned index b: item u is
-// b + 4 * ((u >> 2) * B + lane) + (u & 3)
-template <int B>
-__device__ __forceinline__ int item_off4(int u) {
-    return 4 * ((u >> 2) * B + (int)threadIdx.x) + (u & 3);
 }
 
 // used chunks (fill > 0) grouped by target slice (order within a slice is arbitrary).  Each block
@@ -1417,7 +1413,7 @@ static void allow_lds(K kernel, size_t bytes) {
 
 void chunk_partition(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
                      int nt, bool swap, const part::Layout& L, int64_t g2_want, ChunkPart& cp, bool want_hist,
-                     bool want_split) {
+                     bool want_split, const NarrowRel* nar) {
     using namespace part;
     hipStream_t st = s->stream;
     cp.L = L;
@@ -1469,13 +1465,40 @@ void chunk_partition(capsmi_session* s, const int64_t* const* srcs, const int64_
               : lines ? (want_hist ? k_scatter_l<kP1Block, kItems, 4, true> : k_scatter_l<kP1Block, kItems, 4, false>)
                     : (want_hist ? k_scatter_c<kP1Block, kItems, 4, kP1NT, true>
                                  : k_scatter_c<kP1Block, kItems, 4, kP1NT, false>);
-    allow_lds(k1, lds1);
+    // the same instantiation over a table's 32-bit endpoint copies (NarrowRel), chosen per table
+    using u32 = uint32_t;
+    auto k1n = split ? k_scatter_l<kP1Block, kItems, 4, false, true, false, false, u32>
+               : lines ? (want_hist ? k_scatter_l<kP1Block, kItems, 4, true, false, false, false, u32>
+                                    : k_scatter_l<kP1Block, kItems, 4, false, false, false, false, u32>)
+                     : (want_hist ? k_scatter_c<kP1Block, kItems, 4, kP1NT, true, u32>
+                                  : k_scatter_c<kP1Block, kItems, 4, kP1NT, false, u32>);
+    bool any_wide = false, any_narrow = false;
+    for (int i = 0; i < nt; ++i)
+        if (ms[i] > 0) (nar && nar[i].s ? any_narrow : any_wide) = true;
+    if (any_wide || !any_narrow) allow_lds(k1, lds1);
+    if (any_narrow) allow_lds(k1n, lds1);
     for (int i = 0; i < nt; ++i) {
         if (ms[i] <= 0) continue;
+        uint2* pool = P<uint2>(cp.pool);
+        unsigned long long* meta = P<unsigned long long>(cp.meta);
+        uint32_t* chist = want_hist ? P<uint32_t>(cp.chist) : nullptr;
+        if (nar && nar[i].s) {
+            // a word w stands for the id base + w: the kernel sees the window shifted by -base (part::rel_id), so
+            // rows outside it on either side fail the range test exactly as their int64 words do.  Unsigned: the
+            // shift may wrap, hi - lo does not change.  Declared bytes: 8 read + 8 written per relationship
+            // (the caller's own figure is the int64 columns').
+            Layout Ln = L;
+            Ln.lo = (int64_t)((uint64_t)L.lo - (uint64_t)nar[i].base);
+            Ln.hi = (int64_t)((uint64_t)L.hi - (uint64_t)nar[i].base);
+            KernelTimer kt(s, "part_scatter1", 16.0 * (double)ms[i]);
+            hipLaunchKernelGGL(k1n, dim3(g1[i]), dim3(kP1Block), lds1, st, nar[i].s, nar[i].d, ms[i], Ln, swap ? 1 : 0,
+                               c0[i], (size_t)npool * kCh, pool, meta, chist);
+            s->routes["pass1_narrow"] += 1;
+            continue;
+        }
         KernelTimer kt(s, "part_scatter1");
         hipLaunchKernelGGL(k1, dim3(g1[i]), dim3(kP1Block), lds1, st, srcs[i], dsts[i], ms[i], L, swap ? 1 : 0, c0[i],
-                           (size_t)npool * kCh, P<uint2>(cp.pool), P<unsigned long long>(cp.meta),
-                           want_hist ? P<uint32_t>(cp.chist) : nullptr);
+                           (size_t)npool * kCh, pool, meta, chist);
     }
     HIP_CHECK(hipGetLastError());
     cp.mtot = mtot;
@@ -1568,7 +1591,7 @@ static bool pool_domain(const part::Layout& L) { return L.sbits == part::kSliceB
 static void cells_build(capsmi_session* s, RelPart& rp, const RelPartHop1* h1);
 
 void relpart_build(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms, int nt,
-                   int64_t lo, int64_t hi, RelPart& rp, const RelPartHop1* h1, bool unpacked) {
+                   int64_t lo, int64_t hi, RelPart& rp, const RelPartHop1* h1, bool unpacked, const NarrowRel* nar) {
     REQUIRE(hi > lo && (uint64_t)(hi - lo) <= (uint64_t(1) << 30), CAPSMI_ERR_UNSUPPORTED,
             "partitioned layout needs an id domain of at most 2^30 ids");
     using namespace part;
@@ -1599,7 +1622,7 @@ void relpart_build(capsmi_session* s, const int64_t* const* srcs, const int64_t*
     // k_chunk_hist make them (cells_build)
     // and hop 1 reads no sources: the pool is split (CAPSMI_POOL), so it streams the target words alone
     chunk_partition(s, srcs, dsts, ms, nt, false, L, (int64_t)s->num_cus * (fuse ? 1 : 2), cp, !pool_hop,
-                    pool_hop && s->cfg.pool_split);
+                    pool_hop && s->cfg.pool_split, nar);
     rp.cells = false;
     rp.sel = -1;
     rp.kept = -1;  // known on the device (boff[ncells]); read only when asked (relpart_kept)

@@ -1117,7 +1117,7 @@ void var_length4(capsmi_session* s, const int64_t* const* srcs, const int64_t* c
 // rows (a, count) of the fused var-length grouped count; returns the table's row count
 int64_t var_length_count(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
                          int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower, int upper,
-                         Buf& out_ids, Buf& out_cnt) {
+                         Buf& out_ids, Buf& out_cnt, const NarrowRel* nar) {
     using namespace varlen;
     hipStream_t st = s->stream;
     const int64_t n = b_ok->hi - b_ok->lo;
@@ -1147,7 +1147,7 @@ int64_t var_length_count(capsmi_session* s, const int64_t* const* srcs, const in
         ChunkPart cp, ct;
         {
             KernelTimer kt(s, "varlen_part");
-            chunk_partition(s, srcs, dsts, ms, nt, true, L, s->num_cus, cp, false);
+            chunk_partition(s, srcs, dsts, ms, nt, true, L, s->num_cus, cp, false, false, nar);
         }
         const ChunkWalk cw{P<uint2>(cp.pool), P<unsigned long long>(cp.meta), cp.order, cp.jst, cp.segbase, cp.ja, L.nt};
         const unsigned g = (unsigned)cp.g2;
@@ -1164,7 +1164,7 @@ int64_t var_length_count(capsmi_session* s, const int64_t* const* srcs, const in
             // LDS while k_vl_bset builds it), so a slice with more pairs gets 2^sublog regions, one
             // more k_vl_bset pass each
             KernelTimer kt(s, "varlen_rev");
-            chunk_partition(s, srcs, dsts, ms, nt, false, L, s->num_cus, ct, false);
+            chunk_partition(s, srcs, dsts, ms, nt, false, L, s->num_cus, ct, false, false, nar);
             const int64_t per_slice = (mtot + L.nt - 1) / L.nt;
             // 8 bits per pair (config CAPSMI_VL_BITS), in 2^sublog regions of <= 2^20 bits per slice
             const int64_t bits_per = s->cfg.vl_bits;

@@ -104,8 +104,61 @@ __device__ __forceinline__ int item_off(int u) {
     return 2 * ((u >> 1) * B + (int)threadIdx.x) + (u & 1);
 }
 
+// The same for 32-bit ids (the endpoint columns' narrow copies, Column::narrow): a 16-byte load is four
+// consecutive relationships, load k of the tile at offset 4 * (k * B + lane).  Also the item order of the
+// 4-items-per-load walks over packed words (k_part.hip).
+template <int B>
+__device__ __forceinline__ int item_off4(int u) {
+    return 4 * ((u >> 2) * B + (int)threadIdx.x) + (u & 3);
+}
+// item u of a tile of ids of type IdT
+template <int B, typename IdT>
+__device__ __forceinline__ int tile_item_off(int u) {
+    return sizeof(IdT) == 4 ? item_off4<B>(u) : item_off<B>(u);
+}
+
+// An endpoint relative to the layout's window, in 64 bits whatever the id's width: an id outside the window on
+// either side gives a value >= hi - lo (the subtraction wraps like the int64 one).  A narrow word w stands for
+// the id base + w, and the host hands pass 1 the window shifted by -base (chunk_partition), so w - lo is
+// id - (the window's lo) with no further term.
+template <typename IdT>
+__device__ __forceinline__ uint64_t rel_id(IdT x, int64_t lo) {
+    return (uint64_t)x - (uint64_t)lo;  // uint32_t zero-extends, int64_t converts modulo 2^64
+}
+
 // Issue all of a tile's loads before any test: with a branch around each load the compiler
 // waits for every load before issuing the next.  `vec` = both columns 16-byte aligned.
+template <int B, bool NTL = false, int N>
+__device__ __forceinline__ void load_tile(const uint32_t* __restrict__ src, const uint32_t* __restrict__ dst, int64_t t0,
+                                          int64_t m, bool vec, uint32_t (&sr)[N], uint32_t (&tr)[N]) {
+    static_assert(N % 4 == 0, "four 32-bit ids per load");
+    typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));
+    const uint32_t* __restrict__ sp = src + t0;  // wave-uniform bases, 32-bit lane offsets
+    const uint32_t* __restrict__ dp = dst + t0;
+    if (vec && t0 + B * N <= m) {  // t0 is a multiple of the tile, so the tile starts 16-byte aligned like the columns
+        const v4u32* __restrict__ sv = reinterpret_cast<const v4u32*>(sp);
+        const v4u32* __restrict__ dv = reinterpret_cast<const v4u32*>(dp);
+#pragma unroll
+        for (int k = 0; k < N / 4; ++k) {
+            const v4u32 a = NTL ? __builtin_nontemporal_load(sv + k * B + (int)threadIdx.x) : sv[k * B + (int)threadIdx.x];
+            const v4u32 b = NTL ? __builtin_nontemporal_load(dv + k * B + (int)threadIdx.x) : dv[k * B + (int)threadIdx.x];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                sr[4 * k + e] = a[e];
+                tr[4 * k + e] = b[e];
+            }
+        }
+    } else {
+        const int last = (int)(min(m - t0, (int64_t)B * N) - 1);
+#pragma unroll
+        for (int u = 0; u < N; ++u) {
+            const int i = min(item_off4<B>(u), last);
+            sr[u] = sp[i];
+            tr[u] = dp[i];
+        }
+    }
+}
+
 template <int B, bool NTL = false, int N>
 __device__ __forceinline__ void load_tile(const int64_t* __restrict__ src, const int64_t* __restrict__ dst, int64_t t0,
                                           int64_t m, bool vec, int64_t (&sr)[N], int64_t (&tr)[N]) {
@@ -600,9 +653,11 @@ __device__ __forceinline__ bool owns_slice(const ChunkWalk& cw, int j) {
 // layout); callers whose consumers walk the pool pass false.
 // want_split: ask for the split pool (part::split_t; cp.split says whether the build took it: only without the
 // cell counts and where the whole-line pass 1 fits with 32-pair lines)
+// nar: per table its 32-bit endpoint form (NarrowRel, capsmi_impl.h), read instead of srcs / dsts where set;
+// null: every table is read as int64.  Tables of one pool may differ.
 void chunk_partition(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
                      int nt, bool swap, const part::Layout& L, int64_t g2, ChunkPart& cp, bool want_hist,
-                     bool want_split = false);
+                     bool want_split = false, const NarrowRel* nar = nullptr);
 // the ordering half of chunk_partition for a pool another kernel filled (cp.meta: bucket | fill << 32)
 void chunk_order(capsmi_session* s, int nt, int64_t pool_chunks, int64_t g2, ChunkPart& cp);
 

@@ -24,6 +24,7 @@
 #include <set>
 
 #include "capsmi_impl.h"
+#include "narrow_rule.h"
 
 namespace capsmi {
 
@@ -1652,6 +1653,7 @@ bool fused_var_length(capsmi_session* s, const capsmi_table* in, const PlanNode&
         c.data = ids;
         c.offset = 0;
         c.host.reset();
+        c.narrow.reset();
     }
     (*out)->partitioned = g_dist.on && g_dist.world > 1;  // the rows of this rank's owned start nodes
     route(s, "var_length");
@@ -1822,6 +1824,50 @@ bool try_fused_shapes(capsmi_table* t, capsmi_table** out) {
 
 }  // namespace
 
+// The 32-bit copies of a registered relationship table's endpoint columns (Column::narrow; the rule:
+// narrow_rule.h), base = the window's lo.  A storage encoding of the table, which no query shapes: made once, here,
+// in one pass over both columns on the session's stream, and carried by every later view of the columns.
+// Costs 8 B per relationship of device memory.  CAPSMI_NARROW=off: none.
+static void narrow_endpoints(capsmi_table* t, const EntityInfo& e) {
+    if (e.kind != 2 || !t->sess || !t->sess->cfg.narrow || t->lazy()) return;
+    Column& sc = t->cols[e.src];
+    Column& dc = t->cols[e.dst];
+    if (sc.type != CAPSMI_I64 || dc.type != CAPSMI_I64 || sc.lazy_nullable || dc.lazy_nullable) return;
+    if (!narrow_eligible(sc.valid != nullptr, dc.valid != nullptr, t->nrows, e.lo, e.hi)) return;
+    capsmi_session* s = t->sess;
+    HIP_CHECK(hipSetDevice(s->device));
+    // each copy under its column's own row offset (a table registered behind a skip), so n32() applies it like d()
+    try {
+        sc.narrow = dev_alloc(sizeof(uint32_t) * (size_t)(sc.offset + t->nrows), s);
+        dc.narrow = dev_alloc(sizeof(uint32_t) * (size_t)(dc.offset + t->nrows), s);
+    } catch (const Error& x) {
+        // the copies are optional: a table that leaves no room for them is registered without (every reader
+        // then takes the int64 columns, and narrow_built does not count it)
+        if (x.code != CAPSMI_ERR_OUT_OF_MEMORY) throw;
+        sc.narrow.reset();
+        dc.narrow.reset();
+        return;
+    }
+    sc.narrow_of = sc.data.get();
+    dc.narrow_of = dc.data.get();
+    sc.narrow_base = dc.narrow_base = e.lo;
+    narrow_pair_i64(s, sc.d(), dc.d(), t->nrows, e.lo, P<uint32_t>(sc.narrow) + sc.offset,
+                    P<uint32_t>(dc.narrow) + dc.offset);
+    s->routes["narrow_built"] += 1;
+}
+
+NarrowRel narrow_rel(const capsmi_session* s, const Column& sc, const Column& dc) {
+    NarrowRel r;
+    if (!s->cfg.narrow) return r;
+    const uint32_t *a = sc.n32(), *b = dc.n32();
+    if (a && b && sc.narrow_base == dc.narrow_base) {
+        r.s = a;
+        r.d = b;
+        r.base = sc.narrow_base;
+    }
+    return r;
+}
+
 void attach_entity(capsmi_table* t, int kind, int64_t lo, int64_t hi, bool ids_exact, bool ids_unique) {
     auto e = std::make_shared<EntityInfo>();
     e->kind = kind;
@@ -1836,6 +1882,7 @@ void attach_entity(capsmi_table* t, int kind, int64_t lo, int64_t hi, bool ids_e
     e->ids_exact = ids_exact;
     e->ids_unique = ids_exact || ids_unique;
     t->entity = e;
+    narrow_endpoints(t, *e);
 }
 
 // ============================ operator-by-operator execution, pruned ========================
@@ -2957,6 +3004,12 @@ static capsmi_table* register_entity(capsmi_table* t, int kind, const std::vecto
     o->nrows = t->nrows;
     o->cols = t->cols;
     o->entity = e;
+    try {
+        narrow_endpoints(o, *e);
+    } catch (...) {
+        delete o;
+        throw;
+    }
     return o;
 }
 

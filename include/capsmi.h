@@ -277,7 +277,8 @@ capsmi_status capsmi_session_sync(capsmi_session* s);
  * `name` is the knob's environment name (e.g. "CAPSMI_JOIN", "CAPSMI_COUNT"), `value` its text as the
  * environment would hold it, NULL = back to the environment's value at the time of the call (or the
  * default).  Unknown names and unparsable values are refused (CAPSMI_ERR_ILLEGAL_ARGUMENT).  The knobs and
- * their meaning: DESIGN.md §5a. */
+ * their meaning: DESIGN.md §5a.  Among them CAPSMI_NARROW = auto | off: whether capsmi_rel_table (below) keeps
+ * 32-bit copies of the endpoint columns and the partition's first pass reads them. */
 capsmi_status capsmi_session_set_config(capsmi_session* s, const char* name, const char* value);
 /* the same check without a session or device: CAPSMI_OK when capsmi_session_set_config would accept it */
 capsmi_status capsmi_config_check(const char* name, const char* value);
@@ -407,7 +408,14 @@ capsmi_status capsmi_table_column_device_ptr(const capsmi_table* t, int32_t col,
  *   node: [id, label flags..., properties sorted by name]
  *   rel:  [id, source, target, type flags..., properties sorted by name]     (EntityMapping.scala:50)
  * else CAPSMI_ERR_ILLEGAL_ARGUMENT.  The result shares the input's columns and is what the fused-path
- * recogniser (below) treats as a scanned entity table; registration records the id range. */
+ * recogniser (below) treats as a scanned entity table; registration records the id range.
+ * capsmi_rel_table also keeps, with the result's endpoint columns, a 32-bit copy of each (the value minus the
+ * smallest endpoint) when the table has rows and its endpoints span at most 2^32 ids: one pass over both
+ * columns at registration and 8 bytes of device memory per relationship, shared by every table derived from
+ * the result (select, rename, skip, limit, cache).  The partitioned 2-hop and var-length entry points read the
+ * copies in their first pass instead of the Long columns; results are the same.  CAPSMI_NARROW=off at
+ * registration keeps none; off at a query reads none.  Route counts (capsmi_session_route_count):
+ * "narrow_built" per table that got copies, "pass1_narrow" per first-pass launch that read them. */
 capsmi_status capsmi_node_table(capsmi_table* t, const char* id_col, int32_t nlabels, const char* const* label_cols,
                                 capsmi_table** out);
 capsmi_status capsmi_rel_table(capsmi_table* t, const char* id_col, const char* src_col, const char* dst_col,

@@ -1,6 +1,7 @@
 // Pass-1 microbenchmark (not shipped): times k_scatter_c / k_scatter_l against a copy floor with the same
 // access pattern (16-B loads of both int64 columns, packed 8-B pairs written linearly) on uniform
-// random (source, target) ids over 2^26.  Build: see scripts/p1bench.sh; run on the GPU box.
+// random (source, target) ids over 2^26; the *_n rows are the same kernels and floors over the columns'
+// 32-bit copies (8 B read + 8 B written per relationship).  Build: see scripts/p1bench.sh; run on the GPU box.
 #include "../cypher-for-apache-spark_amd/csrc/k_part.hip"
 
 #include <cstdio>
@@ -30,43 +31,37 @@ __global__ void k_gen(int64_t* __restrict__ a, int64_t* __restrict__ b, int64_t 
     }
 }
 
-// copy floor: same loads as pass 1, pairs written linearly with 16-B stores
-template <bool NTL, bool NTS>
-__global__ void __launch_bounds__(kP1Block) k_floor(const int64_t* __restrict__ src, const int64_t* __restrict__ dst,
+// the endpoint columns' 32-bit copies, as registration makes them (base 0 here)
+__global__ void k_narrow(const int64_t* __restrict__ a, const int64_t* __restrict__ b, int64_t m, uint32_t* __restrict__ oa,
+                         uint32_t* __restrict__ ob) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < m; i += (int64_t)gridDim.x * blockDim.x) {
+        oa[i] = (uint32_t)a[i];
+        ob[i] = (uint32_t)b[i];
+    }
+}
+
+// copy floor: same loads as pass 1 (load_tile: 16-B loads of both columns, int64 or their 32-bit copies), pairs
+// written linearly with 16-B stores -- 16 + 8 B per relationship, or 8 + 8 B over the copies
+template <bool NTL, bool NTS, typename IdT = int64_t>
+__global__ void __launch_bounds__(kP1Block) k_floor(const IdT* __restrict__ src, const IdT* __restrict__ dst,
                                                    int64_t m, uint2* __restrict__ out) {
-    int64_t sr[kItems], tr[kItems];
+    IdT sr[kItems], tr[kItems];
     const int64_t stride = (int64_t)gridDim.x * kP1Tile;
     int64_t t0 = (int64_t)blockIdx.x * kP1Tile;
-    typedef long long v2i64 __attribute__((ext_vector_type(2)));
-    auto ld = [&](int64_t b) {
-        const v2i64* sv = reinterpret_cast<const v2i64*>(src + b);
-        const v2i64* dv = reinterpret_cast<const v2i64*>(dst + b);
-#pragma unroll
-        for (int k = 0; k < kItems / 2; ++k) {
-            v2i64 a, c;
-            if (NTL) {
-                a = __builtin_nontemporal_load(sv + k * kP1Block + threadIdx.x);
-                c = __builtin_nontemporal_load(dv + k * kP1Block + threadIdx.x);
-            } else {
-                a = sv[k * kP1Block + threadIdx.x];
-                c = dv[k * kP1Block + threadIdx.x];
-            }
-            sr[2 * k] = a.x; sr[2 * k + 1] = a.y; tr[2 * k] = c.x; tr[2 * k + 1] = c.y;
-        }
-    };
-    if (t0 < m) ld(t0);
+    if (t0 < m) load_tile<kP1Block, NTL>(src, dst, t0, m, true, sr, tr);
     for (; t0 < m; t0 += stride) {
         uint4 v[kItems / 2];
 #pragma unroll
         for (int k = 0; k < kItems / 2; ++k)
             v[k] = make_uint4((uint32_t)sr[2 * k], (uint32_t)tr[2 * k], (uint32_t)sr[2 * k + 1], (uint32_t)tr[2 * k + 1]);
-        if (t0 + stride < m) ld(t0 + stride);
-        uint4* o = reinterpret_cast<uint4*>(out + t0);
+        if (t0 + stride < m) load_tile<kP1Block, NTL>(src, dst, t0 + stride, m, true, sr, tr);
 #pragma unroll
-        for (int k = 0; k < kItems / 2; ++k) {
+        for (int k = 0; k < kItems / 2; ++k) {  // items 2k and 2k + 1 are neighbours in both item orders
             typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));
             v4u32 w = {v[k].x, v[k].y, v[k].z, v[k].w};
-            v4u32* q = reinterpret_cast<v4u32*>(o) + k * kP1Block + threadIdx.x;
+            const int64_t at = t0 + tile_item_off<kP1Block, IdT>(2 * k);
+            if (at + 1 >= m) continue;
+            v4u32* q = reinterpret_cast<v4u32*>(out + at);
             if (NTS) __builtin_nontemporal_store(w, q); else *q = w;
         }
     }
@@ -114,6 +109,10 @@ int main(int argc, char** argv) {
     CK(hipMalloc(&src, 8 * m));
     CK(hipMalloc(&dst, 8 * m));
     hipLaunchKernelGGL(k_gen, dim3(4096), dim3(256), 0, 0, src, dst, m, bits);
+    uint32_t *src32, *dst32;
+    CK(hipMalloc(&src32, 4 * m));
+    CK(hipMalloc(&dst32, 4 * m));
+    hipLaunchKernelGGL(k_narrow, dim3(4096), dim3(256), 0, 0, src, dst, m, src32, dst32);
     Layout L;
     L.lo = 0;
     L.hi = int64_t(1) << bits;
@@ -126,7 +125,7 @@ int main(int argc, char** argv) {
         const char* name;
         const void* fn;
         int block, tile, gmul, floor;  // floor: 0 k_scatter_c, 1 copy floor, 2 k_scatter_l
-        bool hist, split;
+        bool hist, split, narrow;  // narrow: over the 32-bit copies (8 B read + 8 B written per relationship)
     };
     // the library's instantiations (chunk_partition) and the copy floors
     const V vs[] = {
@@ -136,6 +135,12 @@ int main(int argc, char** argv) {
         {"sl_split", (const void*)k_scatter_l<1024, 8, 4, false, true>, 1024, 8192, 1, 2, false, true},
         {"floor", (const void*)k_floor<false, false>, 1024, 8192, 1, 1, false, false},
         {"floor_ntls", (const void*)k_floor<true, true>, 1024, 8192, 1, 1, false, false},
+        {"sc_hist_n", (const void*)k_scatter_c<1024, 8, 4, false, true, uint32_t>, 1024, 8192, 1, 0, true, false, true},
+        {"sl_hist_n", (const void*)k_scatter_l<1024, 8, 4, true, false, false, false, uint32_t>, 1024, 8192, 1, 2, true, false, true},
+        {"sl_pairs_n", (const void*)k_scatter_l<1024, 8, 4, false, false, false, false, uint32_t>, 1024, 8192, 1, 2, false, false, true},
+        {"sl_split_n", (const void*)k_scatter_l<1024, 8, 4, false, true, false, false, uint32_t>, 1024, 8192, 1, 2, false, true, true},
+        {"floor_n", (const void*)k_floor<false, false, uint32_t>, 1024, 8192, 1, 1, false, false, true},
+        {"floor_ntls_n", (const void*)k_floor<true, true, uint32_t>, 1024, 8192, 1, 1, false, false, true},
     };
     const int nv = sizeof(vs) / sizeof(vs[0]);
     int64_t npool = 1;
@@ -154,7 +159,6 @@ int main(int argc, char** argv) {
     hipEvent_t e0, e1;
     CK(hipEventCreate(&e0));
     CK(hipEventCreate(&e1));
-    const double bytes = 24.0 * (double)m;
     int64_t* dcount;
     CK(hipMalloc(&dcount, 8));
     for (int v = 0; v < nv; ++v) {
@@ -162,24 +166,27 @@ int main(int argc, char** argv) {
         const size_t lds = vs[v].floor == 1 ? 0 : vs[v].floor == 2 ? scatter1l_lds(L.nt, L.ns, vs[v].hist, vs[v].block, vs[v].tile, vs[v].split)
                                                                 : scatter1_lds(L.nt, L.ns, vs[v].hist, vs[v].block, vs[v].tile);
         if (lds) CK(hipFuncSetAttribute(vs[v].fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        const double bytes = (vs[v].narrow ? 16.0 : 24.0) * (double)m;
+        const void* a0 = vs[v].narrow ? (const void*)src32 : (const void*)src;
+        const void* a1 = vs[v].narrow ? (const void*)dst32 : (const void*)dst;
         float best = 1e30f, sum = 0;
         for (int r = 0; r < 6; ++r) {
             CK(hipMemsetAsync(meta, 0, 8 * npool, 0));
             CK(hipEventRecord(e0, 0));
             if (vs[v].floor == 1) {
-                void* args[] = {&src, &dst, (void*)&m, &pool};
+                void* args[] = {&a0, &a1, (void*)&m, &pool};
                 CK(hipLaunchKernel(vs[v].fn, dim3(g), dim3(vs[v].block), args, 0, 0));
             } else if (vs[v].floor == 2) {
                 int swap = 0;
                 int64_t c0 = 0;
                 size_t trash = (size_t)npool * kCh;
-                void* args[] = {&src, &dst, (void*)&m, &L, &swap, &c0, &trash, &pool, &meta, &chist};
+                void* args[] = {&a0, &a1, (void*)&m, &L, &swap, &c0, &trash, &pool, &meta, &chist};
                 CK(hipLaunchKernel(vs[v].fn, dim3(g), dim3(vs[v].block), args, lds, 0));
             } else {
                 int swap = 0;
                 int64_t c0 = 0;
                 size_t trash = (size_t)npool * kCh;
-                void* args[] = {&src, &dst, (void*)&m, &L, &swap, &c0, &trash, &pool, &meta, &chist};
+                void* args[] = {&a0, &a1, (void*)&m, &L, &swap, &c0, &trash, &pool, &meta, &chist};
                 CK(hipLaunchKernel(vs[v].fn, dim3(g), dim3(vs[v].block), args, lds, 0));
             }
             CK(hipEventRecord(e1, 0));
