@@ -239,6 +239,8 @@ __device__ __forceinline__ int p1l_lane() {
 constexpr int kLine = 16;       // pairs per 128-byte line
 constexpr int kLineSplit = 32;  // words per 128-byte line of the split pool's arrays
 __host__ __device__ constexpr int p1_line(bool split) { return split ? kLineSplit : kLine; }
+constexpr int kStageGroup = 4;  // staged pairs per lane and step of the split pool's store loop (two 16-byte stores)
+__host__ __device__ constexpr int p1_pad(bool split) { return split ? kStageGroup : 0; }
 
 template <int LN>
 __device__ __forceinline__ uint32_t held(uint32_t o, uint32_t f) { return o == kNone ? 0u : (f & (LN - 1)); }
@@ -304,8 +306,10 @@ static_assert(kCh / kLine < 1024 && kCh / kLineSplit < 1024 && kCh < 65536, "p1l
 
 // wave 0: run starts `loc` of this tile (exclusive scan over each slice's staged sequence = held
 // items + run), where each run itself starts (base = loc + held), the chunks its runs open (p1, opened,
-// misc[0]), the store loop's per-slice words (Q) and the staged total (misc[2])
-template <int LN>
+// misc[0]), the store loop's per-slice words (Q) and the staged total (misc[2]).  G is the store loop's group:
+// every slice's staged length is rounded up to a multiple of it, so each loc is one and misc[2] is the padded
+// total (kStageGroup for the split pool, whose store loop takes four staged pairs per lane; 1 otherwise).
+template <int LN, int G>
 __device__ __forceinline__ void p1l_plan(int nb, const uint32_t* cn, uint32_t* loc, const uint32_t* ph,
                                          const uint32_t* fl, uint32_t* p1, uint32_t* opened, uint32_t* misc,
                                          uint32_t* base, uint4* Q) {
@@ -314,7 +318,7 @@ __device__ __forceinline__ void p1l_plan(int nb, const uint32_t* cn, uint32_t* l
     uint32_t sum = 0, need = 0;
     for (int i = b0; i < b1; ++i) {
         const uint32_t c = cn[i];
-        sum += c + held<LN>(ph[i], fl[i]);
+        sum += (c + held<LN>(ph[i], fl[i]) + (G - 1)) & ~(uint32_t)(G - 1);
         need += (c && (ph[i] == kNone || fl[i] + c > (uint32_t)kCh)) ? 1u : 0u;
     }
     const uint32_t is = wave_incl_scan(sum), in = wave_incl_scan(need);
@@ -331,7 +335,7 @@ __device__ __forceinline__ void p1l_plan(int nb, const uint32_t* cn, uint32_t* l
         }
         p1[i] = np;
         Q[i] = p1l_pack<LN>(pre, c, o, f, np);
-        pre += c + held<LN>(o, f);
+        pre += (c + held<LN>(o, f) + (G - 1)) & ~(uint32_t)(G - 1);
     }
     if (lane == 63) {
         misc[0] = in;
@@ -340,8 +344,10 @@ __device__ __forceinline__ void p1l_plan(int nb, const uint32_t* cn, uint32_t* l
     wave_lds_order();
 }
 
+// (the split pool's stage has kStageGroup more entries per slice: each staged length is padded to a multiple of it;
+// a whole group and not kStageGroup - 1, so that `hold` and `Q` stay 16-byte aligned for every nb)
 __host__ __device__ constexpr size_t scatter1l_lds(int nb, int ns, bool hist, int block, int tile, bool split = false) {
-    return sizeof(uint2) * ((size_t)tile + (size_t)nb * (2 * p1_line(split))) +
+    return sizeof(uint2) * ((size_t)tile + (size_t)nb * (2 * p1_line(split) + p1_pad(split))) +
            sizeof(uint32_t) * ((hist ? (size_t)nb * hist_words(ns) : 0) + 12 * (size_t)nb + block / 64 + 4);
 }
 
@@ -354,6 +360,8 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_l(const IdT* __restrict__ s
                                                       uint32_t* __restrict__ chist) {
     constexpr int T = B * IT;
     constexpr int kLine = p1_line(SPLIT);  // the instantiation's line, in pairs
+    constexpr int kG = SPLIT ? kStageGroup : 1;  // staged pairs per lane and step of the store loop
+    static_assert(kG == 1 || (kLine % kG == 0 && kG * sizeof(uint2) == 32), "a group is two 16-byte words of a line");
     static_assert(T <= kCh && kCh % kLine == 0, "a pass-1 run must span at most two chunks");
     static_assert(!(SPLIT && HIST), "the split pool is built without the cell counts");
     extern __shared__ __attribute__((aligned(16))) unsigned long long smem[];
@@ -371,8 +379,9 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_l(const IdT* __restrict__ s
             pool[(size_t)q * kCh + pos] = p;
         }
     };
-    uint2* stage = reinterpret_cast<uint2*>(smem);    // T + nb * kLine: runs behind their held items
-    uint2* hold = stage + T + (size_t)nb * kLine;      // nb x kLine held items
+    // T + nb * (kLine + p1_pad): runs behind their held items, each slice's length padded to a multiple of kG
+    uint2* stage = reinterpret_cast<uint2*>(smem);
+    uint2* hold = stage + T + (size_t)nb * (kLine + p1_pad(SPLIT));  // nb x kLine held items
     uint4* Q = reinterpret_cast<uint4*>(hold + (size_t)nb * kLine);  // p1l_pack, 16-byte aligned
     uint32_t* H = reinterpret_cast<uint32_t*>(Q + nb);
     uint32_t* cnt = H + (HIST ? (size_t)nb * hw : 0);
@@ -426,7 +435,7 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_l(const IdT* __restrict__ s
         if (threadIdx.x < 64) {
             if (pending)
                 p1l_settle<HIST, kLine>(L, hw, stage, H, cnt + (par ^ 1) * nb, loc, ph, fl, p1, opened, misc, cmeta, chist);
-            p1l_plan<kLine>(nb, cn, loc, ph, fl, p1, opened, misc, base, Q);
+            p1l_plan<kLine, kG>(nb, cn, loc, ph, fl, p1, opened, misc, base, Q);
         }
         __syncthreads();
         pending = true;
@@ -439,8 +448,44 @@ __global__ void __launch_bounds__(B, MINW) k_scatter_l(const IdT* __restrict__ s
         for (int u = 0; u < IT; ++u)
             if ((valid >> u) & 1u) stage[base[pr[u].y >> L.tbits] + rk[u]] = pr[u];
         __syncthreads();
+        // The split pool: a lane takes kG = 4 staged pairs (two 16-byte LDS reads), one Q[b] and one decode for the
+        // group, and stores the four target words and the four source words with one 16-byte store each (the same
+        // bytes as one pair per lane, in a quarter of the store instructions and of the decodes).  A group needs
+        // no per-item decision: every loc is a multiple of 4 (p1l_plan pads each slice's staged length), so r and
+        // pos are; w, room, both cuts and kCh are multiples of 32.  The group therefore lies wholly in the open
+        // chunk or wholly in the opened one, and wholly below the cut or wholly at or above it.  Padding is the
+        // last 1..3 entries of a slice's sequence whose length is no multiple of 4: that group's first pair is
+        // real (so b is the slice's), the sequence's end is then no multiple of 32, the cut lies below the group
+        // and the group is held; its padding lands in hold slots past the held count, which nobody reads
+        // (pos - cut <= 28, inside the slice's line of hold).
+        if (SPLIT) {
+            typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));  // one LDS / global access each
+            const v4u32* stage4 = reinterpret_cast<const v4u32*>(stage);
+            for (uint32_t idx = kG * threadIdx.x; idx < total; idx += kG * B) {
+                // the pairs (a.x, a.y) (a.z, a.w) (c.x, c.y) (c.z, c.w)
+                const v4u32 a = stage4[idx / 2], c = stage4[idx / 2 + 1];
+                const int b = min((int)(a.y >> L.tbits), nb - 1);
+                const uint4 q = Q[b];
+                const uint32_t r = idx - (q.x & 0xFFFFu), room = q.x >> 16, w = (q.y & 1023u) * kLine;
+                const bool first = r < room;
+                const uint32_t pos = first ? w + r : r - room;
+                const uint32_t cut = ((first ? q.y >> 10 : q.y >> 20) & 1023u) * kLine;
+                if (pos < cut) {
+                    uint32_t* tw = reinterpret_cast<uint32_t*>(pool + (size_t)(first ? q.z : q.w) * kCh) + pos;
+                    const v4u32 t = {a.y | (a.x == a.y ? kLoopBit : 0u), a.w | (a.z == a.w ? kLoopBit : 0u),
+                                     c.y | (c.x == c.y ? kLoopBit : 0u), c.w | (c.z == c.w ? kLoopBit : 0u)};
+                    const v4u32 s = {a.x, a.z, c.x, c.z};
+                    *reinterpret_cast<v4u32*>(tw) = t;
+                    *reinterpret_cast<v4u32*>(tw + kCh) = s;
+                } else {
+                    v4u32* h = reinterpret_cast<v4u32*>(hold + b * kLine + (pos - cut));
+                    h[0] = a;
+                    h[1] = c;
+                }
+            }
+        }
         // staged item r of slice b lands as p1l_pack lays out; one 16-byte LDS read per item
-        for (uint32_t idx = threadIdx.x; idx < (uint32_t)(T + nb * kLine); idx += B) {
+        for (uint32_t idx = threadIdx.x; !SPLIT && idx < (uint32_t)(T + nb * kLine); idx += B) {
             const uint2 p = stage[idx];
             const int b = min((int)(p.y >> L.tbits), nb - 1);
             const uint4 q = Q[b];

@@ -1,7 +1,8 @@
 // Pass-1 microbenchmark (not shipped): times k_scatter_c / k_scatter_l against a copy floor with the same
 // access pattern (16-B loads of both int64 columns, packed 8-B pairs written linearly) on uniform
 // random (source, target) ids over 2^26; the *_n rows are the same kernels and floors over the columns'
-// 32-bit copies (8 B read + 8 B written per relationship).  Build: see scripts/p1bench.sh; run on the GPU box.
+// 32-bit copies (8 B read + 8 B written per relationship); floor_split1_n / floor_split4_n write the split pool's
+// two word arrays with 4-byte and with 16-byte stores.  Build: see scripts/p1bench.sh; run on the GPU box.
 #include "../cypher-for-apache-spark_amd/csrc/k_part.hip"
 
 #include <cstdio>
@@ -63,6 +64,47 @@ __global__ void __launch_bounds__(kP1Block) k_floor(const IdT* __restrict__ src,
             if (at + 1 >= m) continue;
             v4u32* q = reinterpret_cast<v4u32*>(out + at);
             if (NTS) __builtin_nontemporal_store(w, q); else *q = w;
+        }
+    }
+}
+
+// Store-shape floors of the split pool over k_floor's loads: the same 8 B read and 8 B written per relationship,
+// the target words into one array and the source words into another (both linear).  G = 1: one 4-byte store per
+// pair and array, a wave-instruction writing 256 contiguous bytes, as the split store loop issued them before it
+// took groups; G = 4: one 16-byte store per four pairs and array, as it issues them now.  Their difference is
+// what the store shape alone owns.
+template <int G, typename IdT>
+__global__ void __launch_bounds__(kP1Block) k_floor_split(const IdT* __restrict__ src, const IdT* __restrict__ dst,
+                                                         int64_t m, uint2* __restrict__ out) {
+    static_assert(G == 1 || G == 4, "one word or one 16-byte store per array");
+    typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));
+    IdT sr[kItems], tr[kItems];
+    uint32_t* tw = reinterpret_cast<uint32_t*>(out);
+    uint32_t* sw = tw + ((m + 3) & ~int64_t(3));
+    const int64_t stride = (int64_t)gridDim.x * kP1Tile;
+    int64_t t0 = (int64_t)blockIdx.x * kP1Tile;
+    if (t0 < m) load_tile<kP1Block, false>(src, dst, t0, m, true, sr, tr);
+    for (; t0 < m; t0 += stride) {
+        uint32_t x[kItems], y[kItems];
+#pragma unroll
+        for (int k = 0; k < kItems; ++k) {
+            x[k] = (uint32_t)sr[k];
+            y[k] = (uint32_t)tr[k] | (sr[k] == tr[k] ? kLoopBit : 0u);
+        }
+        if (t0 + stride < m) load_tile<kP1Block, false>(src, dst, t0 + stride, m, true, sr, tr);
+#pragma unroll
+        for (int k = 0; k < kItems / G; ++k) {  // lane i takes positions G * (k * B + i) ... + G - 1 of the tile
+            const int64_t at = t0 + (int64_t)G * (k * kP1Block + (int)threadIdx.x);
+            if (at + G > m) continue;
+            if (G == 1) {
+                tw[at] = y[k];
+                sw[at] = x[k];
+            } else {
+                const v4u32 t = {y[4 * k], y[4 * k + 1], y[4 * k + 2], y[4 * k + 3]};
+                const v4u32 s = {x[4 * k], x[4 * k + 1], x[4 * k + 2], x[4 * k + 3]};
+                *reinterpret_cast<v4u32*>(tw + at) = t;
+                *reinterpret_cast<v4u32*>(sw + at) = s;
+            }
         }
     }
 }
@@ -141,6 +183,8 @@ int main(int argc, char** argv) {
         {"sl_split_n", (const void*)k_scatter_l<1024, 8, 4, false, true, false, false, uint32_t>, 1024, 8192, 1, 2, false, true, true},
         {"floor_n", (const void*)k_floor<false, false, uint32_t>, 1024, 8192, 1, 1, false, false, true},
         {"floor_ntls_n", (const void*)k_floor<true, true, uint32_t>, 1024, 8192, 1, 1, false, false, true},
+        {"floor_split1_n", (const void*)k_floor_split<1, uint32_t>, 1024, 8192, 1, 1, false, false, true},
+        {"floor_split4_n", (const void*)k_floor_split<4, uint32_t>, 1024, 8192, 1, 1, false, false, true},
     };
     const int nv = sizeof(vs) / sizeof(vs[0]);
     int64_t npool = 1;
