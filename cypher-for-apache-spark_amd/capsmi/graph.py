@@ -239,6 +239,13 @@ class TriGraph:
         _lib.call("capsmi_trigraph_count", self.session.handle, self._h, part, nparts, ctypes.byref(v))
         return v.value
 
+    def count_by_node(self, id_name: str = "id", count_name: str = "count") -> GpuTable:
+        """``... RETURN id(a), count(*)``: one row (id, count) per node with a non-zero count, unordered."""
+        out = ctypes.c_void_p()
+        _lib.call("capsmi_trigraph_count_by_node", self.session.handle, self._h, id_name.encode(), count_name.encode(),
+                  ctypes.byref(out))
+        return GpuTable(self.session, out)
+
     def stats(self):
         """(id-domain size, oriented simple edges)"""
         n, ne = ctypes.c_int64(), ctypes.c_int64()
@@ -266,6 +273,16 @@ def triangle_count(session: Session, rels: Sequence[GpuTable], n_ok: NodeBitmap,
     _lib.call("capsmi_triangle_count", session.handle, len(rels), _handles(rels), src_col.encode(), dst_col.encode(),
               n_ok.handle, ctypes.byref(v))
     return v.value
+
+
+def triangle_count_by_node(session: Session, rels: Sequence[GpuTable], n_ok: NodeBitmap, id_name: str = "id",
+                           count_name: str = "count", src_col: str = "source", dst_col: str = "target") -> GpuTable:
+    """``MATCH (a)-[r1]->(b)-[r2]->(c)-[r3]->(a) RETURN id(a), count(*)`` (pairwise-distinct relationships):
+    one row per node with a non-zero count, unordered.  Grouping by b or by c gives the same rows."""
+    out = ctypes.c_void_p()
+    _lib.call("capsmi_triangle_count_by_node", session.handle, len(rels), _handles(rels), src_col.encode(),
+              dst_col.encode(), n_ok.handle, id_name.encode(), count_name.encode(), ctypes.byref(out))
+    return GpuTable(session, out)
 
 
 class RelPartition:

@@ -2258,6 +2258,44 @@ capsmi_status capsmi_triangle_count(capsmi_session* s, int32_t nrels, capsmi_tab
     return st;
 }
 
+capsmi_status capsmi_trigraph_count_by_node(capsmi_session* s, const capsmi_trigraph* g, const char* id_name,
+                                            const char* count_name, capsmi_table** out) {
+    API_BEGIN
+    need(s, "session");
+    need(g, "trigraph");
+    need(out, "out");
+    need(id_name, "id_name");
+    need(count_name, "count_name");
+    REQUIRE(std::string(id_name) != count_name, CAPSMI_ERR_ILLEGAL_ARGUMENT, "output names must differ");
+    use_device(s);
+    Buf ids, cnt;
+    const int64_t rows = tri_count_by_node(s, g->g, ids, cnt);
+    add_i64(P<int64_t>(ids), g->g.lo, rows, s->stream);  // relative ids -> the graph's
+    auto* o = new_table(s, rows);
+    Column a, c;
+    a.name = id_name;
+    a.type = CAPSMI_I64;
+    a.data = ids;
+    c.name = count_name;
+    c.type = CAPSMI_I64;
+    c.data = cnt;
+    o->cols.push_back(std::move(a));
+    o->cols.push_back(std::move(c));
+    *out = o;
+    API_END
+}
+
+capsmi_status capsmi_triangle_count_by_node(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                            const char* src_col, const char* dst_col, const capsmi_bitmap* n_ok,
+                                            const char* id_name, const char* count_name, capsmi_table** out) {
+    capsmi_trigraph* g = nullptr;
+    capsmi_status st = capsmi_trigraph_build(s, nrels, rels, src_col, dst_col, n_ok, &g);
+    if (st != CAPSMI_OK) return st;
+    st = capsmi_trigraph_count_by_node(s, g, id_name, count_name, out);
+    capsmi_trigraph_release(g);
+    return st;
+}
+
 capsmi_status capsmi_relpart_size(const capsmi_relpart* p, int64_t* kept_rows) {
     API_BEGIN
     need(p, "relpart");

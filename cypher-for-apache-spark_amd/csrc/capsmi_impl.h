@@ -593,8 +593,9 @@ struct TriGraph {
     // in cb bits each above it (all-ones: read ov); ids are the degree order (0 = highest (degree, id))
     Buf tg;
     int ib = 0, cb = 0;
-    Buf orig;         // int64 per vertex: relative id of the degree-order id (unused by the count)
+    Buf orig;         // int64 per vertex: relative id of the degree-order id (unused by the count; the per-node rows' ids)
     Buf ek, ev, sl;   // undirected keys / payload (pair terms), self-loop counts
+    bool sl_relative = false;  // sl is indexed by relative id (the sorted build, as its ek) -- else by degree-order id
     Buf pair;         // the direct build: the pair terms' sum (u64), added up while the runs are written
     Buf small_u, big_u;  // vertices with out-degree in [2, 64] / above 64
     int64_t nsmall = 0, nbig = 0;
@@ -631,6 +632,9 @@ struct TriDist {
 void tri_build(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms, int nt,
                const capsmi_bitmap* n_ok, TriGraph& g, const TriDist* dd = nullptr);
 uint64_t tri_count(capsmi_session* s, const TriGraph& g, int part, int nparts);
+// the count grouped by the start node (k_tri_grouped.hip): rows (relative id, count) of the nodes with a
+// non-zero count over a single-device trigraph, unordered; returns their number
+int64_t tri_count_by_node(capsmi_session* s, const TriGraph& g, Buf& ids, Buf& counts);
 
 // undirected Expand patterns (k_undirected.hip): hops 1 or 2; kind 0 count(*), 1 count(DISTINCT end),
 // 2 count(DISTINCT start); c unused for one hop.  marks (kinds 1, 2; b's nwords words): the distinct ids'

@@ -16,6 +16,7 @@
 #include <algorithm>
 
 #include "capsmi_impl.h"
+#include "tri_code.h"
 
 namespace capsmi {
 namespace tri {
@@ -184,12 +185,6 @@ __global__ void k_rank_ids(const uint64_t* __restrict__ by_order, int64_t n, uin
         orig[r] = v;
     }
 }
-
-struct TgCode {
-    uint32_t ib, cb;  // id bits, code bits per direction (0: every payload is an exception)
-    __host__ __device__ uint32_t idmask() const { return ib >= 32 ? ~0u : (1u << ib) - 1u; }
-    __host__ __device__ uint32_t cmask() const { return (1u << cb) - 1u; }
-};
 
 // orient each undirected edge from the lower (degree, id) end -- towards the smaller degree-order id;
 // key = rid(from)<<32 | rid(to), payload = m(from,to)<<32 | m(to,from).
@@ -1029,22 +1024,7 @@ __device__ __forceinline__ bool btest(const uint32_t* bf, int bits, uint32_t w) 
     return (bf[x >> 5] >> (x & 31)) & 1u;
 }
 
-// Oriented targets carry their edge's multiplicities (`TgCode`): word = to | f << ib | b << (ib + cb),
-// f = m(from, to), b = m(to, from), cb bits each; a field at its all-ones value (cmask) marks an
-// exception whose exact payload is read from ov.  The wedge walks then resolve a hit from the two words
-// alone (a hit used to cost two dependent 8-byte payload loads: 47 of the 116 ms at C4, measured by a
-// run with the loads removed).  With 2^24 ids, cb = 4: < 1 % of the hits need an exact payload (R-MAT
-// s = 20 / 22, hits whose edges carry a multiplicity >= 15).
-
-__device__ __forceinline__ uint32_t tid(uint32_t word, TgCode c) { return word & c.idmask(); }
-
-// payload (f << 32 | b) of a coded word, or the exact one at ov[pos] for an exception
-__device__ __forceinline__ uint64_t tpay(uint32_t word, TgCode c, const int64_t* __restrict__ ov, int64_t pos) {
-    if (c.cb == 0) return (uint64_t)ov[pos];
-    const uint32_t f = (word >> c.ib) & c.cmask(), b = (word >> (c.ib + c.cb)) & c.cmask();
-    if (f == c.cmask() || b == c.cmask()) return (uint64_t)ov[pos];
-    return (uint64_t)f << 32 | b;
-}
+// (the coded oriented targets, `TgCode` / tid / tpay, and tri_weight: tri_code.h)
 
 // word (id + code bits; the id is the hash key), and the index of its entry in the hashed list (the
 // exact payload of an exception is read through it)
@@ -1072,13 +1052,6 @@ __device__ __forceinline__ int hfind(const uint32_t* hk, int log2cap, uint32_t w
         if ((k & idm) == w) return (int)sl;
         sl = (sl + 1) & mask;
     }
-}
-
-__device__ __forceinline__ unsigned long long tri_weight(uint64_t puv, uint64_t pvw, uint64_t puw) {
-    const uint64_t m_uv = puv >> 32, m_vu = puv & 0xffffffffULL;
-    const uint64_t m_vw = pvw >> 32, m_wv = pvw & 0xffffffffULL;
-    const uint64_t m_uw = puw >> 32, m_wu = puw & 0xffffffffULL;
-    return m_uv * m_vw * m_wu + m_uw * m_wv * m_vu;
 }
 
 struct SmallWave {
@@ -2122,6 +2095,7 @@ void tri_build(capsmi_session* s, const int64_t* const* srcs, const int64_t* con
         // the direction bit rides unsorted at bit 31 when max's digits end at or below bit 24
         const int msh = bits > 24 ? 1 : 0;
         g.sl = dev_alloc(sizeof(uint32_t) * n, s);
+        g.sl_relative = true;
         HIP_CHECK(hipMemsetAsync(P<void>(g.sl), 0, sizeof(uint32_t) * n, st));
         Buf key = dev_alloc(sizeof(uint64_t) * (m > 0 ? m : 1), s);
         {

@@ -1511,6 +1511,74 @@ bool fused_grouped_two_hop(capsmi_session* s, const capsmi_table* in, const Plan
     return true;
 }
 
+// C4's grouped form: the closed triangle grouped by one of its nodes, count(*).  The preconditions of the
+// triangle in fused_counts (three hops closing on position 0, one relationship set, pairwise-unique
+// relationships, one node filter for all three positions) make the pattern symmetric under rotation, so the
+// counts grouped by position 1 or 2 are the counts grouped by position 0 (k_tri_grouped.hip).  Single device.
+bool fused_grouped_triangle(capsmi_session* s, const capsmi_table* in, const PlanNode& g, const std::vector<Path>& B,
+                            capsmi_table** out) {
+    if (B.size() != 1 || g.a.size() != 1 || g.aggs.empty()) return false;
+    const Path& P = B[0];
+    Classified c;
+    if (any_no_loops(P) || !classify(P, c)) return false;
+    for (int x : P.pos_node) if (x < 0) return false;
+    if (P.hops.size() != 3 || P.pos_node.size() != 3 || !same_orientation(P)) return false;
+    const Hop &h0 = P.hops[0], &h1 = P.hops[1], &h2 = P.hops[2];
+    if (!(h0.from == 0 && h0.to == 1 && h1.from == 1 && h1.to == 2 && h2.from == 2 && h2.to == 0)) return false;
+    const int gc = find_col(in, g.a[0]);
+    if (gc < 0 || !id_like(P, P.cols[gc])) return false;
+    const int gp = position_of(P, P.cols[gc]);
+    if (gp < 0 || gp > 2) return false;
+    std::vector<int> kinds;
+    if (!agg_kinds(in, g, P, 0, 0, kinds)) return false;
+    for (int k : kinds) if (k != A_COUNT) return false;
+    std::vector<Path> one{P};
+    int64_t lo, hi;
+    if (!id_window(one, &lo, &hi) || g_dist.on) return false;  // (sets the id domain the views below read)
+    RelViews v0, v1, v2;
+    rel_views(P, h0, v0);
+    rel_views(P, h1, v1);
+    rel_views(P, h2, v2);
+    if (v1.sig != v0.sig || v2.sig != v0.sig || !all_pairs_unique(c, 3)) return false;
+    BitmapSet bs;
+    std::string k0, k1, k2;
+    capsmi_bitmap* a = node_bitmap(s, P, c, P.pos_node[0], lo, hi, bs, &k0);
+    capsmi_bitmap* b = node_bitmap(s, P, c, P.pos_node[1], lo, hi, bs, &k1);
+    capsmi_bitmap* cc = node_bitmap(s, P, c, P.pos_node[2], lo, hi, bs, &k2);
+    // one node filter for all three (a bitmap with an id in two scanned rows comes back null: node_bitmap)
+    if (!a || !b || !cc || k0 != k1 || k1 != k2) return false;
+    std::vector<const int64_t*> srcs, dsts;
+    std::vector<int64_t> ms;
+    for (capsmi_table* t : v0.t) {
+        srcs.push_back(t->cols[0].d());
+        dsts.push_back(t->cols[1].d());
+        ms.push_back(t->nrows);
+    }
+    Buf ids, cnt;
+    int64_t rows = 0;
+    {
+        TriGraph tg;
+        tri_build(s, srcs.data(), dsts.data(), ms.data(), (int)srcs.size(), a, tg);
+        rows = tri_count_by_node(s, tg, ids, cnt);
+    }
+    ids_to_long(s, lo, ::capsmi::P<int64_t>(ids), rows);
+    auto* r = result_table(s, rows);
+    std::unique_ptr<capsmi_table> guard(r);
+    Column k;
+    k.type = CAPSMI_I64;
+    k.data = ids;
+    r->cols.push_back(std::move(k));
+    for (size_t i = 0; i < kinds.size(); ++i) {  // every aggregate is the same count
+        Column v;
+        v.type = CAPSMI_I64;
+        v.data = cnt;
+        r->cols.push_back(std::move(v));
+    }
+    *out = guard.release();
+    route(s, "triangle_grouped");
+    return true;
+}
+
 // The var-length grouped count over BY_SOURCE shards: this rank owns the
 // start ids [rank * span, (rank + 1) * span) and holds their out-relationships (`views`) plus the
 // relationships into its owned ids from other ranks (the bases' in-shards, exchanged at registration).
@@ -1815,6 +1883,7 @@ bool try_fused_shapes(capsmi_table* t, capsmi_table** out) {
             return true;
         }
         if (fused_grouped_two_hop(s, in, p, B, out)) return true;
+        if (fused_grouped_triangle(s, in, p, B, out)) return true;
         return fused_var_length(s, in, p, B, out);
     }
     std::vector<Path> B;

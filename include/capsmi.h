@@ -687,6 +687,15 @@ capsmi_status capsmi_trigraph_stats(const capsmi_trigraph* g, int64_t* nodes, in
 capsmi_status capsmi_trigraph_release(capsmi_trigraph* g);
 capsmi_status capsmi_triangle_count(capsmi_session* s, int32_t nrels, capsmi_table* const* rels, const char* src_col,
                                     const char* dst_col, const capsmi_bitmap* n_ok, int64_t* out_rows);
+/* The same pattern grouped by its start: ... RETURN id(a), count(*) -- the bindings per start node (equally the
+ * counts per b or per c: the pattern is symmetric under rotation).  `*out` gets two non-nullable Long columns,
+ * the graph's own ids (`id_name`) and the counts (`count_name`), one row per node with a non-zero count, in
+ * no particular order.  Single device: a trigraph of a distributed build gives CAPSMI_ERR_UNSUPPORTED. */
+capsmi_status capsmi_trigraph_count_by_node(capsmi_session* s, const capsmi_trigraph* g, const char* id_name,
+                                            const char* count_name, capsmi_table** out);
+capsmi_status capsmi_triangle_count_by_node(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                            const char* src_col, const char* dst_col, const capsmi_bitmap* n_ok,
+                                            const char* id_name, const char* count_name, capsmi_table** out);
 /* count(*) of the 2-hop chain (capsmi_two_hop_count) on one rank of an owner(target) partition:
  * this rank's tables hold every relationship into its owned ids [own_lo, own_hi) (relative to the
  * bitmaps' lo).  begin partitions them and writes the owned ids' in-degrees inA (relationships from

@@ -289,6 +289,9 @@ trait CapsmiLib extends Library {
                                     a: Pointer, b: Pointer, c: Pointer, outDistinct: LongByReference): Int
   def capsmi_triangle_count(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String, dstCol: String, nOk: Pointer,
                             outRows: LongByReference): Int
+  def capsmi_trigraph_count_by_node(s: Pointer, g: Pointer, idName: String, countName: String, out: PointerByReference): Int
+  def capsmi_triangle_count_by_node(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String, dstCol: String,
+                                    nOk: Pointer, idName: String, countName: String, out: PointerByReference): Int
   def capsmi_undirected_count(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String, dstCol: String, hops: Int,
                               a: Pointer, b: Pointer, c: Pointer, kind: Int, out: LongByReference): Int
   def capsmi_var_length_count(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String, dstCol: String, a: Pointer,
