@@ -246,6 +246,20 @@ class TriGraph:
                   ctypes.byref(out))
         return GpuTable(self.session, out)
 
+    def count_transitive(self) -> int:
+        """``MATCH (a)-[r1]->(b)-[r2]->(c)<-[r3]-(a) RETURN count(*)`` over the same graph."""
+        v = ctypes.c_int64()
+        _lib.call("capsmi_trigraph_count_transitive", self.session.handle, self._h, ctypes.byref(v))
+        return v.value
+
+    def count_transitive_by_node(self, role: int, id_name: str = "id", count_name: str = "count") -> GpuTable:
+        """The transitive triangle grouped by the node in `role` (TRI_ROLE_SOURCE a, TRI_ROLE_MIDDLE b,
+        TRI_ROLE_SINK c): one row (id, count) per node with a non-zero count, unordered."""
+        out = ctypes.c_void_p()
+        _lib.call("capsmi_trigraph_count_transitive_by_node", self.session.handle, self._h, role, id_name.encode(),
+                  count_name.encode(), ctypes.byref(out))
+        return GpuTable(self.session, out)
+
     def stats(self):
         """(id-domain size, oriented simple edges)"""
         n, ne = ctypes.c_int64(), ctypes.c_int64()
@@ -282,6 +296,30 @@ def triangle_count_by_node(session: Session, rels: Sequence[GpuTable], n_ok: Nod
     out = ctypes.c_void_p()
     _lib.call("capsmi_triangle_count_by_node", session.handle, len(rels), _handles(rels), src_col.encode(),
               dst_col.encode(), n_ok.handle, id_name.encode(), count_name.encode(), ctypes.byref(out))
+    return GpuTable(session, out)
+
+
+# the roles of (a)-[r1]->(b)-[r2]->(c)<-[r3]-(a) (include/capsmi.h CAPSMI_TRI_ROLE_*)
+TRI_ROLE_SOURCE, TRI_ROLE_MIDDLE, TRI_ROLE_SINK = 0, 1, 2
+
+
+def triangle_count_transitive(session: Session, rels: Sequence[GpuTable], n_ok: NodeBitmap, src_col: str = "source",
+                              dst_col: str = "target") -> int:
+    """``MATCH (a)-[r1]->(b)-[r2]->(c)<-[r3]-(a) RETURN count(*)`` (pairwise-distinct relationships)."""
+    v = ctypes.c_int64()
+    _lib.call("capsmi_triangle_count_transitive", session.handle, len(rels), _handles(rels), src_col.encode(),
+              dst_col.encode(), n_ok.handle, ctypes.byref(v))
+    return v.value
+
+
+def triangle_count_transitive_by_node(session: Session, rels: Sequence[GpuTable], n_ok: NodeBitmap, role: int,
+                                      id_name: str = "id", count_name: str = "count", src_col: str = "source",
+                                      dst_col: str = "target") -> GpuTable:
+    """``MATCH (a)-[r1]->(b)-[r2]->(c)<-[r3]-(a) RETURN id(x), count(*)`` with x the node in `role`
+    (TRI_ROLE_SOURCE a, TRI_ROLE_MIDDLE b, TRI_ROLE_SINK c): one row per node with a non-zero count, unordered."""
+    out = ctypes.c_void_p()
+    _lib.call("capsmi_triangle_count_transitive_by_node", session.handle, len(rels), _handles(rels), src_col.encode(),
+              dst_col.encode(), n_ok.handle, role, id_name.encode(), count_name.encode(), ctypes.byref(out))
     return GpuTable(session, out)
 
 

@@ -2296,6 +2296,69 @@ capsmi_status capsmi_triangle_count_by_node(capsmi_session* s, int32_t nrels, ca
     return st;
 }
 
+capsmi_status capsmi_trigraph_count_transitive(capsmi_session* s, const capsmi_trigraph* g, int64_t* out_rows) {
+    API_BEGIN
+    need(s, "session");
+    need(g, "trigraph");
+    need(out_rows, "out");
+    use_device(s);
+    *out_rows = (int64_t)tri_trans_count(s, g->g);
+    API_END
+}
+
+capsmi_status capsmi_trigraph_count_transitive_by_node(capsmi_session* s, const capsmi_trigraph* g, int32_t role,
+                                                       const char* id_name, const char* count_name,
+                                                       capsmi_table** out) {
+    API_BEGIN
+    need(s, "session");
+    need(g, "trigraph");
+    need(out, "out");
+    need(id_name, "id_name");
+    need(count_name, "count_name");
+    REQUIRE(role >= CAPSMI_TRI_ROLE_SOURCE && role <= CAPSMI_TRI_ROLE_SINK, CAPSMI_ERR_ILLEGAL_ARGUMENT,
+            "role must be CAPSMI_TRI_ROLE_SOURCE, _MIDDLE or _SINK");
+    REQUIRE(std::string(id_name) != count_name, CAPSMI_ERR_ILLEGAL_ARGUMENT, "output names must differ");
+    use_device(s);
+    Buf ids, cnt;
+    const int64_t rows = tri_trans_count_by_node(s, g->g, role, ids, cnt);
+    add_i64(P<int64_t>(ids), g->g.lo, rows, s->stream);  // relative ids -> the graph's
+    auto* o = new_table(s, rows);
+    Column a, c;
+    a.name = id_name;
+    a.type = CAPSMI_I64;
+    a.data = ids;
+    c.name = count_name;
+    c.type = CAPSMI_I64;
+    c.data = cnt;
+    o->cols.push_back(std::move(a));
+    o->cols.push_back(std::move(c));
+    *out = o;
+    API_END
+}
+
+capsmi_status capsmi_triangle_count_transitive(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                               const char* src_col, const char* dst_col, const capsmi_bitmap* n_ok,
+                                               int64_t* out_rows) {
+    capsmi_trigraph* g = nullptr;
+    capsmi_status st = capsmi_trigraph_build(s, nrels, rels, src_col, dst_col, n_ok, &g);
+    if (st != CAPSMI_OK) return st;
+    st = capsmi_trigraph_count_transitive(s, g, out_rows);
+    capsmi_trigraph_release(g);
+    return st;
+}
+
+capsmi_status capsmi_triangle_count_transitive_by_node(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                                       const char* src_col, const char* dst_col,
+                                                       const capsmi_bitmap* n_ok, int32_t role, const char* id_name,
+                                                       const char* count_name, capsmi_table** out) {
+    capsmi_trigraph* g = nullptr;
+    capsmi_status st = capsmi_trigraph_build(s, nrels, rels, src_col, dst_col, n_ok, &g);
+    if (st != CAPSMI_OK) return st;
+    st = capsmi_trigraph_count_transitive_by_node(s, g, role, id_name, count_name, out);
+    capsmi_trigraph_release(g);
+    return st;
+}
+
 capsmi_status capsmi_relpart_size(const capsmi_relpart* p, int64_t* kept_rows) {
     API_BEGIN
     need(p, "relpart");

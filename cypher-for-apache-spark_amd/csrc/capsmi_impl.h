@@ -635,6 +635,10 @@ uint64_t tri_count(capsmi_session* s, const TriGraph& g, int part, int nparts);
 // the count grouped by the start node (k_tri_grouped.hip): rows (relative id, count) of the nodes with a
 // non-zero count over a single-device trigraph, unordered; returns their number
 int64_t tri_count_by_node(capsmi_session* s, const TriGraph& g, Buf& ids, Buf& counts);
+// the transitive triangle (a)->(b)->(c)<-(a) over a single-device trigraph (k_tri_trans.hip): count(*), and the
+// rows (relative id, count) of the nodes with a non-zero count in `role` (CAPSMI_TRI_ROLE_*), unordered
+uint64_t tri_trans_count(capsmi_session* s, const TriGraph& g);
+int64_t tri_trans_count_by_node(capsmi_session* s, const TriGraph& g, int role, Buf& ids, Buf& counts);
 
 // undirected Expand patterns (k_undirected.hip): hops 1 or 2; kind 0 count(*), 1 count(DISTINCT end),
 // 2 count(DISTINCT start); c unused for one hop.  marks (kinds 1, 2; b's nwords words): the distinct ids'

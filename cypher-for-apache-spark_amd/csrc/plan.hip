@@ -13,6 +13,9 @@
 //   Expand + node filters, count(*) ......................... expand count              ("expand_count")
 //   2 x Expand + uniqueness, count(*) / count(DISTINCT end) . two-hop kernels           ("two_hop")
 //   2 x Expand + ExpandInto closing a cycle, count(*) ....... triangle count            ("triangle")
+//   the same grouped by the id of a, b or c ................. per-node triangle counts   ("triangle_grouped")
+//   2 x Expand + ExpandInto, directions mixed, count(*) ..... transitive triangle count ("triangle_transitive")
+//   the same grouped by the id of a, b or c ................. its counts per role       ("triangle_transitive_grouped")
 //   var-length 0 <= l <= u <= 4, grouped count(*) by start .. var-length count          ("var_length")
 // over registered entity tables (capsmi_node_table / capsmi_rel_table), and otherwise runs the
 // operators one by one (api.hip eager_*).  Node predicates become node-scan bitmaps; ids must be
@@ -942,6 +945,34 @@ bool same_orientation(const Path& P) {
     return true;
 }
 
+// hop h read along its relationships: from the position at their source to the position at their target
+Hop directed(const Hop& h) {
+    Hop d;
+    d.rel = h.rel;
+    d.from = h.from_role == ROLE_SRC ? h.from : h.to;
+    d.to = h.from_role == ROLE_SRC ? h.to : h.from;
+    return d;
+}
+
+// The closed path over three positions: Expands 0 - 1 and 1 - 2 and the ExpandInto between 2 and 0 (whose Hop
+// runs from the position joined on the source to the one joined on the target), each in either direction.  The
+// eight spellings are two patterns up to relabelling, told apart by the positions' out-degrees among the three
+// relationships: (1, 1, 1) is the directed cycle, and otherwise one position has 2 (the source of the transitive
+// triangle (a)->(b)->(c)<-(a)), one 1 (the middle) and one 0 (the sink); role[p] = CAPSMI_TRI_ROLE_* of position p.
+enum { TRI_NONE = 0, TRI_CYCLE = 1, TRI_TRANSITIVE = 2 };
+int closed_triangle(const Path& P, int role[3]) {
+    if (P.hops.size() != 3 || P.pos_node.size() != 3) return TRI_NONE;
+    const Hop &h0 = P.hops[0], &h1 = P.hops[1], &h2 = P.hops[2];
+    if (!(h0.from == 0 && h0.to == 1 && h1.from == 1 && h1.to == 2)) return TRI_NONE;
+    if (!((h2.from == 2 && h2.to == 0) || (h2.from == 0 && h2.to == 2))) return TRI_NONE;
+    int out[3] = {0, 0, 0};
+    for (const Hop& h : P.hops) out[directed(h).from] += 1;
+    if (out[0] == 1 && out[1] == 1 && out[2] == 1) return TRI_CYCLE;
+    for (int p = 0; p < 3; ++p)
+        role[p] = out[p] == 2 ? CAPSMI_TRI_ROLE_SOURCE : out[p] == 1 ? CAPSMI_TRI_ROLE_MIDDLE : CAPSMI_TRI_ROLE_SINK;
+    return TRI_TRANSITIVE;
+}
+
 bool all_pairs_unique(const Classified& c, int nh) {
     for (int i = 0; i < nh; ++i)
         for (int j = i + 1; j < nh; ++j)
@@ -1269,14 +1300,14 @@ bool fused_counts(capsmi_session* s, const Path& P, const std::vector<int>& kind
         route(s, "two_hop");
         return true;
     }
-    if (nh == 3 && P.pos_node.size() == 3 && same_orientation(P)) {
-        // P0 -h0-> P1 -h1-> P2 -h2-> P0 (the closing hop is the ExpandInto)
-        const Hop &h0 = P.hops[0], &h1 = P.hops[1], &h2 = P.hops[2];
-        if (!(h0.from == 0 && h0.to == 1 && h1.from == 1 && h1.to == 2 && h2.from == 2 && h2.to == 0)) return false;
-        RelViews v1, v2;
-        rel_views(P, h1, v1);
-        rel_views(P, h2, v2);
-        if (v1.sig != v0.sig || v2.sig != v0.sig || !all_pairs_unique(c, 3)) return false;
+    int tri_role[3];
+    if (const int shape = closed_triangle(P, tri_role)) {
+        // P0 - P1 - P2 - P0 (the closing hop is the ExpandInto), every hop read along its relationships
+        RelViews d0, v1, v2;
+        rel_views(P, directed(P.hops[0]), d0);
+        rel_views(P, directed(P.hops[1]), v1);
+        rel_views(P, directed(P.hops[2]), v2);
+        if (v1.sig != d0.sig || v2.sig != d0.sig || !all_pairs_unique(c, 3)) return false;
         for (int k : kinds) if (k != A_COUNT) return false;
         std::string k0, k1, k2;
         capsmi_bitmap* a = node_bitmap(s, P, c, P.pos_node[0], lo, hi, bs, &k0);
@@ -1286,8 +1317,15 @@ bool fused_counts(capsmi_session* s, const Path& P, const std::vector<int>& kind
         // the distributed build codes oriented targets in 24 bits: larger domains take the generic plan
         if (g_dist.on && (bits_for_ids(hi - lo) + 7) / 8 * 8 > 24) return false;
         int64_t x = 0;
-        if (g_dist.on) x = dist_triangle_count(s, v0.t, a);
-        else check(capsmi_triangle_count(s, (int32_t)nt, v0.t.data(), "s", "t", a, &x));
+        if (shape == TRI_TRANSITIVE) {
+            if (g_dist.on) return false;  // single device
+            check(capsmi_triangle_count_transitive(s, (int32_t)nt, d0.t.data(), "s", "t", a, &x));
+            vals.assign(kinds.size(), x);
+            route(s, "triangle_transitive");
+            return true;
+        }
+        if (g_dist.on) x = dist_triangle_count(s, d0.t, a);
+        else check(capsmi_triangle_count(s, (int32_t)nt, d0.t.data(), "s", "t", a, &x));
         vals.assign(kinds.size(), x);
         route(s, "triangle");
         return true;
@@ -1515,6 +1553,9 @@ bool fused_grouped_two_hop(capsmi_session* s, const capsmi_table* in, const Plan
 // triangle in fused_counts (three hops closing on position 0, one relationship set, pairwise-unique
 // relationships, one node filter for all three positions) make the pattern symmetric under rotation, so the
 // counts grouped by position 1 or 2 are the counts grouped by position 0 (k_tri_grouped.hip).  Single device.
+// The same closed path with mixed directions is the transitive triangle (closed_triangle): the key's position
+// has a role -- source, middle or sink -- and the rows are that role's counts (k_tri_trans.hip,
+// "triangle_transitive_grouped").
 bool fused_grouped_triangle(capsmi_session* s, const capsmi_table* in, const PlanNode& g, const std::vector<Path>& B,
                             capsmi_table** out) {
     if (B.size() != 1 || g.a.size() != 1 || g.aggs.empty()) return false;
@@ -1522,9 +1563,10 @@ bool fused_grouped_triangle(capsmi_session* s, const capsmi_table* in, const Pla
     Classified c;
     if (any_no_loops(P) || !classify(P, c)) return false;
     for (int x : P.pos_node) if (x < 0) return false;
-    if (P.hops.size() != 3 || P.pos_node.size() != 3 || !same_orientation(P)) return false;
-    const Hop &h0 = P.hops[0], &h1 = P.hops[1], &h2 = P.hops[2];
-    if (!(h0.from == 0 && h0.to == 1 && h1.from == 1 && h1.to == 2 && h2.from == 2 && h2.to == 0)) return false;
+    int role[3];
+    const int shape = closed_triangle(P, role);
+    if (shape == TRI_NONE) return false;
+    const Hop h0 = directed(P.hops[0]), h1 = directed(P.hops[1]), h2 = directed(P.hops[2]);
     const int gc = find_col(in, g.a[0]);
     if (gc < 0 || !id_like(P, P.cols[gc])) return false;
     const int gp = position_of(P, P.cols[gc]);
@@ -1559,7 +1601,7 @@ bool fused_grouped_triangle(capsmi_session* s, const capsmi_table* in, const Pla
     {
         TriGraph tg;
         tri_build(s, srcs.data(), dsts.data(), ms.data(), (int)srcs.size(), a, tg);
-        rows = tri_count_by_node(s, tg, ids, cnt);
+        rows = shape == TRI_CYCLE ? tri_count_by_node(s, tg, ids, cnt) : tri_trans_count_by_node(s, tg, role[gp], ids, cnt);
     }
     ids_to_long(s, lo, ::capsmi::P<int64_t>(ids), rows);
     auto* r = result_table(s, rows);
@@ -1575,7 +1617,7 @@ bool fused_grouped_triangle(capsmi_session* s, const capsmi_table* in, const Pla
         r->cols.push_back(std::move(v));
     }
     *out = guard.release();
-    route(s, "triangle_grouped");
+    route(s, shape == TRI_CYCLE ? "triangle_grouped" : "triangle_transitive_grouped");
     return true;
 }
 

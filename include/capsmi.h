@@ -696,6 +696,39 @@ capsmi_status capsmi_trigraph_count_by_node(capsmi_session* s, const capsmi_trig
 capsmi_status capsmi_triangle_count_by_node(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
                                             const char* src_col, const char* dst_col, const capsmi_bitmap* n_ok,
                                             const char* id_name, const char* count_name, capsmi_table** out);
+/* The transitive ("feed-forward") triangle over the same trigraph:
+ *   MATCH (a)-[r1]->(b)-[r2]->(c)<-[r3]-(a) WHERE n_ok(a) AND n_ok(b) AND n_ok(c) RETURN count(*)
+ *   ... RETURN id(a), count(*)     (or id(b), or id(c))
+ * Bindings are rows: r1, r2, r3 are pairwise distinct, node variables may coincide, and the one node filter
+ * applies to all three positions.  With m(x,y) the multiplicity of x->y for x != y, s(x) the self-loops at x and
+ * M(y,z) = m(y,z) + m(z,y), the bindings split by how many of a, b, c coincide:
+ *   three distinct nodes   m(a,b) m(b,c) m(a,c); of a simple triangle {x,y,z}, node x receives
+ *                            as source a   m(x,y) m(x,z) M(y,z)
+ *                            as sink c     m(y,x) m(z,x) M(y,z)
+ *                            as middle b   m(y,x) m(x,z) m(y,z) + m(z,x) m(x,y) m(z,y)
+ *   a = b = x, c = y != x  s(x) m(x,y) (m(x,y)-1)         (r1 is a loop)
+ *   b = c = y, a = x != y  m(x,y) (m(x,y)-1) s(y)         (r2 is a loop)
+ *   a = c = x, b = y != x  m(x,y) m(y,x) s(x)             (r3 is a loop)
+ *   a = b = c = x          s(x) (s(x)-1) (s(x)-2)
+ * The count is the sum of all of these.  The pattern is not symmetric under rotation: the positions are three
+ * roles, and a count grouped by a role credits each term to the node in that role (the b = c = y term goes to x
+ * for the source and to y for the middle and the sink).  The three roles' counts have the same sum.
+ * The _by_node forms follow the result contract of capsmi_trigraph_count_by_node: two non-nullable Long columns,
+ * the graph's own ids and the counts, one row per node with a non-zero count, in no particular order.  Single
+ * device: a trigraph of a distributed build gives CAPSMI_ERR_UNSUPPORTED; a role outside 0..2 gives
+ * CAPSMI_ERR_ILLEGAL_ARGUMENT. */
+enum { CAPSMI_TRI_ROLE_SOURCE = 0, CAPSMI_TRI_ROLE_MIDDLE = 1, CAPSMI_TRI_ROLE_SINK = 2 }; /* a, b, c */
+capsmi_status capsmi_trigraph_count_transitive(capsmi_session* s, const capsmi_trigraph* g, int64_t* out_rows);
+capsmi_status capsmi_trigraph_count_transitive_by_node(capsmi_session* s, const capsmi_trigraph* g, int32_t role,
+                                                       const char* id_name, const char* count_name,
+                                                       capsmi_table** out);
+capsmi_status capsmi_triangle_count_transitive(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                               const char* src_col, const char* dst_col, const capsmi_bitmap* n_ok,
+                                               int64_t* out_rows);
+capsmi_status capsmi_triangle_count_transitive_by_node(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                                       const char* src_col, const char* dst_col,
+                                                       const capsmi_bitmap* n_ok, int32_t role, const char* id_name,
+                                                       const char* count_name, capsmi_table** out);
 /* count(*) of the 2-hop chain (capsmi_two_hop_count) on one rank of an owner(target) partition:
  * this rank's tables hold every relationship into its owned ids [own_lo, own_hi) (relative to the
  * bitmaps' lo).  begin partitions them and writes the owned ids' in-degrees inA (relationships from

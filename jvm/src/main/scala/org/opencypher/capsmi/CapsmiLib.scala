@@ -89,6 +89,11 @@ object Capsmi {
   final val MASK_TRUE = 0     // labels(): the Boolean flag is non-null and TRUE
   final val MASK_NOT_NULL = 1 // keys(): the value is non-null
 
+  // capsmi_*_count_transitive_by_node: the position of (a)-[r1]->(b)-[r2]->(c)<-[r3]-(a) that is counted
+  final val TRI_ROLE_SOURCE = 0 // a
+  final val TRI_ROLE_MIDDLE = 1 // b
+  final val TRI_ROLE_SINK = 2   // c
+
   // join types (JoinType of RelationalPlanner; SparkTable.scala:205-229)
   final val JOIN_INNER = 0
   final val JOIN_LEFT_OUTER = 1
@@ -292,6 +297,14 @@ trait CapsmiLib extends Library {
   def capsmi_trigraph_count_by_node(s: Pointer, g: Pointer, idName: String, countName: String, out: PointerByReference): Int
   def capsmi_triangle_count_by_node(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String, dstCol: String,
                                     nOk: Pointer, idName: String, countName: String, out: PointerByReference): Int
+  def capsmi_trigraph_count_transitive(s: Pointer, g: Pointer, outRows: LongByReference): Int
+  def capsmi_trigraph_count_transitive_by_node(s: Pointer, g: Pointer, role: Int, idName: String, countName: String,
+                                               out: PointerByReference): Int
+  def capsmi_triangle_count_transitive(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String, dstCol: String,
+                                       nOk: Pointer, outRows: LongByReference): Int
+  def capsmi_triangle_count_transitive_by_node(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String,
+                                               dstCol: String, nOk: Pointer, role: Int, idName: String,
+                                               countName: String, out: PointerByReference): Int
   def capsmi_undirected_count(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String, dstCol: String, hops: Int,
                               a: Pointer, b: Pointer, c: Pointer, kind: Int, out: LongByReference): Int
   def capsmi_var_length_count(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String, dstCol: String, a: Pointer,
