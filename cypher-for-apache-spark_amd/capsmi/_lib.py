@@ -184,6 +184,11 @@ _SIGS = {
     "capsmi_triangle_count_transitive": (c_int32, [P, c_int32, PP, c_char_p, c_char_p, P, POINTER(c_int64)]),
     "capsmi_triangle_count_transitive_by_node": (c_int32, [P, c_int32, PP, c_char_p, c_char_p, P, c_int32, c_char_p,
                                                            c_char_p, PP]),
+    "capsmi_trigraph_count_undirected": (c_int32, [P, P, POINTER(c_int64)]),
+    "capsmi_trigraph_count_undirected_by_node": (c_int32, [P, P, c_int32, c_char_p, c_char_p, PP]),
+    "capsmi_triangle_count_undirected": (c_int32, [P, c_int32, PP, c_char_p, c_char_p, P, POINTER(c_int64)]),
+    "capsmi_triangle_count_undirected_by_node": (c_int32, [P, c_int32, PP, c_char_p, c_char_p, P, c_int32, c_char_p,
+                                                           c_char_p, PP]),
     "capsmi_undirected_count": (c_int32, [P, c_int32, PP, c_char_p, c_char_p, c_int32, P, P, P, c_int32,
                                           POINTER(c_int64)]),
     "capsmi_var_length_count": (c_int32, [P, c_int32, PP, c_char_p, c_char_p, P, P, c_int32, c_int32, c_char_p,

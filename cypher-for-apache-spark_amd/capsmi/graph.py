@@ -260,6 +260,21 @@ class TriGraph:
                   count_name.encode(), ctypes.byref(out))
         return GpuTable(self.session, out)
 
+    def count_undirected(self) -> int:
+        """``MATCH (a)-[r1]-(b)-[r2]-(c)-[r3]-(a) RETURN count(*)`` over the same graph (the plan's rows: the
+        closing hop binds a self-loop twice)."""
+        v = ctypes.c_int64()
+        _lib.call("capsmi_trigraph_count_undirected", self.session.handle, self._h, ctypes.byref(v))
+        return v.value
+
+    def count_undirected_by_node(self, position: int, id_name: str = "id", count_name: str = "count") -> GpuTable:
+        """The undirected triangle grouped by the node at a position of class `position` (TRI_UND_END a or c,
+        TRI_UND_MIDDLE b): one row (id, count) per node with a non-zero count, unordered."""
+        out = ctypes.c_void_p()
+        _lib.call("capsmi_trigraph_count_undirected_by_node", self.session.handle, self._h, position, id_name.encode(),
+                  count_name.encode(), ctypes.byref(out))
+        return GpuTable(self.session, out)
+
     def stats(self):
         """(id-domain size, oriented simple edges)"""
         n, ne = ctypes.c_int64(), ctypes.c_int64()
@@ -320,6 +335,30 @@ def triangle_count_transitive_by_node(session: Session, rels: Sequence[GpuTable]
     out = ctypes.c_void_p()
     _lib.call("capsmi_triangle_count_transitive_by_node", session.handle, len(rels), _handles(rels), src_col.encode(),
               dst_col.encode(), n_ok.handle, role, id_name.encode(), count_name.encode(), ctypes.byref(out))
+    return GpuTable(session, out)
+
+
+# the position classes of (a)-[r1]-(b)-[r2]-(c)-[r3]-(a) (include/capsmi.h CAPSMI_TRI_UND_*): a or c; b
+TRI_UND_END, TRI_UND_MIDDLE = 0, 1
+
+
+def triangle_count_undirected(session: Session, rels: Sequence[GpuTable], n_ok: NodeBitmap, src_col: str = "source",
+                              dst_col: str = "target") -> int:
+    """``MATCH (a)-[r1]-(b)-[r2]-(c)-[r3]-(a) RETURN count(*)`` (pairwise-distinct relationships)."""
+    v = ctypes.c_int64()
+    _lib.call("capsmi_triangle_count_undirected", session.handle, len(rels), _handles(rels), src_col.encode(),
+              dst_col.encode(), n_ok.handle, ctypes.byref(v))
+    return v.value
+
+
+def triangle_count_undirected_by_node(session: Session, rels: Sequence[GpuTable], n_ok: NodeBitmap, position: int,
+                                      id_name: str = "id", count_name: str = "count", src_col: str = "source",
+                                      dst_col: str = "target") -> GpuTable:
+    """``MATCH (a)-[r1]-(b)-[r2]-(c)-[r3]-(a) RETURN id(x), count(*)`` with x at a position of class `position`
+    (TRI_UND_END a or c, TRI_UND_MIDDLE b): one row per node with a non-zero count, unordered."""
+    out = ctypes.c_void_p()
+    _lib.call("capsmi_triangle_count_undirected_by_node", session.handle, len(rels), _handles(rels), src_col.encode(),
+              dst_col.encode(), n_ok.handle, position, id_name.encode(), count_name.encode(), ctypes.byref(out))
     return GpuTable(session, out)
 
 

@@ -515,6 +515,9 @@ bool apply(Config& c, const std::string& name, const char* v) {
     } else if (name == "CAPSMI_TRI_SPLIT") {
         if (!parse_int(v, 0, 1, x)) return false;
         c.tri_split = x != 0;
+    } else if (name == "CAPSMI_TRI_UND_COUNT") {
+        if (!parse_choice(v, {"hash", "walk"}, k)) return false;
+        c.tri_und_hash = k == 0;
     } else if (name == "CAPSMI_TRI_VMODE_T") {
         if (!parse_int(v, 0, 1 << 30, x)) return false;
         c.tri_vmode_t = (int)x;
@@ -555,7 +558,7 @@ const std::pair<const char*, const char*> kKnobs[] = {
     {"CAPSMI_UND", "part"},          {"CAPSMI_VL_BITS", "8"},        {"CAPSMI_VL_SUBLOG", "-1"},
     {"CAPSMI_VL_F2", "0"},           {"CAPSMI_COLL_CHUNK", "67108864"}, {"CAPSMI_INGEST_THREADS", "0"},
     {"CAPSMI_HOP2", "auto"},         {"CAPSMI_POOL", "split"},       {"CAPSMI_STR_MATCH", "auto"},
-    {"CAPSMI_HOP2_EXCHANGE", "on"},  {"CAPSMI_NARROW", "auto"}};
+    {"CAPSMI_HOP2_EXCHANGE", "on"},  {"CAPSMI_NARROW", "auto"},      {"CAPSMI_TRI_UND_COUNT", "hash"}};
 }  // namespace
 
 Config config_from_env() {
@@ -2355,6 +2358,69 @@ capsmi_status capsmi_triangle_count_transitive_by_node(capsmi_session* s, int32_
     capsmi_status st = capsmi_trigraph_build(s, nrels, rels, src_col, dst_col, n_ok, &g);
     if (st != CAPSMI_OK) return st;
     st = capsmi_trigraph_count_transitive_by_node(s, g, role, id_name, count_name, out);
+    capsmi_trigraph_release(g);
+    return st;
+}
+
+capsmi_status capsmi_trigraph_count_undirected(capsmi_session* s, const capsmi_trigraph* g, int64_t* out_rows) {
+    API_BEGIN
+    need(s, "session");
+    need(g, "trigraph");
+    need(out_rows, "out");
+    use_device(s);
+    *out_rows = (int64_t)tri_und_count(s, g->g);
+    API_END
+}
+
+capsmi_status capsmi_trigraph_count_undirected_by_node(capsmi_session* s, const capsmi_trigraph* g, int32_t position,
+                                                       const char* id_name, const char* count_name,
+                                                       capsmi_table** out) {
+    API_BEGIN
+    need(s, "session");
+    need(g, "trigraph");
+    need(out, "out");
+    need(id_name, "id_name");
+    need(count_name, "count_name");
+    REQUIRE(position == CAPSMI_TRI_UND_END || position == CAPSMI_TRI_UND_MIDDLE, CAPSMI_ERR_ILLEGAL_ARGUMENT,
+            "position must be CAPSMI_TRI_UND_END or CAPSMI_TRI_UND_MIDDLE");
+    REQUIRE(std::string(id_name) != count_name, CAPSMI_ERR_ILLEGAL_ARGUMENT, "output names must differ");
+    use_device(s);
+    Buf ids, cnt;
+    const int64_t rows = tri_und_count_by_node(s, g->g, position, ids, cnt);
+    add_i64(P<int64_t>(ids), g->g.lo, rows, s->stream);  // relative ids -> the graph's
+    auto* o = new_table(s, rows);
+    Column a, c;
+    a.name = id_name;
+    a.type = CAPSMI_I64;
+    a.data = ids;
+    c.name = count_name;
+    c.type = CAPSMI_I64;
+    c.data = cnt;
+    o->cols.push_back(std::move(a));
+    o->cols.push_back(std::move(c));
+    *out = o;
+    API_END
+}
+
+capsmi_status capsmi_triangle_count_undirected(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                               const char* src_col, const char* dst_col, const capsmi_bitmap* n_ok,
+                                               int64_t* out_rows) {
+    capsmi_trigraph* g = nullptr;
+    capsmi_status st = capsmi_trigraph_build(s, nrels, rels, src_col, dst_col, n_ok, &g);
+    if (st != CAPSMI_OK) return st;
+    st = capsmi_trigraph_count_undirected(s, g, out_rows);
+    capsmi_trigraph_release(g);
+    return st;
+}
+
+capsmi_status capsmi_triangle_count_undirected_by_node(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                                       const char* src_col, const char* dst_col,
+                                                       const capsmi_bitmap* n_ok, int32_t position, const char* id_name,
+                                                       const char* count_name, capsmi_table** out) {
+    capsmi_trigraph* g = nullptr;
+    capsmi_status st = capsmi_trigraph_build(s, nrels, rels, src_col, dst_col, n_ok, &g);
+    if (st != CAPSMI_OK) return st;
+    st = capsmi_trigraph_count_undirected_by_node(s, g, position, id_name, count_name, out);
     capsmi_trigraph_release(g);
     return st;
 }

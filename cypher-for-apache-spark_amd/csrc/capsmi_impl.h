@@ -161,6 +161,7 @@ struct Config {
     bool tri_sorted_build = false;  // CAPSMI_TRI_BUILD = sorted: the sort-oriented trigraph build (above 2^24 ids)
     int tri_deg_sample = 0;       // CAPSMI_TRI_DEG_SAMPLE: 1 in k relationships for the degree order (0: auto)
     bool tri_split = true;        // CAPSMI_TRI_SPLIT = 0: the combined (not direction-split) triangle walks
+    bool tri_und_hash = true;     // CAPSMI_TRI_UND_COUNT = walk: the undirected triangle's count by the search walk
     int tri_vmode_t = 256;        // CAPSMI_TRI_VMODE_T: od(v) threshold of the v-mode walks (0: all u-mode)
     bool und_stream = false;      // CAPSMI_UND = stream: undirected count(DISTINCT) by the streaming form
                                   //   (the form above 2^26 ids) instead of the cell layout
@@ -639,6 +640,13 @@ int64_t tri_count_by_node(capsmi_session* s, const TriGraph& g, Buf& ids, Buf& c
 // rows (relative id, count) of the nodes with a non-zero count in `role` (CAPSMI_TRI_ROLE_*), unordered
 uint64_t tri_trans_count(capsmi_session* s, const TriGraph& g);
 int64_t tri_trans_count_by_node(capsmi_session* s, const TriGraph& g, int role, Buf& ids, Buf& counts);
+// the undirected triangle (a)-(b)-(c)-(a) over a single-device trigraph (k_tri_und.hip): count(*) in the form
+// cfg.tri_und_hash selects, and the rows (relative id, count) of the nodes with a non-zero count at a position of
+// class `position` (CAPSMI_TRI_UND_*), unordered.  tri_und_hash_walk (k_tri.hip): the count's hash walks, which
+// add sum U U U over the simple triangles to the device word *out
+uint64_t tri_und_count(capsmi_session* s, const TriGraph& g);
+int64_t tri_und_count_by_node(capsmi_session* s, const TriGraph& g, int position, Buf& ids, Buf& counts);
+void tri_und_hash_walk(capsmi_session* s, const TriGraph& g, unsigned long long* out);
 
 // undirected Expand patterns (k_undirected.hip): hops 1 or 2; kind 0 count(*), 1 count(DISTINCT end),
 // 2 count(DISTINCT start); c unused for one hop.  marks (kinds 1, 2; b's nwords words): the distinct ids'

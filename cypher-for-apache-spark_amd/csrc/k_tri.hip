@@ -1097,7 +1097,7 @@ __device__ __forceinline__ void list_pass(const uint32_t* __restrict__ tg, TgCod
 }
 
 // the wave walks each out(v) with all lanes (as k_tri_big_items)
-template <int U>
+template <int U, class WT = CycleWeight>
 __global__ void __launch_bounds__(kTriBlock) k_tri_small(const uint32_t* __restrict__ tg, TgCode tc,
                                                          const int64_t* __restrict__ ov,
                                                          const int64_t* __restrict__ off, int vmt,
@@ -1163,7 +1163,7 @@ __global__ void __launch_bounds__(kTriBlock) k_tri_small(const uint32_t* __restr
                 for (int t = 0; t < 4; ++t) {
                     if (!((keep >> t) & 1u)) continue;
                     const int sl = hfind(W.hk, 9, tid(w[t], tc), ~0u);
-                    if (sl >= 0) acc += tri_weight(W.vp[k], tpay(w[t], tc, ov, vo + e + sg * t), W.vp[W.hi[sl]]);
+                    if (sl >= 0) acc += WT::of(W.vp[k], tpay(w[t], tc, ov, vo + e + sg * t), W.vp[W.hi[sl]]);
                 }
             }
         };
@@ -1182,7 +1182,7 @@ __global__ void __launch_bounds__(kTriBlock) k_tri_small(const uint32_t* __restr
                 for (int r = 0; r < U; ++r) {
                     if (!((keep >> r) & 1u)) continue;
                     const int sl = hfind(W.hk, 9, tid(w[r], tc), ~0u);
-                    if (sl >= 0) acc += tri_weight(puv, tpay(w[r], tc, ov, vo + j0 + r * 64), W.vp[W.hi[sl]]);
+                    if (sl >= 0) acc += WT::of(puv, tpay(w[r], tc, ov, vo + j0 + r * 64), W.vp[W.hi[sl]]);
                 }
             }
         }
@@ -1255,7 +1255,7 @@ __global__ void k_tri_item_map(const int64_t* __restrict__ ipre, int64_t nu, uin
 // Register budget: two 1024-lane items per CU need 8 waves per SIMD, i.e. an SGPR granule of at most
 // 96 (800 per SIMD): .amdhsa_next_free_sgpr <= 74 here.  At 77 the v-mode launch admitted one item
 // per CU and took 113 instead of 69 ms (the u-mode 512-lane one 25 instead of 21.6 ms).
-template <int U, bool VM, int B>
+template <int U, bool VM, int B, class WT = CycleWeight>
 __global__ void __launch_bounds__(B, 8) k_tri_big_items(const uint32_t* __restrict__ tg, TgCode tc,
                                                              const int64_t* __restrict__ ov,
                                                              const int64_t* __restrict__ off,
@@ -1361,7 +1361,7 @@ __global__ void __launch_bounds__(B, 8) k_tri_big_items(const uint32_t* __restri
                             const uint64_t pxw = tpay(w[t], tc, ov, vo + e + sg * t);
                             const uint64_t pcw = tpay(L.hk[sl], tc, ov, b + h0 + L.hi[sl]);
                             const uint64_t puv = L.vp[k];
-                            acc += VM ? tri_weight(puv, pcw, pxw) : tri_weight(puv, pxw, pcw);
+                            acc += VM ? WT::of(puv, pcw, pxw) : WT::of(puv, pxw, pcw);
                         }
                     }
                 }
@@ -1383,7 +1383,7 @@ __global__ void __launch_bounds__(B, 8) k_tri_big_items(const uint32_t* __restri
                         if (sl >= 0) {
                             const uint64_t pxw = tpay(w[r], tc, ov, vo + j0 + r * 64);
                             const uint64_t pcw = tpay(L.hk[sl], tc, ov, b + h0 + L.hi[sl]);
-                            acc += VM ? tri_weight(puv, pcw, pxw) : tri_weight(puv, pxw, pcw);
+                            acc += VM ? WT::of(puv, pcw, pxw) : WT::of(puv, pxw, pcw);
                         }
                     }
                 }
@@ -2460,6 +2460,43 @@ uint64_t tri_count(capsmi_session* s, const TriGraph& g, int part, int nparts) {
     HIP_CHECK(hipMemcpyAsync(h, P<void>(out), 24, hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
     return 3 * h[0] + h[1] + h[2];
+}
+
+// The undirected triangle's hash walks (k_tri_und.hip): adds sum U(u,v) U(v,w) U(u,w) over the simple triangles
+// to *out.  The u-mode walks over the combined out-lists with vmt = 0 -- every edge from its u, no v-mode: a
+// split build keeps no combined in-lists, and the base lists are whole on either build.
+void tri_und_hash_walk(capsmi_session* s, const TriGraph& g, unsigned long long* out) {
+    using namespace tri;
+    hipStream_t st = s->stream;
+    KernelTimer kt(s, "triangles_undirected");
+    const TgCode tc{(uint32_t)g.ib, (uint32_t)g.cb};
+    if (g.nbig > 0) {
+        constexpr int B = 512;
+        const int64_t nc = g.nbig;
+        const int64_t* cs = P<int64_t>(g.big_u);
+        Buf ib = dev_alloc(sizeof(int64_t) * (2 * nc + 2), s);
+        int64_t* items = P<int64_t>(ib);
+        int64_t* ipre = items + nc;
+        hipLaunchKernelGGL(k_tri_items, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, st, P<int64_t>(g.off), nullptr, cs,
+                           nc, 2 * B, kVChunk * kVGroup, items);
+        exclusive_scan_i64(items, ipre, nc, s);
+        const int64_t nitems = read_scalar(s, ipre + nc);
+        Buf iq = dev_alloc(sizeof(uint64_t) * (nitems > 0 ? nitems : 1), s);
+        hipLaunchKernelGGL(k_tri_item_map, dim3(grid(s, nc)), dim3(256), 0, st, ipre, nc, P<uint64_t>(iq));
+        Buf ctr = dev_alloc(sizeof(unsigned long long), s);
+        HIP_CHECK(hipMemsetAsync(P<void>(ctr), 0, sizeof(unsigned long long), st));
+        auto kf = k_tri_big_items<4, false, B, UndirectedWeight>;
+        set_lds_attr(reinterpret_cast<const void*>(kf), sizeof(ItemLds<B>));
+        hipLaunchKernelGGL(kf, dim3((unsigned)(s->num_cus * 8)), dim3(B), sizeof(ItemLds<B>), st, P<uint32_t>(g.tg), tc,
+                           P<int64_t>(g.ov), P<int64_t>(g.off), nullptr, nullptr, nullptr, 0, cs, nc, ipre, P<uint64_t>(iq),
+                           P<unsigned long long>(ctr), out);
+    }
+    if (g.nsmall > 0) {
+        const int64_t gs = std::min<int64_t>((g.nsmall + 3) / 4, (int64_t)s->num_cus * 16);
+        hipLaunchKernelGGL((k_tri_small<4, UndirectedWeight>), dim3((unsigned)gs), dim3(kTriBlock), 0, st, P<uint32_t>(g.tg), tc,
+                           P<int64_t>(g.ov), P<int64_t>(g.off), 0, P<int64_t>(g.small_u), g.nsmall, out);
+    }
+    HIP_CHECK(hipGetLastError());
 }
 
 }  // namespace capsmi

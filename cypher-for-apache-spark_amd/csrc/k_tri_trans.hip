@@ -31,8 +31,7 @@
 #include <algorithm>
 
 #include "capsmi_impl.h"
-#include "tile_owner.h"
-#include "tri_code.h"
+#include "tri_walk.h"
 
 namespace capsmi {
 namespace tri {
@@ -40,42 +39,9 @@ namespace {
 
 using namespace tiles;
 
-// the privatised window of k_tri_grouped.hip (measured there), with its build-time override
-#ifndef CAPSMI_TRI_BY_NODE_WIN
-#define CAPSMI_TRI_BY_NODE_WIN 64
-#endif
-constexpr int kByNodeWin = CAPSMI_TRI_BY_NODE_WIN;
-static_assert(kByNodeWin >= 1 && kByNodeWin <= 3072, "the window and the tile's owner arrays share 64 KiB of LDS");
-
 constexpr int kTotal = 3;  // ROLE of the ungrouped form (after CAPSMI_TRI_ROLE_SOURCE / _MIDDLE / _SINK)
 
-typedef unsigned long long u64;
-
-__device__ __forceinline__ void node_add(u64* win, u64* __restrict__ cnt, uint32_t id, u64 x) {
-    if (id < (uint32_t)kByNodeWin) atomicAdd(&win[id], x);
-    else atomicAdd(&cnt[id], x);
-}
-
-__device__ __forceinline__ void win_flush(const u64* win, u64* __restrict__ cnt, int64_t n) {
-    for (int i = threadIdx.x; i < kByNodeWin && i < n; i += blockDim.x)
-        if (win[i]) atomicAdd(&cnt[i], win[i]);
-}
-
-// the workgroup's sum of x, added to *out by one atomic (every thread calls it; tot: one LDS word, zeroed here)
-__device__ __forceinline__ void block_add(u64 x, u64* tot, u64* __restrict__ out) {
-    if (threadIdx.x == 0) *tot = 0;
-    __syncthreads();
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-    if ((threadIdx.x & 63) == 0 && x) atomicAdd(tot, x);
-    __syncthreads();
-    if (threadIdx.x == 0 && *tot) atomicAdd(out, *tot);
-}
-
-inline unsigned egrid(const capsmi_session* s, int64_t n) {
-    const int64_t g = (n + 255) / 256, cap = (int64_t)s->num_cus * 16;
-    return (unsigned)(g < 1 ? 1 : (g > cap ? cap : g));
-}
+// (the window, node_add / win_flush / block_add, the edge pass and the slot search: tri_walk.h)
 
 // What corner x of the simple triangle {x, y, z} receives in ROLE, from the six multiplicities around it.
 template <int ROLE>
@@ -111,25 +77,6 @@ __global__ void __launch_bounds__(256) k_ttr_self(const uint32_t* __restrict__ s
         else cnt[r] = t;
     }
     if (ROLE == kTotal) block_add(acc, &tot, cnt);
-}
-
-// per oriented edge e = u -> v at position p of out(u): its source (off is searched: the base arrays keep no
-// source column), and its slots, min(od(v), p)  (as k_tbn_edges)
-__global__ void k_ttr_edges(const int64_t* __restrict__ off, const uint32_t* __restrict__ tg, TgCode tc, int64_t n,
-                            int64_t ne, uint32_t* __restrict__ eu, int64_t* __restrict__ len, uint8_t* __restrict__ flag) {
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < ne; e += (int64_t)gridDim.x * blockDim.x) {
-        int64_t a = 0, b = n + 1;  // the first entry of off[0, n] above e (off[n] = ne is)
-        while (a < b) {
-            const int64_t mid = (a + b) >> 1;
-            if (off[mid] <= e) a = mid + 1; else b = mid;
-        }
-        const int64_t u = a - 1;
-        const uint32_t v = tid(tg[e], tc);
-        const int64_t l = min(off[v + 1] - off[v], e - off[u]);
-        eu[e] = (uint32_t)u;
-        len[e] = l;
-        flag[e] = l > 0 ? 1 : 0;
-    }
 }
 
 // pair terms: one oriented edge u -> v per undirected pair, f = m(u,v), b = m(v,u); a pair with one direction
@@ -197,45 +144,23 @@ __global__ void __launch_bounds__(kExB) k_ttr_walk(const int64_t* __restrict__ c
             uint32_t u = 0, v = 0;
             u64 wu = 0, wv = 0;
             if (i < nt) {
-                c = L.own[i];
-                const int64_t e = L.srow[c], j = L.sbase[c] + i;
-                u = eu[e];
-                const uint32_t wuv = tg[e];
-                v = tid(wuv, tc);
-                const int64_t uo = off[u], vo = off[v], odv = off[v + 1] - vo, p = e - uo;
-                // walk the shorter of out(v) and out(u)[0, p), search the other
-                const bool wlk = odv <= p;
-                const int64_t at = (wlk ? vo : uo) + j;
-                const uint32_t xw = tg[at], x = tid(xw, tc);
-                int64_t a = wlk ? uo : vo;
-                const int64_t end = wlk ? e : vo + odv;
-                int64_t b = end;
-                while (a < b) {
-                    const int64_t mid = (a + b) >> 1;
-                    if (tid(tg[mid], tc) < x) a = mid + 1; else b = mid;
-                }
-                if (a < end) {
-                    const uint32_t yw = tg[a];
-                    if (tid(yw, tc) == x) {  // w = x closes u -> v -> w
-                        const uint64_t puv = tpay(wuv, tc, ov, e);
-                        const uint64_t pvw = wlk ? tpay(xw, tc, ov, at) : tpay(yw, tc, ov, a);
-                        const uint64_t puw = wlk ? tpay(yw, tc, ov, a) : tpay(xw, tc, ov, at);
-                        const uint64_t uv = puv >> 32, vu = puv & 0xffffffffULL;
-                        const uint64_t vw = pvw >> 32, wv_ = pvw & 0xffffffffULL;
-                        const uint64_t uw = puw >> 32, wu_ = puw & 0xffffffffULL;
-                        if (ROLE == kTotal) {  // the six assignments: every corner as the source
-                            acc += role_weight<CAPSMI_TRI_ROLE_SOURCE>(uv, vu, uw, wu_, vw, wv_) +
-                                   role_weight<CAPSMI_TRI_ROLE_SOURCE>(vu, uv, vw, wv_, uw, wu_) +
-                                   role_weight<CAPSMI_TRI_ROLE_SOURCE>(wu_, uw, wv_, vw, uv, vu);
-                        } else {
-                            constexpr int R = ROLE == kTotal ? 0 : ROLE;
-                            wu = role_weight<R>(uv, vu, uw, wu_, vw, wv_);  // corner u, others v, w
-                            wv = role_weight<R>(vu, uv, vw, wv_, uw, wu_);  // corner v, others u, w
-                            const u64 ww = role_weight<R>(wu_, uw, wv_, vw, uv, vu);  // corner w, others u, v
-                            if (ww) node_add(win, cnt, x, ww);
-                        }
+                // the slot search of tri_walk.h; on a hit x = w closes u -> v -> w
+                tile_slot(L, i, off, tg, tc, ov, eu, c, u, v, [&](uint32_t x, uint64_t puv, uint64_t pvw, uint64_t puw) {
+                    const uint64_t uv = puv >> 32, vu = puv & 0xffffffffULL;
+                    const uint64_t vw = pvw >> 32, wv_ = pvw & 0xffffffffULL;
+                    const uint64_t uw = puw >> 32, wu_ = puw & 0xffffffffULL;
+                    if (ROLE == kTotal) {  // the six assignments: every corner as the source
+                        acc += role_weight<CAPSMI_TRI_ROLE_SOURCE>(uv, vu, uw, wu_, vw, wv_) +
+                               role_weight<CAPSMI_TRI_ROLE_SOURCE>(vu, uv, vw, wv_, uw, wu_) +
+                               role_weight<CAPSMI_TRI_ROLE_SOURCE>(wu_, uw, wv_, vw, uv, vu);
+                    } else {
+                        constexpr int R = ROLE == kTotal ? 0 : ROLE;
+                        wu = role_weight<R>(uv, vu, uw, wu_, vw, wv_);  // corner u, others v, w
+                        wv = role_weight<R>(vu, uv, vw, wv_, uw, wu_);  // corner v, others u, w
+                        const u64 ww = role_weight<R>(wu_, uw, wv_, vw, uv, vu);  // corner w, others u, v
+                        if (ww) node_add(win, cnt, x, ww);
                     }
-                }
+                });
             }
             if (ROLE == kTotal) continue;
             if (__ballot((wu | wv) != 0) == 0) continue;  // wave-uniform
@@ -264,11 +189,6 @@ __global__ void __launch_bounds__(kExB) k_ttr_walk(const int64_t* __restrict__ c
         __syncthreads();
         win_flush(win, cnt, n);
     }
-}
-
-__global__ void k_ttr_flags(const u64* __restrict__ cnt, int64_t n, uint8_t* __restrict__ f) {
-    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (int64_t)gridDim.x * blockDim.x)
-        f[r] = cnt[r] != 0 ? 1 : 0;
 }
 
 struct Timers {
@@ -333,7 +253,6 @@ int64_t tri_trans_count_by_node(capsmi_session* s, const TriGraph& g, int role, 
     using namespace tri;
     REQUIRE(!g.dist, CAPSMI_ERR_UNSUPPORTED, "transitive triangle counts per node: not over a distributed trigraph");
     REQUIRE(role >= CAPSMI_TRI_ROLE_SOURCE && role <= CAPSMI_TRI_ROLE_SINK, CAPSMI_ERR_ILLEGAL_ARGUMENT, "role");
-    hipStream_t st = s->stream;
     const int64_t n = g.n;
     Buf cnt = dev_alloc(sizeof(u64) * (n > 0 ? n : 1), s);
     u64* cp = P<u64>(cnt);
@@ -341,16 +260,7 @@ int64_t tri_trans_count_by_node(capsmi_session* s, const TriGraph& g, int role, 
     if (role == CAPSMI_TRI_ROLE_SOURCE) run<CAPSMI_TRI_ROLE_SOURCE>(s, g, cp, tm);
     else if (role == CAPSMI_TRI_ROLE_MIDDLE) run<CAPSMI_TRI_ROLE_MIDDLE>(s, g, cp, tm);
     else run<CAPSMI_TRI_ROLE_SINK>(s, g, cp, tm);
-    KernelTimer kt(s, "tri_trans_by_node_rows");
-    Buf f = dev_alloc(n > 0 ? n : 1, s), idx;
-    hipLaunchKernelGGL(k_ttr_flags, dim3(egrid(s, n)), dim3(256), 0, st, cp, n, P<uint8_t>(f));
-    HIP_CHECK(hipGetLastError());
-    const int64_t rows = flags_to_indices(s, P<uint8_t>(f), n, idx);
-    ids = dev_alloc(sizeof(int64_t) * (rows > 0 ? rows : 1), s);
-    counts = dev_alloc(sizeof(int64_t) * (rows > 0 ? rows : 1), s);
-    gather_col(P<int64_t>(g.orig), nullptr, P<int64_t>(idx), rows, P<int64_t>(ids), nullptr, st);
-    gather_col(reinterpret_cast<const int64_t*>(cp), nullptr, P<int64_t>(idx), rows, P<int64_t>(counts), nullptr, st);
-    return rows;
+    return node_rows(s, g, cp, "tri_trans_by_node_rows", ids, counts);
 }
 
 }  // namespace capsmi

@@ -16,6 +16,8 @@
 //   the same grouped by the id of a, b or c ................. per-node triangle counts   ("triangle_grouped")
 //   2 x Expand + ExpandInto, directions mixed, count(*) ..... transitive triangle count ("triangle_transitive")
 //   the same grouped by the id of a, b or c ................. its counts per role       ("triangle_transitive_grouped")
+//   2 x undirected Expand + undirected ExpandInto, count(*) . undirected triangle count ("triangle_undirected")
+//   the same grouped by the id of a, b or c ................. its counts per position   ("triangle_undirected_grouped")
 //   var-length 0 <= l <= u <= 4, grouped count(*) by start .. var-length count          ("var_length")
 // over registered entity tables (capsmi_node_table / capsmi_rel_table), and otherwise runs the
 // operators one by one (api.hip eager_*).  Node predicates become node-scan bitmaps; ids must be
@@ -1621,6 +1623,123 @@ bool fused_grouped_triangle(capsmi_session* s, const capsmi_table* in, const Pla
     return true;
 }
 
+// The undirected triangle (a)-[r1]-(b)-[r2]-(c)-[r3]-(a) (RelationalPlanner.scala:126-136 and :150-153): eight
+// branches, one per orientation of the three hops.  Every branch is the closed path of closed_triangle; hops 0 and
+// 1 (the Expands) are incoming exactly when their relationship scan is the start <> end instance, the closing
+// ExpandInto's scan never is (it binds a self-loop in both of its joins); one relationship set read as (start,
+// end) by every hop of every branch, pairwise-unique relationships, one node filter for all positions and
+// branches, count(*) aggregates only.  Without keys: the count ("triangle_undirected"); with one key, the id of
+// the same position p in every branch: the rows of p's class -- the ends of the ExpandInto (p = 0, 2) or the
+// middle (p = 1) -- ("triangle_undirected_grouped", k_tri_und.hip).  Single device.
+bool fused_undirected_triangle(capsmi_session* s, const capsmi_table* in, const PlanNode& g, const std::vector<Path>& B,
+                               capsmi_table** out) {
+    if (B.size() != 8 || g.a.size() > 1 || g.aggs.empty()) return false;
+    std::set<int> orients;
+    std::vector<Classified> cls(B.size());
+    std::vector<int> kinds;
+    int gp = -1;
+    for (size_t bi = 0; bi < B.size(); ++bi) {
+        const Path& P = B[bi];
+        int role[3];
+        if (closed_triangle(P, role) == TRI_NONE) return false;
+        for (int x : P.pos_node) if (x < 0) return false;
+        int o = 0;
+        for (int i = 0; i < 2; ++i) {
+            const bool incoming = P.hops[i].from_role == ROLE_DST;
+            if (P.inst[P.hops[i].rel].no_loops != incoming) return false;
+            o |= (incoming ? 1 : 0) << i;
+        }
+        if (P.inst[P.hops[2].rel].no_loops) return false;
+        o |= (P.hops[2].from == 0 ? 1 : 0) << 2;
+        orients.insert(o);
+        if (!classify(P, cls[bi]) || !all_pairs_unique(cls[bi], 3)) return false;
+        std::vector<int> k;
+        if (!agg_kinds(in, g, P, 0, 0, k)) return false;
+        for (int x : k) if (x != A_COUNT) return false;
+        if (bi == 0) kinds = k;
+        if (!g.a.empty()) {
+            const int gc = find_col(in, g.a[0]);
+            if (gc < 0 || !id_like(P, P.cols[gc])) return false;
+            const int p = position_of(P, P.cols[gc]);
+            if (p < 0 || p > 2 || (bi > 0 && p != gp)) return false;
+            gp = p;
+        }
+    }
+    if (orients.size() != B.size()) return false;
+    int64_t lo, hi;
+    if (!id_window(B, &lo, &hi) || g_dist.on) return false;
+    // one relationship set for every hop of every branch, read as (start, end)
+    auto plain_views = [&](const Path& P, const Hop& hp, RelViews& v) {
+        Hop fwd = hp;
+        fwd.from_role = ROLE_SRC;
+        fwd.to_role = ROLE_DST;
+        rel_views(P, fwd, v);
+    };
+    RelViews v0;
+    plain_views(B[0], B[0].hops[0], v0);
+    for (const Path& P : B)
+        for (const Hop& hp : P.hops) {
+            RelViews v;
+            plain_views(P, hp, v);
+            if (v.sig != v0.sig) return false;
+        }
+    // one node filter for all three positions of every branch
+    BitmapSet bs;
+    std::string k0;
+    capsmi_bitmap* a = node_bitmap(s, B[0], cls[0], B[0].pos_node[0], lo, hi, bs, &k0);
+    if (!a) return false;
+    for (size_t bi = 0; bi < B.size(); ++bi)
+        for (int q = 0; q < 3; ++q) {
+            std::string kq;
+            if (!node_bitmap(s, B[bi], cls[bi], B[bi].pos_node[q], lo, hi, bs, &kq) || kq != k0) return false;
+        }
+    const int nt = (int)v0.t.size();
+    if (nt <= 0) return false;
+    if (g.a.empty()) {
+        int64_t x = 0;
+        check(capsmi_triangle_count_undirected(s, (int32_t)nt, v0.t.data(), "s", "t", a, &x));
+        auto* r = result_table(s, 1);
+        for (size_t i = 0; i < kinds.size(); ++i) {
+            Column c = i64_column(s, {x});
+            c.name = g.aggs[i].output;
+            r->cols.push_back(std::move(c));
+        }
+        *out = r;
+        route(s, "triangle_undirected");
+        return true;
+    }
+    std::vector<const int64_t*> srcs, dsts;
+    std::vector<int64_t> ms;
+    for (capsmi_table* t : v0.t) {
+        srcs.push_back(t->cols[0].d());
+        dsts.push_back(t->cols[1].d());
+        ms.push_back(t->nrows);
+    }
+    Buf ids, cnt;
+    int64_t rows = 0;
+    {
+        TriGraph tg;
+        tri_build(s, srcs.data(), dsts.data(), ms.data(), (int)srcs.size(), a, tg);
+        rows = tri_und_count_by_node(s, tg, gp == 1 ? CAPSMI_TRI_UND_MIDDLE : CAPSMI_TRI_UND_END, ids, cnt);
+    }
+    ids_to_long(s, lo, ::capsmi::P<int64_t>(ids), rows);
+    auto* r = result_table(s, rows);
+    std::unique_ptr<capsmi_table> guard(r);
+    Column k;
+    k.type = CAPSMI_I64;
+    k.data = ids;
+    r->cols.push_back(std::move(k));
+    for (size_t i = 0; i < kinds.size(); ++i) {  // every aggregate is the same count
+        Column v;
+        v.type = CAPSMI_I64;
+        v.data = cnt;
+        r->cols.push_back(std::move(v));
+    }
+    *out = guard.release();
+    route(s, "triangle_undirected_grouped");
+    return true;
+}
+
 // The var-length grouped count over BY_SOURCE shards: this rank owns the
 // start ids [rank * span, (rank + 1) * span) and holds their out-relationships (`views`) plus the
 // relationships into its owned ids from other ranks (the bases' in-shards, exchanged at registration).
@@ -1900,7 +2019,7 @@ bool try_fused_shapes(capsmi_table* t, capsmi_table** out) {
         if (p.a.empty()) {
             if (B.size() != 1) {
                 std::vector<int64_t> vals;
-                if (!fused_undirected(s, in, p, B, vals)) return false;
+                if (!fused_undirected(s, in, p, B, vals)) return fused_undirected_triangle(s, in, p, B, out);
                 auto* r = result_table(s, 1);
                 for (size_t i = 0; i < vals.size(); ++i) {
                     Column c = i64_column(s, {vals[i]});
@@ -1926,6 +2045,7 @@ bool try_fused_shapes(capsmi_table* t, capsmi_table** out) {
         }
         if (fused_grouped_two_hop(s, in, p, B, out)) return true;
         if (fused_grouped_triangle(s, in, p, B, out)) return true;
+        if (fused_undirected_triangle(s, in, p, B, out)) return true;
         return fused_var_length(s, in, p, B, out);
     }
     std::vector<Path> B;

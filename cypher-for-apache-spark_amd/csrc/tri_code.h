@@ -37,5 +37,20 @@ __device__ __forceinline__ unsigned long long tri_weight(uint64_t puv, uint64_t 
     return m_uv * m_vw * m_wu + m_uw * m_wv * m_vu;
 }
 
+// The weight of a hit as a template parameter of the combined list walks (k_tri_small, k_tri_big_items):
+// the directed cycle's, and the undirected triangle's U(u,v) U(v,w) U(u,w) with U = f + b of a payload
+// (k_tri_und.hip).  The latter is symmetric in the three pairs, the order of the arguments does not matter.
+struct CycleWeight {
+    static __device__ __forceinline__ unsigned long long of(uint64_t puv, uint64_t pvw, uint64_t puw) {
+        return tri_weight(puv, pvw, puw);
+    }
+};
+struct UndirectedWeight {
+    static __device__ __forceinline__ unsigned long long of(uint64_t puv, uint64_t pvw, uint64_t puw) {
+        return ((puv >> 32) + (puv & 0xffffffffULL)) * ((pvw >> 32) + (pvw & 0xffffffffULL)) *
+               ((puw >> 32) + (puw & 0xffffffffULL));
+    }
+};
+
 }  // namespace tri
 }  // namespace capsmi

@@ -729,6 +729,42 @@ capsmi_status capsmi_triangle_count_transitive_by_node(capsmi_session* s, int32_
                                                        const char* src_col, const char* dst_col,
                                                        const capsmi_bitmap* n_ok, int32_t role, const char* id_name,
                                                        const char* count_name, capsmi_table** out);
+/* The undirected triangle over the same trigraph, as RelationalPlanner plans it:
+ *   MATCH (a)-[r1]-(b)-[r2]-(c)-[r3]-(a) WHERE n_ok(a) AND n_ok(b) AND n_ok(c) RETURN count(*)
+ *   ... RETURN id(a), count(*)     (or id(b), or id(c))
+ * Bindings are rows: r1, r2, r3 are pairwise distinct, node variables may coincide, and the one node filter
+ * applies to all three positions.  The two Expands bind a self-loop once (their incoming branch runs over the
+ * relationships with start <> end); the closing ExpandInto is a union of two joins without that filter and binds
+ * a self-loop twice.  With m(x,y) the multiplicity of x->y for x != y, s(x) the self-loops at x,
+ * U(x,y) = m(x,y) + m(y,x) and Q(x,y) = U(x,y) (U(x,y) - 1), the bindings split by how many of a, b, c coincide:
+ *   three distinct nodes   U(a,b) U(b,c) U(c,a) per ordered triple; a simple triangle {x,y,z} gives 6 U U U in
+ *                          all, and 2 U U U to each corner at each position
+ *   a = b = x, c = y != x  s(x) Q(x,y)                     (r1 is a loop)
+ *   b = c = y, a = x != y  Q(x,y) s(y)                     (r2 is a loop)
+ *   a = c = x, b = y != x  2 s(x) Q(x,y)                   (r3 is a loop, bound twice)
+ *   a = b = c = x          2 s(x) (s(x)-1) (s(x)-2)
+ * The count is the sum of all of these.  The closing hop makes the positions two classes: the ends of the
+ * ExpandInto (a and c give the same rows: CAPSMI_TRI_UND_END) and the middle b (CAPSMI_TRI_UND_MIDDLE).  With
+ * T(x) = sum over y, z of U(x,y) U(y,z) U(z,x):
+ *   end(x)    = T(x) + sum_y [3 s(x) + s(y)] Q(x,y) + 2 s(x) (s(x)-1) (s(x)-2)
+ *   middle(x) = T(x) + sum_y [2 s(x) + 2 s(y)] Q(x,y) + 2 s(x) (s(x)-1) (s(x)-2)
+ * and both classes' counts sum to the count.  The _by_node forms follow the result contract of
+ * capsmi_trigraph_count_by_node: two non-nullable Long columns, the graph's own ids and the counts, one row per
+ * node with a non-zero count, in no particular order.  Single device: a trigraph of a distributed build gives
+ * CAPSMI_ERR_UNSUPPORTED; a position outside 0..1 gives CAPSMI_ERR_ILLEGAL_ARGUMENT.  Config
+ * CAPSMI_TRI_UND_COUNT = hash | walk selects the count's kernels (the same value either way). */
+enum { CAPSMI_TRI_UND_END = 0, CAPSMI_TRI_UND_MIDDLE = 1 }; /* a or c; b */
+capsmi_status capsmi_trigraph_count_undirected(capsmi_session* s, const capsmi_trigraph* g, int64_t* out_rows);
+capsmi_status capsmi_trigraph_count_undirected_by_node(capsmi_session* s, const capsmi_trigraph* g, int32_t position,
+                                                       const char* id_name, const char* count_name,
+                                                       capsmi_table** out);
+capsmi_status capsmi_triangle_count_undirected(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                               const char* src_col, const char* dst_col, const capsmi_bitmap* n_ok,
+                                               int64_t* out_rows);
+capsmi_status capsmi_triangle_count_undirected_by_node(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                                       const char* src_col, const char* dst_col,
+                                                       const capsmi_bitmap* n_ok, int32_t position, const char* id_name,
+                                                       const char* count_name, capsmi_table** out);
 /* count(*) of the 2-hop chain (capsmi_two_hop_count) on one rank of an owner(target) partition:
  * this rank's tables hold every relationship into its owned ids [own_lo, own_hi) (relative to the
  * bitmaps' lo).  begin partitions them and writes the owned ids' in-degrees inA (relationships from

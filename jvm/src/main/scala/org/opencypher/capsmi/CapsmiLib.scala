@@ -94,6 +94,10 @@ object Capsmi {
   final val TRI_ROLE_MIDDLE = 1 // b
   final val TRI_ROLE_SINK = 2   // c
 
+  // capsmi_*_count_undirected_by_node: the position class of (a)-[r1]-(b)-[r2]-(c)-[r3]-(a) that is counted
+  final val TRI_UND_END = 0    // a or c
+  final val TRI_UND_MIDDLE = 1 // b
+
   // join types (JoinType of RelationalPlanner; SparkTable.scala:205-229)
   final val JOIN_INNER = 0
   final val JOIN_LEFT_OUTER = 1
@@ -304,6 +308,14 @@ trait CapsmiLib extends Library {
                                        nOk: Pointer, outRows: LongByReference): Int
   def capsmi_triangle_count_transitive_by_node(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String,
                                                dstCol: String, nOk: Pointer, role: Int, idName: String,
+                                               countName: String, out: PointerByReference): Int
+  def capsmi_trigraph_count_undirected(s: Pointer, g: Pointer, outRows: LongByReference): Int
+  def capsmi_trigraph_count_undirected_by_node(s: Pointer, g: Pointer, position: Int, idName: String, countName: String,
+                                               out: PointerByReference): Int
+  def capsmi_triangle_count_undirected(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String, dstCol: String,
+                                       nOk: Pointer, outRows: LongByReference): Int
+  def capsmi_triangle_count_undirected_by_node(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String,
+                                               dstCol: String, nOk: Pointer, position: Int, idName: String,
                                                countName: String, out: PointerByReference): Int
   def capsmi_undirected_count(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String, dstCol: String, hops: Int,
                               a: Pointer, b: Pointer, c: Pointer, kind: Int, out: LongByReference): Int
