@@ -28,6 +28,11 @@ Numeric functions: Divide (:186, ``BinOp("/")``), Sqrt / Log / Log10 / Exp / Abs
 gives NULL; the rules are those of the Spark 2.2.1 Column calls the mapper makes (include/capsmi.h, CAPSMI_X_DIV ..
 CAPSMI_X_TO_INTEGER).
 
+Functions of a String's characters: StrSize (:124-127), StrToInteger (:231), StrToFloat (:229) and ToBoolean (:235),
+computed on the device from the bytes of the session's string store (include/capsmi.h, CAPSMI_X_STR_SIZE ..
+CAPSMI_X_TO_BOOLEAN).  The front end picks them by the operand's Cypher type; Size, ToInteger and ToFloat stay the
+list and number forms.
+
 ``compile_program`` lowers a tree to the postfix ``capsmi_expr`` program of include/capsmi.h.
 """
 from __future__ import annotations
@@ -53,6 +58,10 @@ STRING_MATCH_OPS = (X_STARTS_WITH, X_ENDS_WITH, X_CONTAINS)
 # 32..39 are unassigned; the numeric block starts at 40
 (X_DIV, X_SQRT, X_LOG, X_LOG10, X_EXP, X_ABS, X_CEIL, X_FLOOR, X_ROUND, X_SIGN, X_TO_FLOAT,
  X_TO_INTEGER) = range(40, 52)
+# 52..55 are unassigned; the functions that read a String's characters (they read the session's string store too)
+X_STR_SIZE, X_STR_TO_INTEGER, X_STR_TO_FLOAT, X_TO_BOOLEAN = range(56, 60)
+STRING_CONV_OPS = (X_STR_SIZE, X_STR_TO_INTEGER, X_STR_TO_FLOAT, X_TO_BOOLEAN)
+STRING_STORE_OPS = STRING_MATCH_OPS + STRING_CONV_OPS  # a program that holds one needs Session.sync_strings()
 
 BIN_OPS = {"=": X_EQ, "<>": X_NEQ, "<": X_LT, "<=": X_LE, ">": X_GT, ">=": X_GE, "+": X_ADD, "-": X_SUB, "*": X_MUL,
            "/": X_DIV, "&": X_BITAND, "|": X_BITOR, "<<": X_SHL, ">>>": X_SHRU}
@@ -328,6 +337,45 @@ _MATH_FUNCS = {Sqrt: X_SQRT, Log: X_LOG, Log10: X_LOG10, Exp: X_EXP, Abs: X_ABS,
                Round: X_ROUND, Sign: X_SIGN, ToFloat: X_TO_FLOAT, ToInteger: X_TO_INTEGER}
 
 
+@dataclass(frozen=True, eq=False)
+class StrSize(Expr):
+    """Size(expr) of a String (SparkSQLExprMapper.scala:124-127, ``functions.length``, Spark's
+    ``UTF8String.numChars``): the number of code points as a Long -- the bytes of the UTF-8 text that are not
+    ``10xxxxxx``, so an astral character counts 1.  NULL gives NULL.  The front end picks this class for an operand
+    of Cypher type String and ``Size`` for a list, as the mapper's own Size does."""
+    arg: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class StrToInteger(Expr):
+    """ToInteger(expr) of a String (SparkSQLExprMapper.scala:231, ``cast(IntegerType)``, Spark's
+    ``UTF8String.toInt``), held as a Long.  No trimming; the text must match ``[+-]?[0-9]*(\\.[0-9]*)?`` and be none
+    of "", "+", "-"; the fraction is checked, then dropped ("82.9" gives 82, "." gives 0); the signed integer part
+    must lie in [-2^31, 2^31 - 1].  Anything else -- an exponent, a blank, a value out of range -- is NULL."""
+    arg: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class StrToFloat(Expr):
+    """ToFloat(expr) of a String (SparkSQLExprMapper.scala:229, ``cast(DoubleType)``, Java's
+    ``Double.parseDouble``): bytes <= 0x20 are trimmed, then an optional sign and one of ``NaN`` / ``Infinity``, a
+    decimal with an optional exponent, or a hex float with its mandatory ``p`` exponent, each of the last two with
+    an optional suffix out of ``fFdD``.  The Double is correctly rounded (ties to even; subnormals, overflow to an
+    infinity and underflow to a zero included) for digit strings of any length.  Anything else is NULL."""
+    arg: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class ToBoolean(Expr):
+    """ToBoolean(expr) (SparkSQLExprMapper.scala:235, ``cast(BooleanType)``, Spark's ``StringUtils.isTrueString`` /
+    ``isFalseString``).  Of a String: no trimming, ASCII case folded; "t", "true", "y", "yes", "1" give TRUE, "f",
+    "false", "n", "no", "0" FALSE, anything else NULL.  Of a Boolean: the operand itself."""
+    arg: Expr
+
+
+_STRING_CONV = {StrSize: X_STR_SIZE, StrToInteger: X_STR_TO_INTEGER, StrToFloat: X_STR_TO_FLOAT, ToBoolean: X_TO_BOOLEAN}
+
+
 def _sorted_by_name(cols, names):
     cols, names = tuple(cols), tuple(names)
     if len(cols) != len(names):
@@ -560,6 +608,9 @@ def compile_program(e: Expr, column_index: Callable[[str], int], encode_str: Cal
         elif type(x) in _MATH_FUNCS:
             go(x.arg)
             out.append((_MATH_FUNCS[type(x)], 0, 0, 0))
+        elif type(x) in _STRING_CONV:
+            go(x.arg)
+            out.append((_STRING_CONV[type(x)], 0, 0, 0))
         elif isinstance(x, RelType):
             go(x.to_case())
         elif isinstance(x, Case):

@@ -29,7 +29,8 @@ import numpy as np
 
 from .expr import (BOOL, F64, I64, LIST, STR, Ands, BinOp, Col, Explode, Expr, In, IsNotNull, IsNull, ListLit, Lit, Not, Ors,
                    Contains, EndsWith, Index, InList, Keys, Labels, Range, Size, StartsWith, ands, eq,
-                   Abs, Ceil, E, Exp, Floor, Log, Log10, Round, Sign, Sqrt, ToFloat, ToInteger)
+                   Abs, Ceil, E, Exp, Floor, Log, Log10, Round, Sign, Sqrt, ToFloat, ToInteger,
+                   StrSize, StrToFloat, StrToInteger, ToBoolean)
 from .table import ColumnData, decode_value
 
 
@@ -442,6 +443,9 @@ _CMP = {"=", "<>", "<", "<=", ">", ">=", "+", "-", "*", "/"}
 _STRING_MATCH = {"starts_with": StartsWith, "ends_with": EndsWith, "contains": Contains}
 _MATH = {"sqrt": Sqrt, "log": Log, "log10": Log10, "exp": Exp, "abs": Abs, "ceil": Ceil, "floor": Floor,
          "round": Round, "sign": Sign, "tofloat": ToFloat, "tointeger": ToInteger}
+# the functions of a String's characters: the mirror has no types, so the words differ from "size", "tointeger" and
+# "tofloat", which stay the list and number forms
+_STRING_CONV = {"str_size": StrSize, "str_tointeger": StrToInteger, "str_tofloat": StrToFloat, "toboolean": ToBoolean}
 
 
 def to_expr(spec, header: Sequence[str]) -> Expr:
@@ -485,6 +489,8 @@ def to_expr(spec, header: Sequence[str]) -> Expr:
         return _STRING_MATCH[op](to_expr(spec[1], header), to_expr(spec[2], header))
     if op in _MATH:  # ["sqrt", x] .. ["sign", x], ["tofloat", x], ["tointeger", x]
         return _MATH[op](to_expr(spec[1], header))
+    if op in _STRING_CONV:  # ["str_size", s], ["str_tointeger", s], ["str_tofloat", s], ["toboolean", x]
+        return _STRING_CONV[op](to_expr(spec[1], header))
     if op == "e":  # ["e"]
         return E
     if op == "range":

@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _lib
 from .expr import (BOOL, F64, I64, LIST, STR, BinOp, CapsmiExpr, Case, Col, Explode, Expr, In, Index, InList, Keys, Labels, ListLit,
-                   Lit, Param, Range, Size, STRING_MATCH_OPS, contains_range, needs_list_lowering, compile_program,
+                   Lit, Param, Range, Size, STRING_STORE_OPS, contains_range, needs_list_lowering, compile_program,
                    contains_explode, mask_list_args, to_ctypes)
 
 _TLS = threading.local()
@@ -279,9 +279,10 @@ class Session:
 
     def sync_strings(self) -> None:
         """Register the dictionary's strings as the session's string store (include/capsmi.h
-        capsmi_session_set_strings), which StartsWith / EndsWith / Contains read on the device.  Uploads the whole
-        dictionary when it has grown since the last upload, else nothing; codes are stable, so every store is a
-        superset of the one before and programs compiled earlier stay valid."""
+        capsmi_session_set_strings), which StartsWith / EndsWith / Contains and StrSize / StrToInteger / StrToFloat /
+        ToBoolean read on the device.  Uploads the whole dictionary when it has grown since the last upload, else
+        nothing; codes are stable, so every store is a superset of the one before and programs compiled earlier stay
+        valid."""
         if self._strings_at == self.dictionary.growth:
             return
         codes, offsets, data = self.dictionary.arrays()
@@ -612,7 +613,7 @@ class GpuTable:
             return index[name]
 
         prog = compile_program(e, col, self.session.encode_str)
-        if any(p[0] in STRING_MATCH_OPS for p in prog):  # the literals are encoded by now: the store holds them
+        if any(p[0] in STRING_STORE_OPS for p in prog):  # the literals are encoded by now: the store holds them
             self.session.sync_strings()
         arr = to_ctypes(prog)
         if type(e) is Col:

@@ -176,7 +176,8 @@ struct Config {
                                   //   builds none and reads none
     int str_match = 0;            // CAPSMI_STR_MATCH = auto | rows | dict (0..2): which side a string match with a constant
                                   //   pattern runs on -- once per row, or once per entry of the string store with a
-                                  //   lookup per row (auto: the store when the table has at least as many rows; k_strmatch.hip)
+                                  //   lookup per row (auto: the store when the table has at least as many rows; k_strmatch.hip);
+                                  //   size() / toInteger() / toFloat() / toBoolean() of a String column likewise (k_strconv.hip)
 };
 // the environment's values over the defaults
 Config config_from_env();
@@ -409,6 +410,18 @@ void str_match(capsmi_session* s, int32_t op, const StrOperand& h, const StrOper
                uint8_t* out_valid);
 // the same for two constants, on the host (reads their bytes back; synchronises)
 bool str_match_fold(capsmi_session* s, int32_t op, int64_t hcode, int64_t pcode);
+// the pieces of it that k_strconv.hip shares.  The store index of a constant's code (throws ILLEGAL_ARGUMENT when it
+// is not registered); idx[r] = the store index of row r's code, -1 for a null row and for an absent code, which
+// also sets err[0] (queued, timer str_index); the check of err[0] afterwards (synchronises, throws)
+int64_t str_const_index(const StrStore& S, int64_t code);
+void str_index_rows(capsmi_session* s, const StrStore& S, const StrOperand& o, int64_t n, int64_t* idx, int64_t* err);
+void str_index_check(capsmi_session* s, const int64_t* err);
+// size(), toInteger(), toFloat() and toBoolean() of Strings (k_strconv.hip; the parsers are str_conv.h).
+// out / out_valid[r] = CAPSMI_X_STR_SIZE .. CAPSMI_X_TO_BOOLEAN `op` of the rows' words o (not a constant) over the
+// store registered now; throws as str_match does (synchronises)
+void str_conv(capsmi_session* s, int32_t op, const StrOperand& o, int64_t n, int64_t* out, uint8_t* out_valid);
+// the same for a constant, on the host (reads its bytes back; synchronises): whether the result is not NULL, and it
+bool str_conv_fold(capsmi_session* s, int32_t op, int64_t code, int64_t* value);
 // range(from, to, step) per row (step null: 1) as a store whose list r is row r's; `valid`: the rows none of
 // whose operands is null.  Throws ILLEGAL_ARGUMENT for a step 0, UNSUPPORTED for more elements than the device
 // holds (synchronises)

@@ -20,7 +20,8 @@ constexpr int kMaxCols = 64;   // columns a program may address
 inline bool is_list_type(int32_t t) { return t >= CAPSMI_LIST_I64 && t <= CAPSMI_LIST_STR; }
 
 // A new opcode of include/capsmi.h gets a row in expr_pops and check_program.  The numbers are not contiguous
-// (32..39 are unassigned): an opcode is unknown exactly when expr_pops has no row for it (known_expr_op below).
+// (32..39 and 52..55 are unassigned): an opcode is unknown exactly when expr_pops has no row for it (known_expr_op
+// below).
 
 // the numeric block (DIV .. TO_INTEGER): what k_expr.hip's math instantiation adds to the interpreter
 constexpr bool is_math_op(int32_t op) { return op >= CAPSMI_X_DIV && op <= CAPSMI_X_TO_INTEGER; }
@@ -28,6 +29,13 @@ inline const char* math_op_name(int32_t op) {
     static const char* const names[] = {"DIV", "SQRT", "LOG", "LOG10", "EXP", "ABS", "CEIL", "FLOOR", "ROUND", "SIGN",
                                         "TO_FLOAT", "TO_INTEGER"};
     return names[op - CAPSMI_X_DIV];
+}
+
+// the functions that read a String's characters (STR_SIZE .. TO_BOOLEAN): lowered to passes of their own
+// (k_strconv.hip) before the interpreter runs
+constexpr bool is_str_conv(int32_t op) { return op >= CAPSMI_X_STR_SIZE && op <= CAPSMI_X_TO_BOOLEAN; }
+constexpr int32_t str_conv_type(int32_t op) {  // the result's type
+    return op == CAPSMI_X_STR_TO_FLOAT ? CAPSMI_F64 : (op == CAPSMI_X_TO_BOOLEAN ? CAPSMI_BOOL : CAPSMI_I64);
 }
 
 // operands an opcode pops: the one arity table (-1: unknown opcode, CAPSMI_X_PARAM included: it is bound before
@@ -38,7 +46,8 @@ inline int expr_pops(const capsmi_expr& x) {
         case CAPSMI_X_NOT: case CAPSMI_X_ISNULL: case CAPSMI_X_ISNOTNULL: case CAPSMI_X_NEG: case CAPSMI_X_SIZE:
         case CAPSMI_X_SQRT: case CAPSMI_X_LOG: case CAPSMI_X_LOG10: case CAPSMI_X_EXP: case CAPSMI_X_ABS:
         case CAPSMI_X_CEIL: case CAPSMI_X_FLOOR: case CAPSMI_X_ROUND: case CAPSMI_X_SIGN: case CAPSMI_X_TO_FLOAT:
-        case CAPSMI_X_TO_INTEGER: return 1;
+        case CAPSMI_X_TO_INTEGER: case CAPSMI_X_STR_SIZE: case CAPSMI_X_STR_TO_INTEGER: case CAPSMI_X_STR_TO_FLOAT:
+        case CAPSMI_X_TO_BOOLEAN: return 1;
         case CAPSMI_X_AND: case CAPSMI_X_OR: case CAPSMI_X_COALESCE: return x.arg;
         case CAPSMI_X_IN: return x.arg + 1;
         case CAPSMI_X_CASE: return 2 * x.arg + 1;
@@ -95,6 +104,8 @@ inline std::vector<std::pair<int, int>> operand_spans(const capsmi_expr* prog, i
 //     operand): CAPSMI_ERR_ILLEGAL_ARGUMENT.
 //   - The numeric block takes numbers: an operand typed BOOL or STR is CAPSMI_ERR_NOT_IMPLEMENTED; an untyped NULL
 //     and a mixed entry pass (a row that holds no number yields NULL, as for ADD).
+//   - STR_SIZE, STR_TO_INTEGER, STR_TO_FLOAT and TO_BOOLEAN take a String (or an untyped NULL), TO_BOOLEAN a BOOL
+//     too: any other scalar type and a mixed entry are CAPSMI_ERR_ILLEGAL_ARGUMENT.
 inline int32_t check_program(const int32_t* col_types, int ncols, int32_t nn, const capsmi_expr* prog) {
     struct Entry {
         int32_t t;
@@ -158,6 +169,16 @@ inline int32_t check_program(const int32_t* col_types, int ncols, int32_t nn, co
                             "or typed String)");
                 }
                 res.t = CAPSMI_BOOL;
+                break;
+            case CAPSMI_X_STR_SIZE: case CAPSMI_X_STR_TO_INTEGER: case CAPSMI_X_STR_TO_FLOAT: case CAPSMI_X_TO_BOOLEAN:
+                REQUIRE(!opd[0].mixed, CAPSMI_ERR_ILLEGAL_ARGUMENT, kMixed);
+                REQUIRE(opd[0].t < 0 || opd[0].t == CAPSMI_STR || (x.op == CAPSMI_X_TO_BOOLEAN && opd[0].t == CAPSMI_BOOL),
+                        CAPSMI_ERR_ILLEGAL_ARGUMENT,
+                        x.op == CAPSMI_X_TO_BOOLEAN
+                            ? "toBoolean takes a String or a Boolean operand (or a NULL literal that is untyped or typed so)"
+                            : "size(), toInteger() and toFloat() of a String take a String operand (or a NULL literal that "
+                              "is untyped or typed String)");
+                res.t = str_conv_type(x.op);
                 break;
             case CAPSMI_X_NEG: case CAPSMI_X_ABS: res = opd[0]; break;
             case CAPSMI_X_COALESCE: case CAPSMI_X_CASE: {  // CASE: [p1, v1, .., default]; the predicates are BOOL

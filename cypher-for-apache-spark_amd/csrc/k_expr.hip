@@ -21,6 +21,8 @@
 //     all the rows' elements before this interpreter runs.  No other opcode takes a list.
 //   - STARTS WITH / ENDS WITH / CONTAINS (SparkSQLExprMapper.scala:152-157) are lowered on the host the same way
 //     (lower_str_match below): k_strmatch.hip matches the bytes of the session's string store.
+//   - size(), toInteger(), toFloat() and toBoolean() of a String (:124-127, :231, :229, :235) are lowered likewise
+//     (lower_str_conv below): k_strconv.hip reads the store's bytes, and the interpreter never sees these opcodes.
 //   - Divide (:186), Sqrt .. Sign (:249-260), ToFloat / ToInteger (:229-231): eval_math below, with the rules of the
 //     Spark 2.2.1 Column calls the mapper makes (include/capsmi.h states them per opcode).  Double log and exp are
 //     library code of some size, so these cases exist only in the kMath instantiation of the interpreter, which
@@ -370,10 +372,10 @@ Lowered lowered_null(int first) {
     return l;
 }
 
-Lowered lowered_column(capsmi_session* s, int first, int64_t n, const char* name) {
+Lowered lowered_column(capsmi_session* s, int first, int64_t n, const char* name, int32_t type = CAPSMI_BOOL) {
     Lowered l{first, {}, {}};
     l.res.name = name;
-    l.res.type = CAPSMI_BOOL;
+    l.res.type = type;
     l.res.data = dev_alloc(sizeof(int64_t) * n, s);
     l.res.valid = dev_alloc(n, s);
     return l;
@@ -399,7 +401,9 @@ void replace_span_and_eval(capsmi_session* s, const capsmi_table* t, int32_t nn,
             int slot = 0;
             while (slot < kMaxCols && used[slot]) ++slot;
             REQUIRE(slot < kMaxCols, CAPSMI_ERR_NOT_IMPLEMENTED,
-                    std::string(prog[at].op == CAPSMI_X_IN_LIST ? "IN over a list column" : "a string match") +
+                    std::string(prog[at].op == CAPSMI_X_IN_LIST
+                                    ? "IN over a list column"
+                                    : (is_str_conv(prog[at].op) ? "a function of a String's characters" : "a string match")) +
                         " in a program that reads 64 columns");
             l.ref.arg = slot;
             view.cols[slot] = std::move(l.res);
@@ -457,6 +461,41 @@ Lowered lower_str_match(capsmi_session* s, const capsmi_table* t, const capsmi_e
     return l;
 }
 
+// size(), toInteger(), toFloat() or toBoolean() of a String (node `at`, stack [s]): k_strconv.hip's passes produce
+// the column.  A NULL literal operand: NULL without a kernel; a literal: folded on the host; toBoolean of a BOOL
+// is its operand.
+Lowered lower_str_conv(capsmi_session* s, const capsmi_table* t, const capsmi_expr* prog, int at) {
+    const int32_t op = prog[at].op;
+    const int32_t type = str_conv_type(op);
+    const auto span = operand_spans(prog, at)[0];
+    const capsmi_expr& x = prog[span.first];
+    Lowered l{span.first, {}, {}};
+    l.ref.op = CAPSMI_X_NULL;
+    l.ref.arg = type + 1;
+    if (span.first == span.second && x.op == CAPSMI_X_NULL) return l;
+    if (span.first == span.second && x.op == CAPSMI_X_LIT) {
+        int64_t v = x.ival;
+        if (x.type == CAPSMI_BOOL || str_conv_fold(s, op, x.ival, &v)) {
+            l.ref.op = CAPSMI_X_LIT;
+            l.ref.arg = 0;
+            l.ref.type = type;
+            l.ref.ival = v;
+        }
+        return l;
+    }
+    Column col = operand_column(s, t, prog, span.first, span.second);
+    if (col.type == CAPSMI_BOOL) {  // toBoolean of a Boolean (check_program lets no other opcode through)
+        l.res = std::move(col);
+        return l;
+    }
+    l = lowered_column(s, span.first, t->nrows, "__str_conv", type);
+    StrOperand o;
+    o.data = col.d();
+    o.valid = col.v();
+    str_conv(s, op, o, t->nrows, P<int64_t>(l.res.data), P<uint8_t>(l.res.valid));
+    return l;
+}
+
 // evaluates prog over t's rows; returns its static type
 int32_t launch_eval(capsmi_session* s, const capsmi_table* t, int32_t nn, const capsmi_expr* prog, int64_t* out,
                     uint8_t* out_valid, uint8_t* flags) {
@@ -464,8 +503,9 @@ int32_t launch_eval(capsmi_session* s, const capsmi_table* t, int32_t nn, const 
     const int64_t n = t->nrows;
     if (n == 0) return type;
     for (int i = 0; i < nn; ++i) {  // the first node that runs as a pass of its own; the recursion lowers the rest
-        if (prog[i].op != CAPSMI_X_IN_LIST && !is_str_match(prog[i].op)) continue;
-        Lowered l = (prog[i].op == CAPSMI_X_IN_LIST ? lower_in_list : lower_str_match)(s, t, prog, i);
+        if (prog[i].op != CAPSMI_X_IN_LIST && !is_str_match(prog[i].op) && !is_str_conv(prog[i].op)) continue;
+        Lowered l = (prog[i].op == CAPSMI_X_IN_LIST ? lower_in_list
+                                                    : (is_str_conv(prog[i].op) ? lower_str_conv : lower_str_match))(s, t, prog, i);
         replace_span_and_eval(s, t, nn, prog, i, l, out, out_valid, flags);
         return type;
     }

@@ -169,15 +169,6 @@ __global__ void k_str_finish(const uint8_t* __restrict__ hit, StrSide H, StrSide
 
 const char* kNoStore = "string match: no string store is registered (capsmi_session_set_strings)";
 
-// the store index of a constant's code
-int64_t const_index(const StrStore& S, int64_t code) {
-    const auto it = std::lower_bound(S.hcodes.begin(), S.hcodes.end(), code);
-    REQUIRE(it != S.hcodes.end() && *it == code, CAPSMI_ERR_ILLEGAL_ARGUMENT,
-            "string match: the code " + std::to_string((long long)code) +
-                " of a constant operand is not registered in the session's string store (capsmi_session_set_strings)");
-    return it - S.hcodes.begin();
-}
-
 // hit[i] for i < n "rows" whose strings are at H and Pt; columns: the index arrays among them
 void match_pass(capsmi_session* s, int32_t op, const StrStore& S, const StrSide& H, const StrSide& Pt, int64_t n,
                 uint8_t* hit) {
@@ -227,13 +218,35 @@ void match_pass(capsmi_session* s, int32_t op, const StrStore& S, const StrSide&
 
 }  // namespace
 
+int64_t str_const_index(const StrStore& S, int64_t code) {
+    const auto it = std::lower_bound(S.hcodes.begin(), S.hcodes.end(), code);
+    REQUIRE(it != S.hcodes.end() && *it == code, CAPSMI_ERR_ILLEGAL_ARGUMENT,
+            "string match: the code " + std::to_string((long long)code) +
+                " of a constant operand is not registered in the session's string store (capsmi_session_set_strings)");
+    return it - S.hcodes.begin();
+}
+
+void str_index_rows(capsmi_session* s, const StrStore& S, const StrOperand& o, int64_t n, int64_t* idx, int64_t* err) {
+    // algorithmic bytes: the row's word (and validity byte) read, its index written, the codes it searches
+    KernelTimer kt(s, "str_index", (16.0 + (o.valid ? 1.0 : 0.0)) * (double)n + 8.0 * (double)S.n);
+    hipLaunchKernelGGL(k_str_index, dim3(grid_for(n)), dim3(256), 0, s->stream, P<int64_t>(S.codes), S.n, o.data, o.valid, n,
+                       idx, err);
+    HIP_CHECK(hipGetLastError());
+}
+
+void str_index_check(capsmi_session* s, const int64_t* err) {
+    REQUIRE(read_scalar(s, err) == 0, CAPSMI_ERR_ILLEGAL_ARGUMENT,
+            "string match: a String value's code is not registered in the session's string store "
+            "(capsmi_session_set_strings)");
+}
+
 bool str_match_fold(capsmi_session* s, int32_t op, int64_t hcode, int64_t pcode) {
     const std::shared_ptr<const StrStore> S = s->strings;
     REQUIRE(S, CAPSMI_ERR_ILLEGAL_ARGUMENT, kNoStore);
     std::string str[2];
     const int64_t code[2] = {hcode, pcode};
     for (int q = 0; q < 2; ++q) {
-        const int64_t i = const_index(*S, code[q]);
+        const int64_t i = str_const_index(*S, code[q]);
         const int64_t b = S->hoffsets[i], len = S->hoffsets[i + 1] - b;
         str[q].resize(len);
         if (len > 0)
@@ -259,7 +272,7 @@ void str_match(capsmi_session* s, int32_t op, const StrOperand& h, const StrOper
     const StrOperand* opd[2] = {&h, &p};
     for (int q = 0; q < 2; ++q) {
         if (opd[q]->is_const) {
-            side[q] = StrSide{nullptr, const_index(*S, opd[q]->code)};
+            side[q] = StrSide{nullptr, str_const_index(*S, opd[q]->code)};
             continue;
         }
         if (!err) {
@@ -267,16 +280,10 @@ void str_match(capsmi_session* s, int32_t op, const StrOperand& h, const StrOper
             fill_i64(P<int64_t>(err), 0, 1, st);
         }
         idx[q] = dev_alloc(sizeof(int64_t) * n, s);
-        // algorithmic bytes: the row's word (and validity byte) read, its index written, the codes it searches
-        KernelTimer kt(s, "str_index", (16.0 + (opd[q]->valid ? 1.0 : 0.0)) * (double)n + 8.0 * (double)S->n);
-        hipLaunchKernelGGL(k_str_index, dim3(grid_for(n)), dim3(256), 0, st, P<int64_t>(S->codes), S->n, opd[q]->data,
-                           opd[q]->valid, n, P<int64_t>(idx[q]), P<int64_t>(err));
-        HIP_CHECK(hipGetLastError());
+        str_index_rows(s, *S, *opd[q], n, P<int64_t>(idx[q]), P<int64_t>(err));
         side[q] = StrSide{P<int64_t>(idx[q]), 0};
     }
-    REQUIRE(read_scalar(s, P<int64_t>(err)) == 0, CAPSMI_ERR_ILLEGAL_ARGUMENT,
-            "string match: a String value's code is not registered in the session's string store "
-            "(capsmi_session_set_strings)");
+    if (err) str_index_check(s, P<int64_t>(err));
     // the dictionary side: a constant pattern is matched once per store entry and the rows look their entry up
     const bool can_dict = p.is_const && !h.is_const;
     const bool dict = can_dict && (s->cfg.str_match == 2 || (s->cfg.str_match == 0 && n >= S->n));

@@ -208,10 +208,50 @@ enum {
                                  0; functions.signum(e).cast(IntegerType), :259 */
     CAPSMI_X_TO_FLOAT = 50,   /* stack [x]: Double; a Long is converted, a Double stays; cast(DoubleType), :229.
                                  String operands are not implemented */
-    CAPSMI_X_TO_INTEGER = 51  /* stack [x]: Long holding Spark's 32-bit IntegerType: from Long the low 32 bits,
+    CAPSMI_X_TO_INTEGER = 51, /* stack [x]: Long holding Spark's 32-bit IntegerType: from Long the low 32 bits,
                                  sign-extended (2^31 gives -2^31, 2^32 + 5 gives 5); from Double truncated
                                  toward zero and saturated to [-2^31, 2^31 - 1], NaN 0; cast(IntegerType),
                                  :231.  String operands are not implemented */
+    /* 52..55 are unassigned. */
+    /* Functions that read a String's characters (Size of a String, :124-127, functions.length; ToFloat, :229;
+       ToInteger, :231; ToBoolean, :235).  Stack [s]: CAPSMI_STR or a NULL literal (typed STR or untyped), for
+       TO_BOOLEAN also BOOL; any other scalar type is CAPSMI_ERR_ILLEGAL_ARGUMENT when the node is built, as is a
+       "mixed" value; a list value is CAPSMI_ERR_NOT_IMPLEMENTED.  The operand may be any scalar expression.  A
+       NULL operand gives NULL.  The bytes come from the string store that is registered when the action runs
+       (capsmi_session_set_strings): without one the action fails with CAPSMI_ERR_ILLEGAL_ARGUMENT ("no string
+       store"), as it does when a non-null operand's code is not registered in it.  A NULL literal operand gives
+       NULL in every row without a kernel; a literal operand is folded on the host.  Each of these nodes runs as
+       passes of its own before the row-wise interpreter (k_strconv.hip; the parsing code is csrc/str_conv.h),
+       which then reads its result as a column.  With CAPSMI_STR_MATCH = auto the conversion runs once per store
+       entry and the rows look their entry up when the table has at least as many rows as the store has entries,
+       else once per row; rows | dict force a side.  The rules are those of the Spark 2.2.1 calls the mapper
+       makes, stated from knowledge of Spark's source, not from a run. */
+    CAPSMI_X_STR_SIZE = 56,       /* stack [s]: Long, the number of code points (UTF8String.numChars): the count of
+                                     bytes that are not 10xxxxxx, so an astral character counts 1 (Java's
+                                     String.length would say 2).  For bytes that are not well-formed UTF-8 the
+                                     result is that same count; Spark's walk by lead byte differs there.  The
+                                     count is load-balanced over fixed tiles of the store's byte array */
+    CAPSMI_X_STR_TO_INTEGER = 57, /* stack [s]: Long holding Spark's 32-bit IntegerType (UTF8String.toInt).  No
+                                     trimming.  The bytes must match [+-]?[0-9]*(\.[0-9]*)? and be none of "",
+                                     "+", "-"; the fraction is checked, then dropped ("82.9" gives 82, "-82.9"
+                                     -82, ".", "+." and ".5" give 0); the signed integer part, at any number of
+                                     digits, must lie in [-2^31, 2^31 - 1].  Anything else is NULL: an exponent,
+                                     a blank, a second dot, a non-ASCII digit, a value out of range */
+    CAPSMI_X_STR_TO_FLOAT = 58,   /* stack [s]: Double, Java's Double.parseDouble(s.toString); what throws
+                                     NumberFormatException is NULL.  Bytes <= 0x20 are trimmed at both ends; an
+                                     optional sign; then exactly one of: "NaN" or "Infinity" (case-sensitive; NaN
+                                     is the one quiet NaN whatever the sign); a decimal D+ [.] D* or . D+ with an
+                                     optional exponent [eE][+-]?D+ and an optional suffix out of fFdD; a hex float
+                                     0[xX] with H+ [.] H* or . H+, a mandatory [pP][+-]?D+ and the optional suffix.
+                                     The value is correctly rounded, ties to even, subnormals, overflow to
+                                     +-Infinity and underflow to +-0.0 included ("-0" gives -0.0), for mantissa
+                                     and exponent digit strings of any length.  Any other byte gives NULL, every
+                                     non-ASCII byte among them */
+    CAPSMI_X_TO_BOOLEAN = 59      /* stack [s] or [b]: BOOL.  Of a String (StringUtils.isTrueString /
+                                     isFalseString over toLowerCase): no trimming, ASCII case folded (none of the
+                                     words has a non-ASCII case partner); "t", "true", "y", "yes", "1" give TRUE,
+                                     "f", "false", "n", "no", "0" FALSE, anything else NULL.  Of a BOOL: the
+                                     identity */
 };
 
 typedef struct {
@@ -311,6 +351,12 @@ capsmi_status capsmi_session_kernel_time(capsmi_session* s, const char* name, in
  * on the data and are not counted); "str_match_lookup", the dictionary side's row gather: 18 B per row;
  * CONTAINS's lengths / scan / compaction are timed as "str_match_starts" and the row side's three-valued finish as
  * "str_match_finish", both without bytes);
+ * size() / toInteger() / toFloat() / toBoolean() of Strings share "str_index"; "str_conv", the conversion over n rows
+ * -- or over the store's entries on the dictionary side: two offsets (16 B) per row, on the rows side its index word
+ * (8 B) too, 9 B written per row (size: 8 B), and the strings' bytes once each where they are known -- on the
+ * dictionary side the whole byte array, for size one byte per slot; on the rows side of the parsers they depend on
+ * the data and are not counted; "str_conv_lookup", the dictionary side's row gather: 26 B per row (size: 25 B);
+ * size's lengths / scan / compaction are timed as "str_conv_starts", without bytes;
  * 0 otherwise; then the counter resets. */
 capsmi_status capsmi_session_kernel_bytes(capsmi_session* s, const char* name, double* bytes);
 /* fused-path routing of lazy plans: enable / disable (default on; off = operator by operator, for

@@ -84,6 +84,11 @@ object Capsmi {
   final val X_SIGN = 49        // [x]: Long -1, 0, 1
   final val X_TO_FLOAT = 50    // [x]: Double
   final val X_TO_INTEGER = 51  // [x]: Long holding a 32-bit Int
+  // 52..55 are unassigned.  Functions of a String's characters, over the session's string store (include/capsmi.h)
+  final val X_STR_SIZE = 56        // [s]: Long, the number of code points
+  final val X_STR_TO_INTEGER = 57  // [s]: Long holding a 32-bit Int, NULL for what UTF8String.toInt refuses
+  final val X_STR_TO_FLOAT = 58    // [s]: Double, Double.parseDouble correctly rounded, NULL for what it refuses
+  final val X_TO_BOOLEAN = 59      // [s] or [b]: BOOL; the ten words of StringUtils, else NULL; a Boolean stays
 
   // capsmi_with_mask_list_column: which columns of a row pass
   final val MASK_TRUE = 0     // labels(): the Boolean flag is non-null and TRUE

@@ -94,7 +94,8 @@ final class GpuSession(device: Int = 0) extends RelationalCypherSession[GpuTable
   private var stringsAt = -1L
 
   /** Registers the dictionary as the session's string store (capsmi_session_set_strings) when it has grown since
-    * the last upload: ExprCompiler calls it for every program with a StartsWith / EndsWith / Contains, after the
+    * the last upload: ExprCompiler calls it for every program that reads a String's bytes (StartsWith / EndsWith /
+    * Contains, Size / ToFloat / ToInteger of a String, ToBoolean), after the
     * program's literals are encoded.  Codes are stable, so every store is a superset of the one before. */
   def syncStrings(): Unit = synchronized {
     if (stringsAt != dictionary.growth) {

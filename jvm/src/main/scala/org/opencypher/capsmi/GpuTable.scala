@@ -381,8 +381,11 @@ final class GpuTable private (val handle: Pointer)(implicit val session: GpuSess
   * (:152-157) are CAPSMI_X_STARTS_WITH / ENDS_WITH / CONTAINS; a program that holds one uploads the session's
   * string store first (GpuSession.syncStrings).  Divide (:186), Sqrt / Log / Log10 / Exp / Abs / Ceil / Floor /
   * Round / Sign (:249-260) and ToFloat / ToInteger of numbers (:229-231) are CAPSMI_X_DIV .. CAPSMI_X_TO_INTEGER,
-  * E() the literal Math.E.  Shapes the device path does not evaluate (regular expressions, other functions, maps,
-  * size() / toFloat() / toInteger() of a string, rand()) raise NotImplementedException.
+  * E() the literal Math.E.  Size (:126-127), ToFloat and ToInteger of an operand of type CTString and ToBoolean (:235)
+  * are CAPSMI_X_STR_SIZE / STR_TO_FLOAT / STR_TO_INTEGER / TO_BOOLEAN, chosen by the operand's Cypher type as the
+  * mapper's own Size chooses; they read the string store too.  Shapes the device path does not evaluate (regular
+  * expressions, other functions, maps, toString, + on strings, toBoolean of a number, rand()) raise
+  * NotImplementedException or, from the library, IllegalArgumentException.
   */
 final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters: CypherMap,
                               lists: Map[Expr, String] = Map.empty) {
@@ -395,7 +398,8 @@ final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters:
     go(e, out)
     if (params.nonEmpty) bindParams()
     // the literals and parameters are encoded by now, so the store holds every string the program names
-    if (out.exists(n => n._1 >= Capsmi.X_STARTS_WITH && n._1 <= Capsmi.X_CONTAINS)) table.session.syncStrings()
+    if (out.exists(n => (n._1 >= Capsmi.X_STARTS_WITH && n._1 <= Capsmi.X_CONTAINS) ||
+        (n._1 >= Capsmi.X_STR_SIZE && n._1 <= Capsmi.X_TO_BOOLEAN))) table.session.syncStrings()
     out
   }
 
@@ -434,8 +438,7 @@ final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters:
 
   private def go(e: Expr, out: mutable.ArrayBuffer[Node]): Unit = e match {
     case Size(ListLit(vs)) => out += lit(Capsmi.I64, vs.size.toLong)
-    case Size(x) if x.cypherType.material == CTString =>
-      throw NotImplementedException("size() of a string on the device path: string lengths live in the caller's dictionary")
+    case Size(x) if x.cypherType.material == CTString => go(x, out); out += ((Capsmi.X_STR_SIZE, 0, 0, 0L)) // functions.length, :126-127
     case Size(x) => list(x, out); out += ((Capsmi.X_SIZE, 0, 0, 0L))
     case ContainerIndex(container, index) => list(container, out); go(index, out); out += ((Capsmi.X_INDEX, 0, 0, 0L))
     case In(lhs, rhs) if listColumn(rhs) => go(lhs, out); list(rhs, out); out += ((Capsmi.X_IN_LIST, 0, 0, 0L))
@@ -480,12 +483,12 @@ final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters:
     case Floor(x) => go(x, out); out += ((Capsmi.X_FLOOR, 0, 0, 0L))
     case Round(x) => go(x, out); out += ((Capsmi.X_ROUND, 0, 0, 0L))
     case Sign(x) => go(x, out); out += ((Capsmi.X_SIGN, 0, 0, 0L))
-    case ToFloat(x) if x.cypherType.material == CTString =>
-      throw NotImplementedException("toFloat() of a string on the device path: the bytes live in the caller's dictionary")
+    case ToFloat(x) if x.cypherType.material == CTString => go(x, out); out += ((Capsmi.X_STR_TO_FLOAT, 0, 0, 0L))
     case ToFloat(x) => go(x, out); out += ((Capsmi.X_TO_FLOAT, 0, 0, 0L))
-    case ToInteger(x) if x.cypherType.material == CTString =>
-      throw NotImplementedException("toInteger() of a string on the device path: the bytes live in the caller's dictionary")
+    case ToInteger(x) if x.cypherType.material == CTString => go(x, out); out += ((Capsmi.X_STR_TO_INTEGER, 0, 0, 0L))
     case ToInteger(x) => go(x, out); out += ((Capsmi.X_TO_INTEGER, 0, 0, 0L))
+    // cast(BooleanType), :235: of a String or a Boolean; the library refuses numbers when the node is built
+    case ToBoolean(x) => go(x, out); out += ((Capsmi.X_TO_BOOLEAN, 0, 0, 0L))
     case BitwiseAnd(l, r) => bin(Capsmi.X_BITAND, l, r, out)
     case BitwiseOr(l, r) => bin(Capsmi.X_BITOR, l, r, out)
     case ShiftLeft(v, bits) => bin(Capsmi.X_SHL, v, bits, out)
