@@ -224,6 +224,24 @@ class VarlenShard:
             pass
 
 
+def _int_of(fn: str, *args) -> int:
+    """the int64 a library call returns through its last argument"""
+    v = ctypes.c_int64()
+    _lib.call(fn, *args, ctypes.byref(v))
+    return v.value
+
+
+def _table_of(session: Session, fn: str, *args) -> GpuTable:
+    """the table a library call returns through its last argument"""
+    out = ctypes.c_void_p()
+    _lib.call(fn, *args, ctypes.byref(out))
+    return GpuTable(session, out)
+
+
+def _tri_args(session: Session, rels: Sequence[GpuTable], src_col: str, dst_col: str, n_ok: NodeBitmap) -> tuple:
+    return session.handle, len(rels), _handles(rels), src_col.encode(), dst_col.encode(), n_ok.handle
+
+
 class TriGraph:
     """Oriented simple graph with directed multiplicities for the cyclic triangle count (C4)."""
 
@@ -235,45 +253,33 @@ class TriGraph:
                   dst_col.encode(), n_ok.handle, ctypes.byref(self._h))
 
     def count(self, part: int = 0, nparts: int = 1) -> int:
-        v = ctypes.c_int64()
-        _lib.call("capsmi_trigraph_count", self.session.handle, self._h, part, nparts, ctypes.byref(v))
-        return v.value
+        return _int_of("capsmi_trigraph_count", self.session.handle, self._h, part, nparts)
 
     def count_by_node(self, id_name: str = "id", count_name: str = "count") -> GpuTable:
         """``... RETURN id(a), count(*)``: one row (id, count) per node with a non-zero count, unordered."""
-        out = ctypes.c_void_p()
-        _lib.call("capsmi_trigraph_count_by_node", self.session.handle, self._h, id_name.encode(), count_name.encode(),
-                  ctypes.byref(out))
-        return GpuTable(self.session, out)
+        return _table_of(self.session, "capsmi_trigraph_count_by_node", self.session.handle, self._h, id_name.encode(),
+                         count_name.encode())
 
     def count_transitive(self) -> int:
         """``MATCH (a)-[r1]->(b)-[r2]->(c)<-[r3]-(a) RETURN count(*)`` over the same graph."""
-        v = ctypes.c_int64()
-        _lib.call("capsmi_trigraph_count_transitive", self.session.handle, self._h, ctypes.byref(v))
-        return v.value
+        return _int_of("capsmi_trigraph_count_transitive", self.session.handle, self._h)
 
     def count_transitive_by_node(self, role: int, id_name: str = "id", count_name: str = "count") -> GpuTable:
         """The transitive triangle grouped by the node in `role` (TRI_ROLE_SOURCE a, TRI_ROLE_MIDDLE b,
         TRI_ROLE_SINK c): one row (id, count) per node with a non-zero count, unordered."""
-        out = ctypes.c_void_p()
-        _lib.call("capsmi_trigraph_count_transitive_by_node", self.session.handle, self._h, role, id_name.encode(),
-                  count_name.encode(), ctypes.byref(out))
-        return GpuTable(self.session, out)
+        return _table_of(self.session, "capsmi_trigraph_count_transitive_by_node", self.session.handle, self._h, role,
+                         id_name.encode(), count_name.encode())
 
     def count_undirected(self) -> int:
         """``MATCH (a)-[r1]-(b)-[r2]-(c)-[r3]-(a) RETURN count(*)`` over the same graph (the plan's rows: the
         closing hop binds a self-loop twice)."""
-        v = ctypes.c_int64()
-        _lib.call("capsmi_trigraph_count_undirected", self.session.handle, self._h, ctypes.byref(v))
-        return v.value
+        return _int_of("capsmi_trigraph_count_undirected", self.session.handle, self._h)
 
     def count_undirected_by_node(self, position: int, id_name: str = "id", count_name: str = "count") -> GpuTable:
         """The undirected triangle grouped by the node at a position of class `position` (TRI_UND_END a or c,
         TRI_UND_MIDDLE b): one row (id, count) per node with a non-zero count, unordered."""
-        out = ctypes.c_void_p()
-        _lib.call("capsmi_trigraph_count_undirected_by_node", self.session.handle, self._h, position, id_name.encode(),
-                  count_name.encode(), ctypes.byref(out))
-        return GpuTable(self.session, out)
+        return _table_of(self.session, "capsmi_trigraph_count_undirected_by_node", self.session.handle, self._h,
+                         position, id_name.encode(), count_name.encode())
 
     def stats(self):
         """(id-domain size, oriented simple edges)"""
@@ -298,20 +304,15 @@ class TriGraph:
 def triangle_count(session: Session, rels: Sequence[GpuTable], n_ok: NodeBitmap, src_col: str = "source",
                    dst_col: str = "target") -> int:
     """``MATCH (a)-[r1]->(b)-[r2]->(c)-[r3]->(a) RETURN count(*)`` (pairwise-distinct relationships)."""
-    v = ctypes.c_int64()
-    _lib.call("capsmi_triangle_count", session.handle, len(rels), _handles(rels), src_col.encode(), dst_col.encode(),
-              n_ok.handle, ctypes.byref(v))
-    return v.value
+    return _int_of("capsmi_triangle_count", *_tri_args(session, rels, src_col, dst_col, n_ok))
 
 
 def triangle_count_by_node(session: Session, rels: Sequence[GpuTable], n_ok: NodeBitmap, id_name: str = "id",
                            count_name: str = "count", src_col: str = "source", dst_col: str = "target") -> GpuTable:
     """``MATCH (a)-[r1]->(b)-[r2]->(c)-[r3]->(a) RETURN id(a), count(*)`` (pairwise-distinct relationships):
     one row per node with a non-zero count, unordered.  Grouping by b or by c gives the same rows."""
-    out = ctypes.c_void_p()
-    _lib.call("capsmi_triangle_count_by_node", session.handle, len(rels), _handles(rels), src_col.encode(),
-              dst_col.encode(), n_ok.handle, id_name.encode(), count_name.encode(), ctypes.byref(out))
-    return GpuTable(session, out)
+    return _table_of(session, "capsmi_triangle_count_by_node", *_tri_args(session, rels, src_col, dst_col, n_ok),
+                     id_name.encode(), count_name.encode())
 
 
 # the roles of (a)-[r1]->(b)-[r2]->(c)<-[r3]-(a) (include/capsmi.h CAPSMI_TRI_ROLE_*)
@@ -321,10 +322,7 @@ TRI_ROLE_SOURCE, TRI_ROLE_MIDDLE, TRI_ROLE_SINK = 0, 1, 2
 def triangle_count_transitive(session: Session, rels: Sequence[GpuTable], n_ok: NodeBitmap, src_col: str = "source",
                               dst_col: str = "target") -> int:
     """``MATCH (a)-[r1]->(b)-[r2]->(c)<-[r3]-(a) RETURN count(*)`` (pairwise-distinct relationships)."""
-    v = ctypes.c_int64()
-    _lib.call("capsmi_triangle_count_transitive", session.handle, len(rels), _handles(rels), src_col.encode(),
-              dst_col.encode(), n_ok.handle, ctypes.byref(v))
-    return v.value
+    return _int_of("capsmi_triangle_count_transitive", *_tri_args(session, rels, src_col, dst_col, n_ok))
 
 
 def triangle_count_transitive_by_node(session: Session, rels: Sequence[GpuTable], n_ok: NodeBitmap, role: int,
@@ -332,10 +330,8 @@ def triangle_count_transitive_by_node(session: Session, rels: Sequence[GpuTable]
                                       dst_col: str = "target") -> GpuTable:
     """``MATCH (a)-[r1]->(b)-[r2]->(c)<-[r3]-(a) RETURN id(x), count(*)`` with x the node in `role`
     (TRI_ROLE_SOURCE a, TRI_ROLE_MIDDLE b, TRI_ROLE_SINK c): one row per node with a non-zero count, unordered."""
-    out = ctypes.c_void_p()
-    _lib.call("capsmi_triangle_count_transitive_by_node", session.handle, len(rels), _handles(rels), src_col.encode(),
-              dst_col.encode(), n_ok.handle, role, id_name.encode(), count_name.encode(), ctypes.byref(out))
-    return GpuTable(session, out)
+    return _table_of(session, "capsmi_triangle_count_transitive_by_node",
+                     *_tri_args(session, rels, src_col, dst_col, n_ok), role, id_name.encode(), count_name.encode())
 
 
 # the position classes of (a)-[r1]-(b)-[r2]-(c)-[r3]-(a) (include/capsmi.h CAPSMI_TRI_UND_*): a or c; b
@@ -345,10 +341,7 @@ TRI_UND_END, TRI_UND_MIDDLE = 0, 1
 def triangle_count_undirected(session: Session, rels: Sequence[GpuTable], n_ok: NodeBitmap, src_col: str = "source",
                               dst_col: str = "target") -> int:
     """``MATCH (a)-[r1]-(b)-[r2]-(c)-[r3]-(a) RETURN count(*)`` (pairwise-distinct relationships)."""
-    v = ctypes.c_int64()
-    _lib.call("capsmi_triangle_count_undirected", session.handle, len(rels), _handles(rels), src_col.encode(),
-              dst_col.encode(), n_ok.handle, ctypes.byref(v))
-    return v.value
+    return _int_of("capsmi_triangle_count_undirected", *_tri_args(session, rels, src_col, dst_col, n_ok))
 
 
 def triangle_count_undirected_by_node(session: Session, rels: Sequence[GpuTable], n_ok: NodeBitmap, position: int,
@@ -356,10 +349,8 @@ def triangle_count_undirected_by_node(session: Session, rels: Sequence[GpuTable]
                                       dst_col: str = "target") -> GpuTable:
     """``MATCH (a)-[r1]-(b)-[r2]-(c)-[r3]-(a) RETURN id(x), count(*)`` with x at a position of class `position`
     (TRI_UND_END a or c, TRI_UND_MIDDLE b): one row per node with a non-zero count, unordered."""
-    out = ctypes.c_void_p()
-    _lib.call("capsmi_triangle_count_undirected_by_node", session.handle, len(rels), _handles(rels), src_col.encode(),
-              dst_col.encode(), n_ok.handle, position, id_name.encode(), count_name.encode(), ctypes.byref(out))
-    return GpuTable(session, out)
+    return _table_of(session, "capsmi_triangle_count_undirected_by_node",
+                     *_tri_args(session, rels, src_col, dst_col, n_ok), position, id_name.encode(), count_name.encode())
 
 
 class RelPartition:

@@ -2200,6 +2200,60 @@ static void rel_cols(int32_t nrels, capsmi_table* const* rels, const char* src_c
     }
 }
 
+// f over a temporary trigraph of the relationships: the first failing status of build and f
+template <class F>
+static capsmi_status over_trigraph(capsmi_session* s, int32_t nrels, capsmi_table* const* rels, const char* src_col,
+                                   const char* dst_col, const capsmi_bitmap* n_ok, F f) {
+    capsmi_trigraph* g = nullptr;
+    capsmi_status st = capsmi_trigraph_build(s, nrels, rels, src_col, dst_col, n_ok, &g);
+    if (st != CAPSMI_OK) return st;
+    st = f(g);
+    capsmi_trigraph_release(g);
+    return st;
+}
+
+// count(*) of the transitive or the undirected triangle over a trigraph
+static capsmi_status trigraph_shape_count(capsmi_session* s, const capsmi_trigraph* g, TriShape shape, int64_t* out_rows) {
+    API_BEGIN
+    need(s, "session");
+    need(g, "trigraph");
+    need(out_rows, "out");
+    use_device(s);
+    *out_rows = (int64_t)tri_shape_count(s, g->g, shape);
+    API_END
+}
+
+// the (id, count) table of a trigraph's per-node counts; cls: the shape's role or position class, bad_cls: what
+// an out-of-range one is refused with (else null)
+static capsmi_status trigraph_by_node(capsmi_session* s, const capsmi_trigraph* g, TriShape shape, int cls,
+                                      const char* bad_cls, const char* id_name, const char* count_name,
+                                      capsmi_table** out) {
+    API_BEGIN
+    need(s, "session");
+    need(g, "trigraph");
+    need(out, "out");
+    need(id_name, "id_name");
+    need(count_name, "count_name");
+    REQUIRE(!bad_cls, CAPSMI_ERR_ILLEGAL_ARGUMENT, bad_cls);
+    REQUIRE(std::string(id_name) != count_name, CAPSMI_ERR_ILLEGAL_ARGUMENT, "output names must differ");
+    use_device(s);
+    Buf ids, cnt;
+    const int64_t rows = tri_shape_count_by_node(s, g->g, shape, cls, ids, cnt);
+    add_i64(P<int64_t>(ids), g->g.lo, rows, s->stream);  // relative ids -> the graph's
+    auto* o = new_table(s, rows);
+    Column a, c;
+    a.name = id_name;
+    a.type = CAPSMI_I64;
+    a.data = ids;
+    c.name = count_name;
+    c.type = CAPSMI_I64;
+    c.data = cnt;
+    o->cols.push_back(std::move(a));
+    o->cols.push_back(std::move(c));
+    *out = o;
+    API_END
+}
+
 extern "C" {
 
 capsmi_status capsmi_trigraph_build(capsmi_session* s, int32_t nrels, capsmi_table* const* rels, const char* src_col,
@@ -2253,176 +2307,78 @@ capsmi_status capsmi_trigraph_release(capsmi_trigraph* g) {
 
 capsmi_status capsmi_triangle_count(capsmi_session* s, int32_t nrels, capsmi_table* const* rels, const char* src_col,
                                     const char* dst_col, const capsmi_bitmap* n_ok, int64_t* out_rows) {
-    capsmi_trigraph* g = nullptr;
-    capsmi_status st = capsmi_trigraph_build(s, nrels, rels, src_col, dst_col, n_ok, &g);
-    if (st != CAPSMI_OK) return st;
-    st = capsmi_trigraph_count(s, g, 0, 1, out_rows);
-    capsmi_trigraph_release(g);
-    return st;
+    return over_trigraph(s, nrels, rels, src_col, dst_col, n_ok,
+                         [&](capsmi_trigraph* g) { return capsmi_trigraph_count(s, g, 0, 1, out_rows); });
 }
 
 capsmi_status capsmi_trigraph_count_by_node(capsmi_session* s, const capsmi_trigraph* g, const char* id_name,
                                             const char* count_name, capsmi_table** out) {
-    API_BEGIN
-    need(s, "session");
-    need(g, "trigraph");
-    need(out, "out");
-    need(id_name, "id_name");
-    need(count_name, "count_name");
-    REQUIRE(std::string(id_name) != count_name, CAPSMI_ERR_ILLEGAL_ARGUMENT, "output names must differ");
-    use_device(s);
-    Buf ids, cnt;
-    const int64_t rows = tri_count_by_node(s, g->g, ids, cnt);
-    add_i64(P<int64_t>(ids), g->g.lo, rows, s->stream);  // relative ids -> the graph's
-    auto* o = new_table(s, rows);
-    Column a, c;
-    a.name = id_name;
-    a.type = CAPSMI_I64;
-    a.data = ids;
-    c.name = count_name;
-    c.type = CAPSMI_I64;
-    c.data = cnt;
-    o->cols.push_back(std::move(a));
-    o->cols.push_back(std::move(c));
-    *out = o;
-    API_END
+    return trigraph_by_node(s, g, TriShape::cycle, 0, nullptr, id_name, count_name, out);
 }
 
 capsmi_status capsmi_triangle_count_by_node(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
                                             const char* src_col, const char* dst_col, const capsmi_bitmap* n_ok,
                                             const char* id_name, const char* count_name, capsmi_table** out) {
-    capsmi_trigraph* g = nullptr;
-    capsmi_status st = capsmi_trigraph_build(s, nrels, rels, src_col, dst_col, n_ok, &g);
-    if (st != CAPSMI_OK) return st;
-    st = capsmi_trigraph_count_by_node(s, g, id_name, count_name, out);
-    capsmi_trigraph_release(g);
-    return st;
+    return over_trigraph(s, nrels, rels, src_col, dst_col, n_ok, [&](capsmi_trigraph* g) {
+        return capsmi_trigraph_count_by_node(s, g, id_name, count_name, out);
+    });
 }
 
 capsmi_status capsmi_trigraph_count_transitive(capsmi_session* s, const capsmi_trigraph* g, int64_t* out_rows) {
-    API_BEGIN
-    need(s, "session");
-    need(g, "trigraph");
-    need(out_rows, "out");
-    use_device(s);
-    *out_rows = (int64_t)tri_trans_count(s, g->g);
-    API_END
+    return trigraph_shape_count(s, g, TriShape::transitive, out_rows);
 }
 
 capsmi_status capsmi_trigraph_count_transitive_by_node(capsmi_session* s, const capsmi_trigraph* g, int32_t role,
                                                        const char* id_name, const char* count_name,
                                                        capsmi_table** out) {
-    API_BEGIN
-    need(s, "session");
-    need(g, "trigraph");
-    need(out, "out");
-    need(id_name, "id_name");
-    need(count_name, "count_name");
-    REQUIRE(role >= CAPSMI_TRI_ROLE_SOURCE && role <= CAPSMI_TRI_ROLE_SINK, CAPSMI_ERR_ILLEGAL_ARGUMENT,
-            "role must be CAPSMI_TRI_ROLE_SOURCE, _MIDDLE or _SINK");
-    REQUIRE(std::string(id_name) != count_name, CAPSMI_ERR_ILLEGAL_ARGUMENT, "output names must differ");
-    use_device(s);
-    Buf ids, cnt;
-    const int64_t rows = tri_trans_count_by_node(s, g->g, role, ids, cnt);
-    add_i64(P<int64_t>(ids), g->g.lo, rows, s->stream);  // relative ids -> the graph's
-    auto* o = new_table(s, rows);
-    Column a, c;
-    a.name = id_name;
-    a.type = CAPSMI_I64;
-    a.data = ids;
-    c.name = count_name;
-    c.type = CAPSMI_I64;
-    c.data = cnt;
-    o->cols.push_back(std::move(a));
-    o->cols.push_back(std::move(c));
-    *out = o;
-    API_END
+    const bool ok = role >= CAPSMI_TRI_ROLE_SOURCE && role <= CAPSMI_TRI_ROLE_SINK;
+    return trigraph_by_node(s, g, TriShape::transitive, role,
+                            ok ? nullptr : "role must be CAPSMI_TRI_ROLE_SOURCE, _MIDDLE or _SINK", id_name, count_name, out);
 }
 
 capsmi_status capsmi_triangle_count_transitive(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
                                                const char* src_col, const char* dst_col, const capsmi_bitmap* n_ok,
                                                int64_t* out_rows) {
-    capsmi_trigraph* g = nullptr;
-    capsmi_status st = capsmi_trigraph_build(s, nrels, rels, src_col, dst_col, n_ok, &g);
-    if (st != CAPSMI_OK) return st;
-    st = capsmi_trigraph_count_transitive(s, g, out_rows);
-    capsmi_trigraph_release(g);
-    return st;
+    return over_trigraph(s, nrels, rels, src_col, dst_col, n_ok,
+                         [&](capsmi_trigraph* g) { return capsmi_trigraph_count_transitive(s, g, out_rows); });
 }
 
 capsmi_status capsmi_triangle_count_transitive_by_node(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
                                                        const char* src_col, const char* dst_col,
                                                        const capsmi_bitmap* n_ok, int32_t role, const char* id_name,
                                                        const char* count_name, capsmi_table** out) {
-    capsmi_trigraph* g = nullptr;
-    capsmi_status st = capsmi_trigraph_build(s, nrels, rels, src_col, dst_col, n_ok, &g);
-    if (st != CAPSMI_OK) return st;
-    st = capsmi_trigraph_count_transitive_by_node(s, g, role, id_name, count_name, out);
-    capsmi_trigraph_release(g);
-    return st;
+    return over_trigraph(s, nrels, rels, src_col, dst_col, n_ok, [&](capsmi_trigraph* g) {
+        return capsmi_trigraph_count_transitive_by_node(s, g, role, id_name, count_name, out);
+    });
 }
 
 capsmi_status capsmi_trigraph_count_undirected(capsmi_session* s, const capsmi_trigraph* g, int64_t* out_rows) {
-    API_BEGIN
-    need(s, "session");
-    need(g, "trigraph");
-    need(out_rows, "out");
-    use_device(s);
-    *out_rows = (int64_t)tri_und_count(s, g->g);
-    API_END
+    return trigraph_shape_count(s, g, TriShape::undirected, out_rows);
 }
 
 capsmi_status capsmi_trigraph_count_undirected_by_node(capsmi_session* s, const capsmi_trigraph* g, int32_t position,
                                                        const char* id_name, const char* count_name,
                                                        capsmi_table** out) {
-    API_BEGIN
-    need(s, "session");
-    need(g, "trigraph");
-    need(out, "out");
-    need(id_name, "id_name");
-    need(count_name, "count_name");
-    REQUIRE(position == CAPSMI_TRI_UND_END || position == CAPSMI_TRI_UND_MIDDLE, CAPSMI_ERR_ILLEGAL_ARGUMENT,
-            "position must be CAPSMI_TRI_UND_END or CAPSMI_TRI_UND_MIDDLE");
-    REQUIRE(std::string(id_name) != count_name, CAPSMI_ERR_ILLEGAL_ARGUMENT, "output names must differ");
-    use_device(s);
-    Buf ids, cnt;
-    const int64_t rows = tri_und_count_by_node(s, g->g, position, ids, cnt);
-    add_i64(P<int64_t>(ids), g->g.lo, rows, s->stream);  // relative ids -> the graph's
-    auto* o = new_table(s, rows);
-    Column a, c;
-    a.name = id_name;
-    a.type = CAPSMI_I64;
-    a.data = ids;
-    c.name = count_name;
-    c.type = CAPSMI_I64;
-    c.data = cnt;
-    o->cols.push_back(std::move(a));
-    o->cols.push_back(std::move(c));
-    *out = o;
-    API_END
+    const bool ok = position == CAPSMI_TRI_UND_END || position == CAPSMI_TRI_UND_MIDDLE;
+    return trigraph_by_node(s, g, TriShape::undirected, position,
+                            ok ? nullptr : "position must be CAPSMI_TRI_UND_END or CAPSMI_TRI_UND_MIDDLE", id_name,
+                            count_name, out);
 }
 
 capsmi_status capsmi_triangle_count_undirected(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
                                                const char* src_col, const char* dst_col, const capsmi_bitmap* n_ok,
                                                int64_t* out_rows) {
-    capsmi_trigraph* g = nullptr;
-    capsmi_status st = capsmi_trigraph_build(s, nrels, rels, src_col, dst_col, n_ok, &g);
-    if (st != CAPSMI_OK) return st;
-    st = capsmi_trigraph_count_undirected(s, g, out_rows);
-    capsmi_trigraph_release(g);
-    return st;
+    return over_trigraph(s, nrels, rels, src_col, dst_col, n_ok,
+                         [&](capsmi_trigraph* g) { return capsmi_trigraph_count_undirected(s, g, out_rows); });
 }
 
 capsmi_status capsmi_triangle_count_undirected_by_node(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
                                                        const char* src_col, const char* dst_col,
                                                        const capsmi_bitmap* n_ok, int32_t position, const char* id_name,
                                                        const char* count_name, capsmi_table** out) {
-    capsmi_trigraph* g = nullptr;
-    capsmi_status st = capsmi_trigraph_build(s, nrels, rels, src_col, dst_col, n_ok, &g);
-    if (st != CAPSMI_OK) return st;
-    st = capsmi_trigraph_count_undirected_by_node(s, g, position, id_name, count_name, out);
-    capsmi_trigraph_release(g);
-    return st;
+    return over_trigraph(s, nrels, rels, src_col, dst_col, n_ok, [&](capsmi_trigraph* g) {
+        return capsmi_trigraph_count_undirected_by_node(s, g, position, id_name, count_name, out);
+    });
 }
 
 capsmi_status capsmi_relpart_size(const capsmi_relpart* p, int64_t* kept_rows) {

@@ -646,19 +646,17 @@ struct TriDist {
 void tri_build(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms, int nt,
                const capsmi_bitmap* n_ok, TriGraph& g, const TriDist* dd = nullptr);
 uint64_t tri_count(capsmi_session* s, const TriGraph& g, int part, int nparts);
-// the count grouped by the start node (k_tri_grouped.hip): rows (relative id, count) of the nodes with a
-// non-zero count over a single-device trigraph, unordered; returns their number
-int64_t tri_count_by_node(capsmi_session* s, const TriGraph& g, Buf& ids, Buf& counts);
-// the transitive triangle (a)->(b)->(c)<-(a) over a single-device trigraph (k_tri_trans.hip): count(*), and the
-// rows (relative id, count) of the nodes with a non-zero count in `role` (CAPSMI_TRI_ROLE_*), unordered
-uint64_t tri_trans_count(capsmi_session* s, const TriGraph& g);
-int64_t tri_trans_count_by_node(capsmi_session* s, const TriGraph& g, int role, Buf& ids, Buf& counts);
-// the undirected triangle (a)-(b)-(c)-(a) over a single-device trigraph (k_tri_und.hip): count(*) in the form
-// cfg.tri_und_hash selects, and the rows (relative id, count) of the nodes with a non-zero count at a position of
-// class `position` (CAPSMI_TRI_UND_*), unordered.  tri_und_hash_walk (k_tri.hip): the count's hash walks, which
-// add sum U U U over the simple triangles to the device word *out
-uint64_t tri_und_count(capsmi_session* s, const TriGraph& g);
-int64_t tri_und_count_by_node(capsmi_session* s, const TriGraph& g, int position, Buf& ids, Buf& counts);
+// the closed triangle's shapes over a single-device trigraph (k_tri_nodes.hip): the cycle (a)->(b)->(c)->(a), the
+// transitive triangle (a)->(b)->(c)<-(a) and the undirected one (a)-(b)-(c)-(a)
+enum class TriShape { cycle, transitive, undirected };
+// count(*) of the transitive or the undirected triangle (the latter in the form cfg.tri_und_hash selects; the
+// cycle's is tri_count)
+uint64_t tri_shape_count(capsmi_session* s, const TriGraph& g, TriShape shape);
+// the count grouped by one node: rows (relative id, count) of the nodes with a non-zero count, unordered; returns
+// their number.  cls: the transitive triangle's role (CAPSMI_TRI_ROLE_*), the undirected one's position class
+// (CAPSMI_TRI_UND_*); the cycle takes none (the same rows at every position)
+int64_t tri_shape_count_by_node(capsmi_session* s, const TriGraph& g, TriShape shape, int cls, Buf& ids, Buf& counts);
+// the undirected count's hash walks (k_tri.hip), which add sum U U U over the simple triangles to the device word *out
 void tri_und_hash_walk(capsmi_session* s, const TriGraph& g, unsigned long long* out);
 
 // undirected Expand patterns (k_undirected.hip): hops 1 or 2; kind 0 count(*), 1 count(DISTINCT end),

@@ -2462,7 +2462,7 @@ uint64_t tri_count(capsmi_session* s, const TriGraph& g, int part, int nparts) {
     return 3 * h[0] + h[1] + h[2];
 }
 
-// The undirected triangle's hash walks (k_tri_und.hip): adds sum U(u,v) U(v,w) U(u,w) over the simple triangles
+// The undirected triangle's hash walks (k_tri_nodes.hip): adds sum U(u,v) U(v,w) U(u,w) over the simple triangles
 // to *out.  The u-mode walks over the combined out-lists with vmt = 0 -- every edge from its u, no v-mode: a
 // split build keeps no combined in-lists, and the base lists are whole on either build.
 void tri_und_hash_walk(capsmi_session* s, const TriGraph& g, unsigned long long* out) {

@@ -982,6 +982,42 @@ bool all_pairs_unique(const Classified& c, int nh) {
     return (int)c.uniq.size() == nh * (nh - 1) / 2;
 }
 
+// What the triangle routes ask of their nb branches: one relationship set for every hop, read as (start, end),
+// and one node filter for every position.  Fills v0 with the set's views and returns the filter's bitmap; null
+// says "not this route" (a bitmap with an id in two scanned rows comes back null too: node_bitmap).
+capsmi_bitmap* one_set_one_filter(capsmi_session* s, const Path* B, const Classified* cls, size_t nb, int64_t lo,
+                                  int64_t hi, BitmapSet& bs, RelViews& v0) {
+    rel_views(B[0], directed(B[0].hops[0]), v0);
+    for (size_t bi = 0; bi < nb; ++bi)
+        for (const Hop& hp : B[bi].hops) {
+            RelViews v;
+            rel_views(B[bi], directed(hp), v);
+            if (v.sig != v0.sig) return nullptr;
+        }
+    std::string k0;
+    capsmi_bitmap* a = node_bitmap(s, B[0], cls[0], B[0].pos_node[0], lo, hi, bs, &k0);
+    if (!a) return nullptr;
+    for (size_t bi = 0; bi < nb; ++bi)
+        for (int x : B[bi].pos_node) {
+            std::string kx;
+            if (!node_bitmap(s, B[bi], cls[bi], x, lo, hi, bs, &kx) || kx != k0) return nullptr;
+        }
+    return a;
+}
+
+// the (s, t) columns of relationship views, as the kernels' entry points take them
+struct RelCols {
+    std::vector<const int64_t*> srcs, dsts;
+    std::vector<int64_t> ms;
+    explicit RelCols(const std::vector<capsmi_table*>& views) {
+        for (capsmi_table* t : views) {
+            srcs.push_back(t->cols[0].d());
+            dsts.push_back(t->cols[1].d());
+            ms.push_back(t->nrows);
+        }
+    }
+};
+
 void route(capsmi_session* s, const char* name) { s->routes[name] += 1; }
 
 bool any_no_loops(const Path& P) {  // an undirected branch: only fused_undirected takes it
@@ -1189,19 +1225,13 @@ int64_t dist_two_hop_count_owned(capsmi_session* s, const Path& P, const RelView
 // build (k_tri.hip tri_build: pairs exchanged to their lower end's owner, oriented ranges exchanged and
 // all-gathered), this rank's work share of the centers, one all-reduce of the parts
 int64_t dist_triangle_count(capsmi_session* s, const std::vector<capsmi_table*>& views, const capsmi_bitmap* n_ok) {
-    std::vector<const int64_t*> srcs, dsts;
-    std::vector<int64_t> ms;
-    for (capsmi_table* t : views) {
-        srcs.push_back(t->cols[0].d());
-        dsts.push_back(t->cols[1].d());
-        ms.push_back(t->nrows);
-    }
+    const RelCols rc(views);
     TriDist dd;
     dd.rank = g_dist.rank;
     dd.world = g_dist.world;
     dd.span = 32 * g_dist.slice_words;
     TriGraph g;
-    tri_build(s, srcs.data(), dsts.data(), ms.data(), (int)srcs.size(), n_ok, g, &dd);
+    tri_build(s, rc.srcs.data(), rc.dsts.data(), rc.ms.data(), (int)rc.ms.size(), n_ok, g, &dd);
     const uint64_t part = tri_count(s, g, g_dist.rank, g_dist.world);
     return sum_over_ranks(s, (int64_t)part);
 }
@@ -1305,17 +1335,11 @@ bool fused_counts(capsmi_session* s, const Path& P, const std::vector<int>& kind
     int tri_role[3];
     if (const int shape = closed_triangle(P, tri_role)) {
         // P0 - P1 - P2 - P0 (the closing hop is the ExpandInto), every hop read along its relationships
-        RelViews d0, v1, v2;
-        rel_views(P, directed(P.hops[0]), d0);
-        rel_views(P, directed(P.hops[1]), v1);
-        rel_views(P, directed(P.hops[2]), v2);
-        if (v1.sig != d0.sig || v2.sig != d0.sig || !all_pairs_unique(c, 3)) return false;
+        if (!all_pairs_unique(c, 3)) return false;
         for (int k : kinds) if (k != A_COUNT) return false;
-        std::string k0, k1, k2;
-        capsmi_bitmap* a = node_bitmap(s, P, c, P.pos_node[0], lo, hi, bs, &k0);
-        capsmi_bitmap* b = node_bitmap(s, P, c, P.pos_node[1], lo, hi, bs, &k1);
-        capsmi_bitmap* cc = node_bitmap(s, P, c, P.pos_node[2], lo, hi, bs, &k2);
-        if (!a || !b || !cc || k0 != k1 || k1 != k2) return false;  // one node filter for all three
+        RelViews d0;
+        capsmi_bitmap* a = one_set_one_filter(s, &P, &c, 1, lo, hi, bs, d0);
+        if (!a) return false;
         // the distributed build codes oriented targets in 24 bits: larger domains take the generic plan
         if (g_dist.on && (bits_for_ids(hi - lo) + 7) / 8 * 8 > 24) return false;
         int64_t x = 0;
@@ -1551,12 +1575,35 @@ bool fused_grouped_two_hop(capsmi_session* s, const capsmi_table* in, const Plan
     return true;
 }
 
+// The grouped triangle routes' tail: the trigraph of the views, its per-node rows (relative ids back to the graph's
+// Long ids) and the result table: the key and one count column per aggregate (every aggregate is the same count).
+capsmi_table* tri_grouped_rows(capsmi_session* s, const RelViews& v, const capsmi_bitmap* n_ok, TriShape shape, int cls,
+                               int64_t lo, size_t naggs) {
+    const RelCols rc(v.t);
+    Buf ids, cnt;
+    int64_t rows = 0;
+    {
+        TriGraph tg;
+        tri_build(s, rc.srcs.data(), rc.dsts.data(), rc.ms.data(), (int)rc.ms.size(), n_ok, tg);
+        rows = tri_shape_count_by_node(s, tg, shape, cls, ids, cnt);
+    }
+    ids_to_long(s, lo, ::capsmi::P<int64_t>(ids), rows);
+    std::unique_ptr<capsmi_table> r(result_table(s, rows));
+    Column k;
+    k.type = CAPSMI_I64;
+    k.data = ids;
+    r->cols.push_back(k);
+    k.data = cnt;
+    r->cols.insert(r->cols.end(), naggs, k);
+    return r.release();
+}
+
 // C4's grouped form: the closed triangle grouped by one of its nodes, count(*).  The preconditions of the
 // triangle in fused_counts (three hops closing on position 0, one relationship set, pairwise-unique
 // relationships, one node filter for all three positions) make the pattern symmetric under rotation, so the
-// counts grouped by position 1 or 2 are the counts grouped by position 0 (k_tri_grouped.hip).  Single device.
+// counts grouped by position 1 or 2 are the counts grouped by position 0 (k_tri_nodes.hip).  Single device.
 // The same closed path with mixed directions is the transitive triangle (closed_triangle): the key's position
-// has a role -- source, middle or sink -- and the rows are that role's counts (k_tri_trans.hip,
+// has a role -- source, middle or sink -- and the rows are that role's counts (k_tri_nodes.hip,
 // "triangle_transitive_grouped").
 bool fused_grouped_triangle(capsmi_session* s, const capsmi_table* in, const PlanNode& g, const std::vector<Path>& B,
                             capsmi_table** out) {
@@ -1568,7 +1615,6 @@ bool fused_grouped_triangle(capsmi_session* s, const capsmi_table* in, const Pla
     int role[3];
     const int shape = closed_triangle(P, role);
     if (shape == TRI_NONE) return false;
-    const Hop h0 = directed(P.hops[0]), h1 = directed(P.hops[1]), h2 = directed(P.hops[2]);
     const int gc = find_col(in, g.a[0]);
     if (gc < 0 || !id_like(P, P.cols[gc])) return false;
     const int gp = position_of(P, P.cols[gc]);
@@ -1579,46 +1625,13 @@ bool fused_grouped_triangle(capsmi_session* s, const capsmi_table* in, const Pla
     std::vector<Path> one{P};
     int64_t lo, hi;
     if (!id_window(one, &lo, &hi) || g_dist.on) return false;  // (sets the id domain the views below read)
-    RelViews v0, v1, v2;
-    rel_views(P, h0, v0);
-    rel_views(P, h1, v1);
-    rel_views(P, h2, v2);
-    if (v1.sig != v0.sig || v2.sig != v0.sig || !all_pairs_unique(c, 3)) return false;
+    if (!all_pairs_unique(c, 3)) return false;
     BitmapSet bs;
-    std::string k0, k1, k2;
-    capsmi_bitmap* a = node_bitmap(s, P, c, P.pos_node[0], lo, hi, bs, &k0);
-    capsmi_bitmap* b = node_bitmap(s, P, c, P.pos_node[1], lo, hi, bs, &k1);
-    capsmi_bitmap* cc = node_bitmap(s, P, c, P.pos_node[2], lo, hi, bs, &k2);
-    // one node filter for all three (a bitmap with an id in two scanned rows comes back null: node_bitmap)
-    if (!a || !b || !cc || k0 != k1 || k1 != k2) return false;
-    std::vector<const int64_t*> srcs, dsts;
-    std::vector<int64_t> ms;
-    for (capsmi_table* t : v0.t) {
-        srcs.push_back(t->cols[0].d());
-        dsts.push_back(t->cols[1].d());
-        ms.push_back(t->nrows);
-    }
-    Buf ids, cnt;
-    int64_t rows = 0;
-    {
-        TriGraph tg;
-        tri_build(s, srcs.data(), dsts.data(), ms.data(), (int)srcs.size(), a, tg);
-        rows = shape == TRI_CYCLE ? tri_count_by_node(s, tg, ids, cnt) : tri_trans_count_by_node(s, tg, role[gp], ids, cnt);
-    }
-    ids_to_long(s, lo, ::capsmi::P<int64_t>(ids), rows);
-    auto* r = result_table(s, rows);
-    std::unique_ptr<capsmi_table> guard(r);
-    Column k;
-    k.type = CAPSMI_I64;
-    k.data = ids;
-    r->cols.push_back(std::move(k));
-    for (size_t i = 0; i < kinds.size(); ++i) {  // every aggregate is the same count
-        Column v;
-        v.type = CAPSMI_I64;
-        v.data = cnt;
-        r->cols.push_back(std::move(v));
-    }
-    *out = guard.release();
+    RelViews v0;
+    capsmi_bitmap* a = one_set_one_filter(s, &P, &c, 1, lo, hi, bs, v0);
+    if (!a) return false;
+    if (shape == TRI_CYCLE) *out = tri_grouped_rows(s, v0, a, TriShape::cycle, 0, lo, kinds.size());
+    else *out = tri_grouped_rows(s, v0, a, TriShape::transitive, role[gp], lo, kinds.size());
     route(s, shape == TRI_CYCLE ? "triangle_grouped" : "triangle_transitive_grouped");
     return true;
 }
@@ -1630,7 +1643,7 @@ bool fused_grouped_triangle(capsmi_session* s, const capsmi_table* in, const Pla
 // end) by every hop of every branch, pairwise-unique relationships, one node filter for all positions and
 // branches, count(*) aggregates only.  Without keys: the count ("triangle_undirected"); with one key, the id of
 // the same position p in every branch: the rows of p's class -- the ends of the ExpandInto (p = 0, 2) or the
-// middle (p = 1) -- ("triangle_undirected_grouped", k_tri_und.hip).  Single device.
+// middle (p = 1) -- ("triangle_undirected_grouped", k_tri_nodes.hip).  Single device.
 bool fused_undirected_triangle(capsmi_session* s, const capsmi_table* in, const PlanNode& g, const std::vector<Path>& B,
                                capsmi_table** out) {
     if (B.size() != 8 || g.a.size() > 1 || g.aggs.empty()) return false;
@@ -1668,31 +1681,12 @@ bool fused_undirected_triangle(capsmi_session* s, const capsmi_table* in, const 
     if (orients.size() != B.size()) return false;
     int64_t lo, hi;
     if (!id_window(B, &lo, &hi) || g_dist.on) return false;
-    // one relationship set for every hop of every branch, read as (start, end)
-    auto plain_views = [&](const Path& P, const Hop& hp, RelViews& v) {
-        Hop fwd = hp;
-        fwd.from_role = ROLE_SRC;
-        fwd.to_role = ROLE_DST;
-        rel_views(P, fwd, v);
-    };
-    RelViews v0;
-    plain_views(B[0], B[0].hops[0], v0);
-    for (const Path& P : B)
-        for (const Hop& hp : P.hops) {
-            RelViews v;
-            plain_views(P, hp, v);
-            if (v.sig != v0.sig) return false;
-        }
-    // one node filter for all three positions of every branch
+    // one relationship set for every hop of every branch, read as (start, end), and one node filter for all three
+    // positions of every branch
     BitmapSet bs;
-    std::string k0;
-    capsmi_bitmap* a = node_bitmap(s, B[0], cls[0], B[0].pos_node[0], lo, hi, bs, &k0);
+    RelViews v0;
+    capsmi_bitmap* a = one_set_one_filter(s, B.data(), cls.data(), B.size(), lo, hi, bs, v0);
     if (!a) return false;
-    for (size_t bi = 0; bi < B.size(); ++bi)
-        for (int q = 0; q < 3; ++q) {
-            std::string kq;
-            if (!node_bitmap(s, B[bi], cls[bi], B[bi].pos_node[q], lo, hi, bs, &kq) || kq != k0) return false;
-        }
     const int nt = (int)v0.t.size();
     if (nt <= 0) return false;
     if (g.a.empty()) {
@@ -1708,34 +1702,8 @@ bool fused_undirected_triangle(capsmi_session* s, const capsmi_table* in, const 
         route(s, "triangle_undirected");
         return true;
     }
-    std::vector<const int64_t*> srcs, dsts;
-    std::vector<int64_t> ms;
-    for (capsmi_table* t : v0.t) {
-        srcs.push_back(t->cols[0].d());
-        dsts.push_back(t->cols[1].d());
-        ms.push_back(t->nrows);
-    }
-    Buf ids, cnt;
-    int64_t rows = 0;
-    {
-        TriGraph tg;
-        tri_build(s, srcs.data(), dsts.data(), ms.data(), (int)srcs.size(), a, tg);
-        rows = tri_und_count_by_node(s, tg, gp == 1 ? CAPSMI_TRI_UND_MIDDLE : CAPSMI_TRI_UND_END, ids, cnt);
-    }
-    ids_to_long(s, lo, ::capsmi::P<int64_t>(ids), rows);
-    auto* r = result_table(s, rows);
-    std::unique_ptr<capsmi_table> guard(r);
-    Column k;
-    k.type = CAPSMI_I64;
-    k.data = ids;
-    r->cols.push_back(std::move(k));
-    for (size_t i = 0; i < kinds.size(); ++i) {  // every aggregate is the same count
-        Column v;
-        v.type = CAPSMI_I64;
-        v.data = cnt;
-        r->cols.push_back(std::move(v));
-    }
-    *out = guard.release();
+    *out = tri_grouped_rows(s, v0, a, TriShape::undirected, gp == 1 ? CAPSMI_TRI_UND_MIDDLE : CAPSMI_TRI_UND_END, lo,
+                            kinds.size());
     route(s, "triangle_undirected_grouped");
     return true;
 }

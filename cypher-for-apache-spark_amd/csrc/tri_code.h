@@ -1,5 +1,5 @@
 // tri_code.h -- the coded oriented targets of a TriGraph and a triangle's weight, shared by the triangle
-// count (k_tri.hip) and its per-node form (k_tri_grouped.hip).
+// count (k_tri.hip) and its per-node form (k_tri_nodes.hip).
 #pragma once
 
 #include "capsmi_impl.h"
@@ -39,7 +39,7 @@ __device__ __forceinline__ unsigned long long tri_weight(uint64_t puv, uint64_t 
 
 // The weight of a hit as a template parameter of the combined list walks (k_tri_small, k_tri_big_items):
 // the directed cycle's, and the undirected triangle's U(u,v) U(v,w) U(u,w) with U = f + b of a payload
-// (k_tri_und.hip).  The latter is symmetric in the three pairs, the order of the arguments does not matter.
+// (k_tri_nodes.hip).  The latter is symmetric in the three pairs, the order of the arguments does not matter.
 struct CycleWeight {
     static __device__ __forceinline__ unsigned long long of(uint64_t puv, uint64_t pvw, uint64_t puw) {
         return tri_weight(puv, pvw, puw);

@@ -1,4 +1,4 @@
-"""Transitive triangle timing: the walks of csrc/k_tri_trans.hip -- TriGraph.count_transitive_by_node for the
+"""Transitive triangle timing: the walks of csrc/k_tri_nodes.hip -- TriGraph.count_transitive_by_node for the
 source, the middle and the sink, and TriGraph.count_transitive -- against the cyclic grouped walk
 (TriGraph.count_by_node, the yardstick: the same slots with one weight and symmetric adds), on the C4 graph of
 bench.py -- R-MAT with seed parameters (57, 19, 19), edge factor 16, every node scanned -- over one trigraph handle,

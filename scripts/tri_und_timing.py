@@ -1,4 +1,4 @@
-"""Undirected triangle timing: the forms of csrc/k_tri_und.hip -- TriGraph.count_undirected by the hash walks
+"""Undirected triangle timing: the forms of csrc/k_tri_nodes.hip -- TriGraph.count_undirected by the hash walks
 (CAPSMI_TRI_UND_COUNT=hash) and by the search walk (=walk), and TriGraph.count_undirected_by_node for the END and the
 MIDDLE class -- on the C4 graph of bench.py (R-MAT with seed parameters (57, 19, 19), edge factor 16, every node
 scanned) over one trigraph handle, alternating in one process, from the library's own kernel timers

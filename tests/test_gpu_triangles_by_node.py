@@ -1,10 +1,11 @@
-"""The cyclic triangle grouped by its start (csrc/k_tri_grouped.hip, route "triangle_grouped"):
+"""The cyclic triangle grouped by its start (csrc/k_tri_nodes.hip, route "triangle_grouped"):
   MATCH (a)-[r1]->(b)-[r2]->(c)-[r3]->(a) RETURN id(a), count(*)
 through the direct entry points on both trigraph builds and through the planner, against the plain restatements
 of tests/tri_grouped_ref.py (pinned against the C enumeration in tests/test_tri_grouped_ref_cpu.py).  Every row
 is compared, with its id; counts are integers and must match exactly."""
 import ctypes
 import functools
+import itertools
 
 import numpy as np
 import pytest
@@ -57,6 +58,69 @@ def test_random_multigraphs(session, knobs, seed, build):
     want = tg.per_node_enumerate(n, src, dst)
     assert want.tolist() == tg.per_node_dense(n, src, dst).tolist()
     assert same_rows(_by_node(session, n, src, dst, handle=seed % 2 == 1), tg.rows_of(want))
+
+
+# ---- one triangle, six different multiplicities, every degree order ----------------------------------------------
+
+def _cycle_weight(puv, pvw, puw):
+    """tri_weight (csrc/tri_code.h) of the payloads (f, b) of u -> v, v -> w, u -> w"""
+    return puv[0] * pvw[0] * puw[1] + puw[0] * pvw[1] * puv[1]
+
+
+@pytest.mark.parametrize("build", BUILDS)
+@pytest.mark.parametrize("pend", list(itertools.permutations((1, 2, 3))))
+def test_prime_triangle_under_every_degree_order(session, knobs, pend, build):
+    """The walk hands tri_weight the payloads of u -> v, v -> w and u -> w (u > v > w as degree-order ids), the
+    latter two in an order that depends on which list it walked.  Every corner's weight is 2*5*13 + 11*7*3 = 361;
+    with u -> w exchanged for u -> v or for v -> w, or the halves of any one payload flipped, it is 347, 349 or 383
+    under each of the six orders.  (Exchanging u -> v with v -> w leaves the cyclic weight as it is: that one
+    cannot show here; the transitive test catches it.)"""
+    _build(knobs, session, build)
+    n, src, dst = tg.prime_triangle(pend)
+    rid = tg.degree_order(n, src, dst)
+    w, v, u = sorted(range(3), key=lambda x: rid[x])
+    pay = {(x, y): (tg.PRIMES[x, y], tg.PRIMES[y, x]) for x, y in tg.PRIMES}
+    puv, pvw, puw = pay[u, v], pay[v, w], pay[u, w]
+    assert _cycle_weight(puv, pvw, puw) == 361
+    wrong = [_cycle_weight(puw, pvw, puv), _cycle_weight(puv, puw, pvw), _cycle_weight(puv[::-1], pvw, puw),
+             _cycle_weight(puv, pvw[::-1], puw), _cycle_weight(puv, pvw, puw[::-1])]
+    assert set(wrong) <= {347, 349, 383}
+    want = tg.per_node_enumerate(n, src, dst)
+    assert want.tolist() == tg.per_node_dense(n, src, dst).tolist() and want[3:].sum() == 0
+    assert same_rows(_by_node(session, n, src, dst), tg.rows_of(want))
+
+
+# ---- pair and self terms -----------------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("build", BUILDS)
+def test_one_directional_pairs_beside_loops(session, knobs, build):
+    """the graph of tests/test_gpu_triangles_transitive.py: 0 has two loops, 3 one; 0 -> 1 twice, 2 -> 0 three
+    times, 1 -> 3 three times, 3 -> 4 twice, 5 -> 0 once: pairs in one direction beside a loop, which have no term
+    in the cycle (the pair pass leaves them on their coded word), and 4 <-> 5 without a loop: no row at all.  With
+    1 -> 0 added, {0, 1} is reciprocated beside the loops of 0 and alone contributes: 2 * 1 * (2 * 2 + 0) to 0 and
+    2 * 1 * (0 + 2) to 1."""
+    _build(knobs, session, build)
+    src = np.array([0, 0, 3, 0, 0, 2, 2, 2, 1, 1, 1, 3, 3, 4, 5, 5], dtype=np.int64)
+    dst = np.array([0, 0, 3, 1, 1, 0, 0, 0, 3, 3, 3, 4, 4, 5, 4, 0], dtype=np.int64)
+    want = tg.per_node_enumerate(6, src, dst)
+    assert want.tolist() == tg.per_node_dense(6, src, dst).tolist() == [0] * 6
+    assert _by_node(session, 6, src, dst) == []
+    assert _by_node(session, 6, src, dst, handle=True) == []
+    src, dst = np.append(src, 1), np.append(dst, 0)
+    want = tg.per_node_enumerate(6, src, dst)
+    assert want.tolist() == tg.per_node_dense(6, src, dst).tolist() == [8, 4, 0, 0, 0, 0]
+    assert same_rows(_by_node(session, 6, src, dst), tg.rows_of(want))
+    assert same_rows(_by_node(session, 6, src, dst, handle=True), tg.rows_of(want))
+
+
+@pytest.mark.parametrize("build", BUILDS)
+def test_loops_only(session, knobs, build):
+    """s = 0, 1, 2, 3, 4 self-loops and nothing else: s (s - 1) (s - 2)"""
+    _build(knobs, session, build)
+    v = np.repeat(np.arange(5, dtype=np.int64), np.arange(5))
+    want = tg.per_node_enumerate(5, v, v)
+    assert want.tolist() == tg.per_node_dense(5, v, v).tolist() == [0, 0, 0, 6, 24]
+    assert same_rows(_by_node(session, 5, v, v), tg.rows_of(want))
 
 
 @pytest.mark.parametrize("build", BUILDS)

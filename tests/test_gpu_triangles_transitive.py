@@ -1,4 +1,4 @@
-"""The transitive triangle (csrc/k_tri_trans.hip, routes "triangle_transitive" and "triangle_transitive_grouped"):
+"""The transitive triangle (csrc/k_tri_nodes.hip, routes "triangle_transitive" and "triangle_transitive_grouped"):
   MATCH (a)-[r1]->(b)-[r2]->(c)<-[r3]-(a) RETURN count(*)
   MATCH (a)-[r1]->(b)-[r2]->(c)<-[r3]-(a) RETURN id(a), count(*)     (or id(b), or id(c))
 through the direct entry points on both trigraph builds and through the planner, against the enumeration and the
@@ -77,33 +77,13 @@ def test_random_multigraphs(session, knobs, seed, build):
 
 # ---- one triangle, six different multiplicities, every degree order ----------------------------------------------
 
-PRIMES = {(0, 1): 2, (1, 0): 3, (1, 2): 5, (2, 1): 7, (0, 2): 11, (2, 0): 13}
-PRIME_LOOPS = (1, 2, 4)   # self-loops at the corners 0, 1, 2
-PENDANT_UNIT = 40         # see _prime_triangle
+PRIMES = tt.PRIMES
 
 
 @functools.lru_cache(maxsize=None)
 def _prime_triangle(pendants):
-    """The triangle {0, 1, 2} with m(0,1), m(1,0), m(1,2), m(2,1), m(0,2), m(2,0) = 2, 3, 5, 7, 11, 13 and 1, 2, 4
-    self-loops, and pendants[i] bundles of pendant relationships at corner i.  A corner's degree counts its
-    relationships with their multiplicities (29, 17 and 36 here), so single pendant relationships would leave the
-    degree order where the primes put it: a bundle is PENDANT_UNIT relationships, each to a leaf of its own and
-    pointing out of or into the corner in turn, which outweighs the triangle's own spread of 19."""
-    src, dst = [], []
-    for (x, y), m in PRIMES.items():
-        src += [x] * m
-        dst += [y] * m
-    for x, s in enumerate(PRIME_LOOPS):
-        src += [x] * s
-        dst += [x] * s
-    n = 3
-    for x, k in enumerate(pendants):
-        for j in range(k * PENDANT_UNIT):
-            a, b = (x, n) if j % 2 else (n, x)
-            src.append(a), dst.append(b)
-            n += 1
-    perm = np.random.default_rng(501).permutation(len(src))
-    src, dst = np.array(src, dtype=np.int64)[perm], np.array(dst, dtype=np.int64)[perm]
+    """the prime triangle of tests/tri_grouped_ref.py with its expected 3 x n counts"""
+    n, src, dst = tt.prime_triangle(pendants)
     return n, src, dst, tt.per_node_enumerate_all(n, src, dst)
 
 

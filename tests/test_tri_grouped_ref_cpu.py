@@ -1,6 +1,8 @@
 """The two restatements of the per-node triangle counts (tests/tri_grouped_ref.py) against each other and
 against the C enumeration of the whole count (oracle/rmat.c), on random multigraphs with self-loops; the
 rotation symmetry that lets the planner route a grouping by b or by c; and the hand-built graphs' own claims."""
+import itertools
+
 import numpy as np
 import pytest
 
@@ -45,6 +47,21 @@ def test_heavy_triangle_counts():
     want = tg.heavy_triangle_counts()
     assert tg.per_node_dense(n, src, dst).tolist() == want.tolist()
     assert want.min() > 2 ** 32
+
+
+def test_prime_triangle_reaches_every_degree_order():
+    """the shared builder's six pendant permutations put the corners into six different degree orders, above
+    every leaf; the triangle's own part of every corner's cyclic count is 2*5*13 + 11*7*3"""
+    orders = set()
+    for pend in itertools.permutations((1, 2, 3)):
+        n, src, dst = tg.prime_triangle(pend)
+        assert n == 3 + 6 * tg.PENDANT_UNIT
+        rid = tg.degree_order(n, src, dst)
+        assert sorted(rid[:3].tolist()) == [0, 1, 2]  # the corners outrank every leaf
+        orders.add(tuple(rid[:3].tolist()))
+        nl = src != dst
+        assert tg.per_node_dense(n, src[nl], dst[nl])[:3].tolist() == [361] * 3
+    assert len(orders) == 6
 
 
 def test_built_graphs_sit_on_the_edges():

@@ -1,4 +1,4 @@
-"""Shared by the tests of the grouped cyclic triangle (csrc/k_tri_grouped.hip, route "triangle_grouped"):
+"""Shared by the tests of the grouped cyclic triangle (csrc/k_tri_nodes.hip, route "triangle_grouped"):
   MATCH (a)-[r1]->(b)-[r2]->(c)-[r3]->(a) RETURN id(a), count(*)     (r1, r2, r3 pairwise distinct)
 Two plain restatements of the per-node counts that share nothing with the device kernels, mirrors of the
 kernel's constants, and the hand-built graphs that sit on its edges.
@@ -13,7 +13,7 @@ import functools
 
 import numpy as np
 
-# csrc/k_tri_grouped.hip kByNodeWin: the degree-order ids [0, BY_NODE_WIN) are counted in the workgroup's LDS window
+# csrc/k_tri_nodes.hip kByNodeWin: the degree-order ids [0, BY_NODE_WIN) are counted in the workgroup's LDS window
 BY_NODE_WIN = 64
 # csrc/capsmi_impl.h kExplodeTile: slots (oriented edge, position in the walked list) per tile of the walk
 TILE_SLOTS = 2048
@@ -80,17 +80,25 @@ def rows_of(cnt, ids=None):
 
 # ---- a mirror of the walk's slots ---------------------------------------------------------------------------
 
-def walk_slots(n, src, dst):
-    """The slots of k_tbn_walk on the graph: vertices ranked by (relationship count without loops, id), the
-    highest first (exact degrees: every graph here has fewer than 2^22 relationships), each pair oriented from
-    its lower-ranked end, out-lists sorted by rank; the edge u -> v at position p of out(u) owns
-    min(od(v), p) slots.  Returns the slots per oriented edge in (u, position) order."""
+def degree_order(n, src, dst):
+    """degree-order id of every node, as tri_build ranks them: by (relationship count without loops, id), the
+    highest first (exact degrees: every graph here has fewer than 2^22 relationships)"""
     src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
     nl = src != dst
     deg = np.bincount(src[nl], minlength=n) + np.bincount(dst[nl], minlength=n)
     order = np.lexsort((np.arange(n), deg))      # ascending (degree, id)
     rid = np.empty(n, dtype=np.int64)
     rid[order] = n - 1 - np.arange(n)            # degree-order id: 0 = the highest (degree, id)
+    return rid
+
+
+def walk_slots(n, src, dst):
+    """The slots of k_tri_walk on the graph: vertices in degree order, each pair oriented from its lower-ranked
+    end, out-lists sorted by rank; the edge u -> v at position p of out(u) owns min(od(v), p) slots.  Returns the
+    slots per oriented edge in (u, position) order."""
+    src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
+    nl = src != dst
+    rid = degree_order(n, src, dst)
     a, b = rid[src[nl]], rid[dst[nl]]
     pairs = np.unique(np.stack([np.maximum(a, b), np.minimum(a, b)], axis=1), axis=0)  # from (larger id) -> to
     od = np.bincount(pairs[:, 0], minlength=n)
@@ -200,6 +208,37 @@ def heavy_triangle_counts():
     m = 1700
     w = 2 * m ** 3
     return np.array([w + m * m * 3, w + m * m * 3, w + 2 * m * m * 6 + 6], dtype=np.int64)
+
+
+# one triangle, six different multiplicities, every degree order (shared with the transitive and undirected tests)
+PRIMES = {(0, 1): 2, (1, 0): 3, (1, 2): 5, (2, 1): 7, (0, 2): 11, (2, 0): 13}
+PRIME_LOOPS = (1, 2, 4)   # self-loops at the corners 0, 1, 2
+PENDANT_UNIT = 40         # see prime_triangle
+
+
+@functools.lru_cache(maxsize=None)
+def prime_triangle(pendants):
+    """The triangle {0, 1, 2} with m(0,1), m(1,0), m(1,2), m(2,1), m(0,2), m(2,0) = 2, 3, 5, 7, 11, 13 and 1, 2, 4
+    self-loops, and pendants[i] bundles of pendant relationships at corner i.  A corner's degree counts its
+    relationships with their multiplicities (29, 17 and 36 here), so single pendant relationships would leave the
+    degree order where the primes put it: a bundle is PENDANT_UNIT relationships, each to a leaf of its own and
+    pointing out of or into the corner in turn, which outweighs the triangle's own spread of 19.  The six
+    permutations of (1, 2, 3) bundles put the corners into the six degree orders, so a walk that takes a payload
+    half or a payload for another shows under at least one of them."""
+    src, dst = [], []
+    for (x, y), m in PRIMES.items():
+        src += [x] * m
+        dst += [y] * m
+    for x, s in enumerate(PRIME_LOOPS):
+        src += [x] * s
+        dst += [x] * s
+    n = 3
+    for x, k in enumerate(pendants):
+        for j in range(k * PENDANT_UNIT):
+            a, b = (x, n) if j % 2 else (n, x)
+            src.append(a), dst.append(b)
+            n += 1
+    return _frozen(n, src, dst, 501)
 
 
 # ---- the tagged-id graph ------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""Shared by the tests of the transitive triangle (csrc/k_tri_trans.hip, routes "triangle_transitive" and
+"""Shared by the tests of the transitive triangle (csrc/k_tri_nodes.hip, routes "triangle_transitive" and
 "triangle_transitive_grouped"):
   MATCH (a)-[r1]->(b)-[r2]->(c)<-[r3]-(a) RETURN count(*)            (r1, r2, r3 pairwise distinct)
   MATCH (a)-[r1]->(b)-[r2]->(c)<-[r3]-(a) RETURN id(a), count(*)     (or id(b), or id(c))
@@ -18,8 +18,9 @@ multiplicity matrix and Q = A (A - 1), R = A A^T elementwise:
 import numpy as np
 
 from tri_ref import random_multigraph  # noqa: F401  (re-exported)
-from tri_grouped_ref import (BY_NODE_WIN, TILE_SLOTS, clique_and_triangles, disjoint_triangles,  # noqa: F401
-                             heavy_triangle, relabel, star_behind, tagged_graph, walk_slots)
+from tri_grouped_ref import (BY_NODE_WIN, PRIME_LOOPS, PRIMES, TILE_SLOTS, clique_and_triangles,  # noqa: F401
+                             degree_order, disjoint_triangles, heavy_triangle, prime_triangle, relabel, star_behind,
+                             tagged_graph, walk_slots)
 
 SOURCE, MIDDLE, SINK = 0, 1, 2  # include/capsmi.h CAPSMI_TRI_ROLE_*: the positions a, b, c
 ROLES = (SOURCE, MIDDLE, SINK)
@@ -116,15 +117,3 @@ def rows_of(cnt, ids=None):
     """the result rows [(id, count)] of a count vector: the nodes with a non-zero count"""
     nz = np.nonzero(cnt)[0]
     return [{"id": int(ids[i] if ids is not None else i), "n": int(cnt[i])} for i in nz]
-
-
-def degree_order(n, src, dst):
-    """degree-order id of every node, as tri_build ranks them (tri_grouped_ref.walk_slots): by (relationship count
-    without loops, id), the highest first"""
-    src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
-    nl = src != dst
-    deg = np.bincount(src[nl], minlength=n) + np.bincount(dst[nl], minlength=n)
-    order = np.lexsort((np.arange(n), deg))
-    rid = np.empty(n, dtype=np.int64)
-    rid[order] = n - 1 - np.arange(n)
-    return rid

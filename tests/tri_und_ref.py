@@ -1,4 +1,4 @@
-"""Shared by the tests of the undirected triangle (csrc/k_tri_und.hip, routes "triangle_undirected" and
+"""Shared by the tests of the undirected triangle (csrc/k_tri_nodes.hip, routes "triangle_undirected" and
 "triangle_undirected_grouped"):
   MATCH (a)-[r1]-(b)-[r2]-(c)-[r3]-(a) RETURN count(*)            (r1, r2, r3 pairwise distinct)
   MATCH (a)-[r1]-(b)-[r2]-(c)-[r3]-(a) RETURN id(a), count(*)     (or id(b), or id(c))
@@ -23,9 +23,9 @@ T + sum_y [2 s(x) + 2 s(y)] Q[x,y] + self.
 """
 import numpy as np
 
-from tri_trans_ref import (BY_NODE_WIN, TILE_GRID_CAP, TILE_SLOTS, clique_and_triangles, degree_order,  # noqa: F401
-                           disjoint_triangles, heavy_triangle, random_multigraph, relabel, rows_of, star_behind,
-                           tagged_graph, walk_slots)
+from tri_trans_ref import (BY_NODE_WIN, PRIME_LOOPS, PRIMES, TILE_GRID_CAP, TILE_SLOTS,  # noqa: F401
+                           clique_and_triangles, degree_order, disjoint_triangles, heavy_triangle, prime_triangle,
+                           random_multigraph, relabel, rows_of, star_behind, tagged_graph, walk_slots)
 
 END, MIDDLE = 0, 1            # include/capsmi.h CAPSMI_TRI_UND_*: the class of positions a and c, and of b
 CLASSES = (END, MIDDLE)
