@@ -83,6 +83,8 @@ PP = POINTER(c_void_p)
 STRS = POINTER(c_char_p)
 
 INTERN_FN = ctypes.CFUNCTYPE(c_int64, c_void_p, ctypes.POINTER(ctypes.c_char), c_size_t)
+# capsmi_string_sink_fn(ctx, n, offsets, bytes, codes_out) -> 0 on success
+STRING_SINK_FN = ctypes.CFUNCTYPE(c_int32, c_void_p, c_int64, POINTER(c_int64), POINTER(ctypes.c_char), POINTER(c_int64))
 # capsmi_collective_fn(ctx, op, send, recv, count, dtype) -> 0 on success
 COLLECTIVE_FN = ctypes.CFUNCTYPE(c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_int32)
 COLL_ALL_GATHER, COLL_ALL_REDUCE_SUM, COLL_ALL_REDUCE_MAX, COLL_ALL_TO_ALL_V, COLL_U32 = 0, 1, 2, 3, 100
@@ -112,6 +114,8 @@ _SIGS = {
     "capsmi_session_kernel_bytes": (c_int32, [P, c_char_p, POINTER(ctypes.c_double)]),
     "capsmi_session_set_params": (c_int32, [P, c_int32, P]),
     "capsmi_session_set_strings": (c_int32, [P, c_int64, P, P, P]),
+    "capsmi_session_set_string_sink": (c_int32, [P, STRING_SINK_FN, c_void_p]),
+    "capsmi_session_string_count": (c_int32, [P, POINTER(c_int64)]),
     "capsmi_table_from_host": (c_int32, [P, c_int32, POINTER(ColDesc), c_int64, PP]),
     "capsmi_table_from_device": (c_int32, [P, c_int32, POINTER(ColDesc), c_int64, PP]),
     "capsmi_table_retain": (c_int32, [P]),

@@ -33,6 +33,13 @@ computed on the device from the bytes of the session's string store (include/cap
 CAPSMI_X_TO_BOOLEAN).  The front end picks them by the operand's Cypher type; Size, ToInteger and ToFloat stay the
 list and number forms.
 
+Functions that make a String: ToString (:233) of a Long, a Boolean or a String, and Concat (Add over a String and a
+String or a Number, :160-181, ``functions.concat``).  The strings are made on the device and get their codes from the
+session's dictionary through the string sink (include/capsmi.h, CAPSMI_X_TO_STRING, CAPSMI_X_CONCAT,
+capsmi_session_set_string_sink).  ``BinOp("+")`` compiles to the concatenation when an operand is typed String by
+the tree itself -- a String literal, a ToString, a Concat, a RelType, or a ``+`` over one; over a String column the
+front end builds ``Concat``, as it picks ``StrSize`` for ``Size``.  Double operands are not implemented.
+
 ``compile_program`` lowers a tree to the postfix ``capsmi_expr`` program of include/capsmi.h.
 """
 from __future__ import annotations
@@ -61,7 +68,12 @@ STRING_MATCH_OPS = (X_STARTS_WITH, X_ENDS_WITH, X_CONTAINS)
 # 52..55 are unassigned; the functions that read a String's characters (they read the session's string store too)
 X_STR_SIZE, X_STR_TO_INTEGER, X_STR_TO_FLOAT, X_TO_BOOLEAN = range(56, 60)
 STRING_CONV_OPS = (X_STR_SIZE, X_STR_TO_INTEGER, X_STR_TO_FLOAT, X_TO_BOOLEAN)
-STRING_STORE_OPS = STRING_MATCH_OPS + STRING_CONV_OPS  # a program that holds one needs Session.sync_strings()
+# 60..63 are unassigned; the functions that make a String: their codes come from the session's string sink
+X_TO_STRING, X_CONCAT = 64, 65
+STRING_MAKE_OPS = (X_TO_STRING, X_CONCAT)
+STRING_STORE_OPS = STRING_MATCH_OPS + STRING_CONV_OPS  # the opcodes that read a String's bytes
+# a program that holds one needs Session.sync_strings(): the makers read STR operands from the store and merge into it
+STRING_SYNC_OPS = STRING_STORE_OPS + STRING_MAKE_OPS
 
 BIN_OPS = {"=": X_EQ, "<>": X_NEQ, "<": X_LT, "<=": X_LE, ">": X_GT, ">=": X_GE, "+": X_ADD, "-": X_SUB, "*": X_MUL,
            "/": X_DIV, "&": X_BITAND, "|": X_BITOR, "<<": X_SHL, ">>>": X_SHRU}
@@ -376,6 +388,33 @@ class ToBoolean(Expr):
 _STRING_CONV = {StrSize: X_STR_SIZE, StrToInteger: X_STR_TO_INTEGER, StrToFloat: X_STR_TO_FLOAT, ToBoolean: X_TO_BOOLEAN}
 
 
+@dataclass(frozen=True, eq=False)
+class ToString(Expr):
+    """ToString(expr) (SparkSQLExprMapper.scala:233, ``cast(StringType)``).  Of a Long: Java's ``Long.toString`` --
+    decimal digits, a leading ``-`` for a negative value, no ``+``, no padding.  Of a Boolean: ``true`` or ``false``.  Of
+    a String: the operand itself.  NULL gives NULL.  A Double operand is not implemented on the device path (Java's
+    ``Double.toString`` is not restated)."""
+    arg: Expr
+
+
+@dataclass(frozen=True, eq=False)
+class Concat(Expr):
+    """Add(lhs, rhs) over a String and a String or a Long (SparkSQLExprMapper.scala:160-181, ``functions.concat``, the
+    Long cast to StringType): the bytes of ``left`` followed by the bytes of ``right``; NULL when either is NULL.  At
+    least one operand is a String; a Boolean or a Double operand is refused."""
+    left: Expr
+    right: Expr
+
+
+def is_string_typed(e: Expr) -> bool:
+    """Whether the tree itself types ``e`` as a String (a column's type is the front end's to know)."""
+    if isinstance(e, Lit):
+        return e.resolved_type() == STR
+    if isinstance(e, (ToString, Concat, RelType)):
+        return True
+    return isinstance(e, BinOp) and e.op == "+" and (is_string_typed(e.left) or is_string_typed(e.right))
+
+
 def _sorted_by_name(cols, names):
     cols, names = tuple(cols), tuple(names)
     if len(cols) != len(names):
@@ -561,7 +600,7 @@ def compile_program(e: Expr, column_index: Callable[[str], int], encode_str: Cal
         elif isinstance(x, BinOp):
             go(x.left)
             go(x.right)
-            out.append((BIN_OPS[x.op], 0, 0, 0))
+            out.append((X_CONCAT if x.op == "+" and is_string_typed(x) else BIN_OPS[x.op], 0, 0, 0))
         elif isinstance(x, Not):
             go(x.arg)
             out.append((X_NOT, 0, 0, 0))
@@ -611,6 +650,13 @@ def compile_program(e: Expr, column_index: Callable[[str], int], encode_str: Cal
         elif type(x) in _STRING_CONV:
             go(x.arg)
             out.append((_STRING_CONV[type(x)], 0, 0, 0))
+        elif isinstance(x, ToString):
+            go(x.arg)
+            out.append((X_TO_STRING, 0, 0, 0))
+        elif isinstance(x, Concat):
+            go(x.left)
+            go(x.right)
+            out.append((X_CONCAT, 0, 0, 0))
         elif isinstance(x, RelType):
             go(x.to_case())
         elif isinstance(x, Case):

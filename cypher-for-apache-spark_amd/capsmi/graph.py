@@ -11,7 +11,7 @@ import ctypes
 from typing import Optional, Sequence, Tuple
 
 from . import _lib
-from .expr import STRING_STORE_OPS, Expr, compile_program, to_ctypes
+from .expr import STRING_SYNC_OPS, Expr, compile_program, to_ctypes
 from .table import GpuTable, Session
 
 RMAT_GRAPH500 = (57, 19, 19)  # (A, B, C) percent, D = 5  -- SURVEY.md §8d
@@ -42,7 +42,7 @@ class NodeBitmap:
             names = nodes.physicalColumns
             index = {n: i for i, n in enumerate(names)}
             prog = compile_program(predicate, lambda c: index[c], self.session.encode_str)
-            if any(p[0] in STRING_STORE_OPS for p in prog):
+            if any(p[0] in STRING_SYNC_OPS for p in prog):
                 self.session.sync_strings()
             _lib.call("capsmi_bitmap_add_scan", self._h, nodes.handle, id_col.encode(), len(prog), to_ctypes(prog))
         return self

@@ -30,7 +30,7 @@ import numpy as np
 from .expr import (BOOL, F64, I64, LIST, STR, Ands, BinOp, Col, Explode, Expr, In, IsNotNull, IsNull, ListLit, Lit, Not, Ors,
                    Contains, EndsWith, Index, InList, Keys, Labels, Range, Size, StartsWith, ands, eq,
                    Abs, Ceil, E, Exp, Floor, Log, Log10, Round, Sign, Sqrt, ToFloat, ToInteger,
-                   StrSize, StrToFloat, StrToInteger, ToBoolean)
+                   StrSize, StrToFloat, StrToInteger, ToBoolean, ToString, Concat)
 from .table import ColumnData, decode_value
 
 
@@ -491,6 +491,10 @@ def to_expr(spec, header: Sequence[str]) -> Expr:
         return _MATH[op](to_expr(spec[1], header))
     if op in _STRING_CONV:  # ["str_size", s], ["str_tointeger", s], ["str_tofloat", s], ["toboolean", x]
         return _STRING_CONV[op](to_expr(spec[1], header))
+    if op == "tostring":  # ["tostring", x]
+        return ToString(to_expr(spec[1], header))
+    if op == "concat":  # ["concat", a, b]: + over a String and a String or a Long (the mirror has no types)
+        return Concat(to_expr(spec[1], header), to_expr(spec[2], header))
     if op == "e":  # ["e"]
         return E
     if op == "range":

@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _lib
 from .expr import (BOOL, F64, I64, LIST, STR, BinOp, CapsmiExpr, Case, Col, Explode, Expr, In, Index, InList, Keys, Labels, ListLit,
-                   Lit, Param, Range, Size, STRING_STORE_OPS, contains_range, needs_list_lowering, compile_program,
+                   Lit, Param, Range, Size, STRING_SYNC_OPS, contains_range, needs_list_lowering, compile_program,
                    contains_explode, mask_list_args, to_ctypes)
 
 _TLS = threading.local()
@@ -172,6 +172,18 @@ class StringDictionary:
         self._codes = [c for c, _ in merged]
         self._sorted = [x for _, x in merged]
 
+    def intern_batch(self, offsets, data) -> np.ndarray:
+        """The codes (int64[n]) of the n strings ``data[offsets[i]:offsets[i + 1]]`` -- the arrays a string sink gets
+        (include/capsmi.h capsmi_string_sink_fn): one ``extend`` for the whole batch, so ``growth`` moves at most once,
+        then one lookup per string.  The strings may repeat and may be known.  Bytes that are not UTF-8 are kept as
+        surrogate escapes, the inverse of ``arrays()``."""
+        data = bytes(data)
+        strs = [data[int(offsets[i]):int(offsets[i + 1])].decode("utf-8", "surrogateescape")
+                for i in range(len(offsets) - 1)]
+        self.extend(strs)
+        return np.fromiter((self._codes[bisect.bisect_left(self._sorted, x)] for x in strs), dtype=np.int64,
+                           count=len(strs))
+
     def encode(self, s: str) -> int:
         i = bisect.bisect_left(self._sorted, s)
         if i < len(self._sorted) and self._sorted[i] == s:
@@ -199,6 +211,33 @@ class Session:
         self.dictionary = dictionary or StringDictionary()
         self.params: List[object] = []  # the values of set_params (Explode of a list Param reads them)
         self._strings_at = None  # the dictionary's growth counter at the last upload of the string store
+        # the string sink (include/capsmi.h capsmi_session_set_string_sink): strings made on the device get their
+        # codes from this session's dictionary; the callback object lives as long as the session
+        self._sink_cb = _lib.STRING_SINK_FN(self._string_sink)
+        self.set_string_sink(self._sink_cb)
+
+    def _string_sink(self, _ctx, n, offsets, data, codes_out) -> int:
+        try:
+            off = np.ctypeslib.as_array(offsets, shape=(n + 1,))
+            synced = self._strings_at == self.dictionary.growth
+            codes = self.dictionary.intern_batch(off, ctypes.string_at(data, int(off[n])))
+            ctypes.memmove(codes_out, codes.ctypes.data, 8 * n)
+            if synced:  # the library merges what is new into its store: nothing to upload again
+                self._strings_at = self.dictionary.growth
+            return 0
+        except Exception:  # an exception cannot cross the C frames: the action fails with the sink's status
+            return 1
+
+    def set_string_sink(self, cb) -> None:
+        """Register ``cb`` (a ``_lib.STRING_SINK_FN`` the caller keeps alive) as the session's string sink, None to
+        remove it.  The session registers its dictionary's at creation."""
+        _lib.call("capsmi_session_set_string_sink", self._h, cb if cb is not None else _lib.STRING_SINK_FN(), None)
+
+    def string_count(self) -> int:
+        """Entries of the string store registered on the device (capsmi_session_string_count)."""
+        n = ctypes.c_int64()
+        _lib.call("capsmi_session_string_count", self._h, ctypes.byref(n))
+        return n.value
 
     @property
     def handle(self):
@@ -279,8 +318,9 @@ class Session:
 
     def sync_strings(self) -> None:
         """Register the dictionary's strings as the session's string store (include/capsmi.h
-        capsmi_session_set_strings), which StartsWith / EndsWith / Contains and StrSize / StrToInteger / StrToFloat /
-        ToBoolean read on the device.  Uploads the whole dictionary when it has grown since the last upload, else
+        capsmi_session_set_strings), which StartsWith / EndsWith / Contains, StrSize / StrToInteger / StrToFloat /
+        ToBoolean and the String operands of Concat read on the device, and into which ToString / Concat merge the
+        strings they make (the sink then moves ``_strings_at`` along, so they are not uploaded again).  Uploads the whole dictionary when it has grown since the last upload, else
         nothing; codes are stable, so every store is a superset of the one before and programs compiled earlier stay
         valid."""
         if self._strings_at == self.dictionary.growth:
@@ -613,7 +653,7 @@ class GpuTable:
             return index[name]
 
         prog = compile_program(e, col, self.session.encode_str)
-        if any(p[0] in STRING_STORE_OPS for p in prog):  # the literals are encoded by now: the store holds them
+        if any(p[0] in STRING_SYNC_OPS for p in prog):  # the literals are encoded by now: the store holds them
             self.session.sync_strings()
         arr = to_ctypes(prog)
         if type(e) is Col:

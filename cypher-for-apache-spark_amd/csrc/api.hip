@@ -738,6 +738,7 @@ capsmi_status capsmi_session_set_strings(capsmi_session* s, int64_t nstrings, co
     st->n = nstrings;
     st->hcodes.assign(codes, codes + nstrings);
     st->hoffsets.assign(offsets, offsets + nstrings + 1);
+    if (nbytes > 0) st->hbytes.assign(bytes, (size_t)nbytes);
     st->codes = dev_alloc(sizeof(int64_t) * nstrings, s);
     st->offsets = dev_alloc(sizeof(int64_t) * (nstrings + 1), s);
     st->bytes = dev_alloc(nbytes > 0 ? nbytes : 1, s);
@@ -747,6 +748,22 @@ capsmi_status capsmi_session_set_strings(capsmi_session* s, int64_t nstrings, co
     if (nbytes > 0) HIP_CHECK(hipMemcpyAsync(P<void>(st->bytes), bytes, nbytes, hipMemcpyHostToDevice, s->stream));
     HIP_CHECK(hipStreamSynchronize(s->stream));  // the caller's arrays are free again when the call returns
     s->strings = std::move(st);
+    API_END
+}
+
+capsmi_status capsmi_session_set_string_sink(capsmi_session* s, capsmi_string_sink_fn fn, void* ctx) {
+    API_BEGIN
+    need(s, "session");
+    s->sink = fn;
+    s->sink_ctx = fn ? ctx : nullptr;
+    API_END
+}
+
+capsmi_status capsmi_session_string_count(capsmi_session* s, int64_t* out) {
+    API_BEGIN
+    need(s, "session");
+    need(out, "out");
+    *out = s->strings ? s->strings->n : 0;
     API_END
 }
 

@@ -62,11 +62,14 @@ struct ListStore {
 };
 
 // The session's string store (capsmi_session_set_strings): string i has code codes[i] (strictly ascending) and
-// bytes[offsets[i] .. offsets[i+1]).  Replaced as a whole; a pass holds the one it started with.
+// bytes[offsets[i] .. offsets[i+1]).  Replaced as a whole -- by a registration, or by the merge of the strings an
+// action has made (str_store_merge, k_strmake.hip) -- and a pass holds the one it started with.
 struct StrStore {
     int64_t n = 0;                           // strings (> 0: an empty registration clears the store)
     Buf codes, offsets, bytes;               // int64[n], int64[n + 1], uint8[offsets[n]]
     std::vector<int64_t> hcodes, hoffsets;   // host copies: constant operands are resolved without the device
+    std::string hbytes;                      // and the bytes: a sink's codes are checked against them, literal
+                                             // operands of CONCAT are read from them
 };
 inline bool is_str_match(int32_t op) { return op >= CAPSMI_X_STARTS_WITH && op <= CAPSMI_X_CONTAINS; }
 
@@ -196,6 +199,9 @@ struct capsmi_session {
     };
     std::vector<Param> params;  // query parameters (capsmi_session_set_params)
     std::shared_ptr<const capsmi::StrStore> strings;  // the string store (capsmi_session_set_strings); null: none
+    // how strings made on the device get their codes (capsmi_session_set_string_sink); null: no sink
+    capsmi_string_sink_fn sink = nullptr;
+    void* sink_ctx = nullptr;
     int device = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;  // current (own or external)
@@ -422,6 +428,25 @@ void str_index_check(capsmi_session* s, const int64_t* err);
 void str_conv(capsmi_session* s, int32_t op, const StrOperand& o, int64_t n, int64_t* out, uint8_t* out_valid);
 // the same for a constant, on the host (reads its bytes back; synchronises): whether the result is not NULL, and it
 bool str_conv_fold(capsmi_session* s, int32_t op, int64_t code, int64_t* value);
+// toString() and string concatenation (k_strmake.hip; the formatting code is str_make.h).  An operand is a column
+// of String codes, Longs or Booleans (data, valid or null), or constant bytes (a literal, formatted by the caller).
+struct MakeOperand {
+    int32_t type = CAPSMI_STR;  // the column's type; unused for a constant
+    bool is_const = false;
+    std::string bytes;          // the constant
+    const int64_t* data = nullptr;
+    const uint8_t* valid = nullptr;
+};
+// out / out_valid[r] = the code of the bytes of o[0] followed by those of o[1] (nops = 1: o[0] alone), NULL when an
+// operand is NULL; at least one operand is a column.  The distinct operand tuples are formatted once each, the
+// session's sink gives the codes, and the new entries are merged into the registered store.  Throws
+// ILLEGAL_ARGUMENT without a sink, for what the sink may not do, and as str_match does for a STR column
+// (synchronises)
+void str_make(capsmi_session* s, int nops, const MakeOperand* o, int64_t n, int64_t* out, uint8_t* out_valid);
+// the same for constant bytes, on the host: one sink call with one string, the merge, the code
+int64_t str_make_fold(capsmi_session* s, const std::string& bytes);
+// the bytes of a constant String operand's code (throws ILLEGAL_ARGUMENT when no store is registered or it lacks it)
+std::string str_const_bytes(capsmi_session* s, int64_t code);
 // range(from, to, step) per row (step null: 1) as a store whose list r is row r's; `valid`: the rows none of
 // whose operands is null.  Throws ILLEGAL_ARGUMENT for a step 0, UNSUPPORTED for more elements than the device
 // holds (synchronises)

@@ -20,7 +20,7 @@ constexpr int kMaxCols = 64;   // columns a program may address
 inline bool is_list_type(int32_t t) { return t >= CAPSMI_LIST_I64 && t <= CAPSMI_LIST_STR; }
 
 // A new opcode of include/capsmi.h gets a row in expr_pops and check_program.  The numbers are not contiguous
-// (32..39 and 52..55 are unassigned): an opcode is unknown exactly when expr_pops has no row for it (known_expr_op
+// (32..39, 52..55 and 60..63 are unassigned): an opcode is unknown exactly when expr_pops has no row for it (known_expr_op
 // below).
 
 // the numeric block (DIV .. TO_INTEGER): what k_expr.hip's math instantiation adds to the interpreter
@@ -38,6 +38,10 @@ constexpr int32_t str_conv_type(int32_t op) {  // the result's type
     return op == CAPSMI_X_STR_TO_FLOAT ? CAPSMI_F64 : (op == CAPSMI_X_TO_BOOLEAN ? CAPSMI_BOOL : CAPSMI_I64);
 }
 
+// the functions that make a String (TO_STRING, CONCAT): lowered to passes of their own (k_strmake.hip) before the
+// interpreter runs; the strings get their codes from the session's string sink
+constexpr bool is_str_make(int32_t op) { return op == CAPSMI_X_TO_STRING || op == CAPSMI_X_CONCAT; }
+
 // operands an opcode pops: the one arity table (-1: unknown opcode, CAPSMI_X_PARAM included: it is bound before
 // anything counts)
 inline int expr_pops(const capsmi_expr& x) {
@@ -47,7 +51,7 @@ inline int expr_pops(const capsmi_expr& x) {
         case CAPSMI_X_SQRT: case CAPSMI_X_LOG: case CAPSMI_X_LOG10: case CAPSMI_X_EXP: case CAPSMI_X_ABS:
         case CAPSMI_X_CEIL: case CAPSMI_X_FLOOR: case CAPSMI_X_ROUND: case CAPSMI_X_SIGN: case CAPSMI_X_TO_FLOAT:
         case CAPSMI_X_TO_INTEGER: case CAPSMI_X_STR_SIZE: case CAPSMI_X_STR_TO_INTEGER: case CAPSMI_X_STR_TO_FLOAT:
-        case CAPSMI_X_TO_BOOLEAN: return 1;
+        case CAPSMI_X_TO_BOOLEAN: case CAPSMI_X_TO_STRING: return 1;
         case CAPSMI_X_AND: case CAPSMI_X_OR: case CAPSMI_X_COALESCE: return x.arg;
         case CAPSMI_X_IN: return x.arg + 1;
         case CAPSMI_X_CASE: return 2 * x.arg + 1;
@@ -55,7 +59,8 @@ inline int expr_pops(const capsmi_expr& x) {
         case CAPSMI_X_ADD: case CAPSMI_X_SUB: case CAPSMI_X_MUL:
         case CAPSMI_X_BITAND: case CAPSMI_X_BITOR: case CAPSMI_X_SHL: case CAPSMI_X_SHRU:
         case CAPSMI_X_INDEX: case CAPSMI_X_IN_LIST:
-        case CAPSMI_X_STARTS_WITH: case CAPSMI_X_ENDS_WITH: case CAPSMI_X_CONTAINS: case CAPSMI_X_DIV: return 2;
+        case CAPSMI_X_STARTS_WITH: case CAPSMI_X_ENDS_WITH: case CAPSMI_X_CONTAINS: case CAPSMI_X_DIV:
+        case CAPSMI_X_CONCAT: return 2;
         default: return -1;
     }
 }
@@ -106,6 +111,9 @@ inline std::vector<std::pair<int, int>> operand_spans(const capsmi_expr* prog, i
 //     and a mixed entry pass (a row that holds no number yields NULL, as for ADD).
 //   - STR_SIZE, STR_TO_INTEGER, STR_TO_FLOAT and TO_BOOLEAN take a String (or an untyped NULL), TO_BOOLEAN a BOOL
 //     too: any other scalar type and a mixed entry are CAPSMI_ERR_ILLEGAL_ARGUMENT.
+//   - TO_STRING takes a Long, a Boolean or a String, CONCAT Strings and Longs of which at least one is a String (an
+//     untyped NULL stands for either): a Double is CAPSMI_ERR_NOT_IMPLEMENTED (Java's Double.toString is not
+//     restated), a Boolean in CONCAT, two Longs and a mixed entry are CAPSMI_ERR_ILLEGAL_ARGUMENT.
 inline int32_t check_program(const int32_t* col_types, int ncols, int32_t nn, const capsmi_expr* prog) {
     struct Entry {
         int32_t t;
@@ -180,6 +188,21 @@ inline int32_t check_program(const int32_t* col_types, int ncols, int32_t nn, co
                               "is untyped or typed String)");
                 res.t = str_conv_type(x.op);
                 break;
+            case CAPSMI_X_TO_STRING: case CAPSMI_X_CONCAT: {
+                const bool cat = x.op == CAPSMI_X_CONCAT;
+                for (int q = 0; q < pops; ++q) {
+                    REQUIRE(!opd[q].mixed, CAPSMI_ERR_ILLEGAL_ARGUMENT, kMixed);
+                    REQUIRE(opd[q].t != CAPSMI_F64, CAPSMI_ERR_NOT_IMPLEMENTED,
+                            std::string("a Double operand of ") + (cat ? "string concatenation" : "toString()") +
+                                " would need Java's Double.toString, which is not restated on the device path");
+                    REQUIRE(!cat || opd[q].t != CAPSMI_BOOL, CAPSMI_ERR_ILLEGAL_ARGUMENT,
+                            "string concatenation takes String and Long operands, not a Boolean");
+                }
+                REQUIRE(!cat || opd[0].t != CAPSMI_I64 || opd[1].t != CAPSMI_I64, CAPSMI_ERR_ILLEGAL_ARGUMENT,
+                        "string concatenation needs a String operand (Long + Long is CAPSMI_X_ADD)");
+                res.t = CAPSMI_STR;
+                break;
+            }
             case CAPSMI_X_NEG: case CAPSMI_X_ABS: res = opd[0]; break;
             case CAPSMI_X_COALESCE: case CAPSMI_X_CASE: {  // CASE: [p1, v1, .., default]; the predicates are BOOL
                 const bool is_case = x.op == CAPSMI_X_CASE;

@@ -23,11 +23,14 @@
 //     (lower_str_match below): k_strmatch.hip matches the bytes of the session's string store.
 //   - size(), toInteger(), toFloat() and toBoolean() of a String (:124-127, :231, :229, :235) are lowered likewise
 //     (lower_str_conv below): k_strconv.hip reads the store's bytes, and the interpreter never sees these opcodes.
+//   - toString() (:233) and Add over a String (:160-181, functions.concat) make Strings (lower_str_make below):
+//     k_strmake.hip formats one string per distinct operand tuple and the session's string sink gives the codes.
 //   - Divide (:186), Sqrt .. Sign (:249-260), ToFloat / ToInteger (:229-231): eval_math below, with the rules of the
 //     Spark 2.2.1 Column calls the mapper makes (include/capsmi.h states them per opcode).  Double log and exp are
 //     library code of some size, so these cases exist only in the kMath instantiation of the interpreter, which
 //     launch_eval takes for a program that holds one of them; every other program runs the code it ran before.
 #include "capsmi_impl.h"
+#include "str_make.h"
 
 namespace capsmi {
 
@@ -403,7 +406,9 @@ void replace_span_and_eval(capsmi_session* s, const capsmi_table* t, int32_t nn,
             REQUIRE(slot < kMaxCols, CAPSMI_ERR_NOT_IMPLEMENTED,
                     std::string(prog[at].op == CAPSMI_X_IN_LIST
                                     ? "IN over a list column"
-                                    : (is_str_conv(prog[at].op) ? "a function of a String's characters" : "a string match")) +
+                                    : (is_str_conv(prog[at].op)
+                                           ? "a function of a String's characters"
+                                           : (is_str_make(prog[at].op) ? "a function that makes a String" : "a string match"))) +
                         " in a program that reads 64 columns");
             l.ref.arg = slot;
             view.cols[slot] = std::move(l.res);
@@ -496,6 +501,58 @@ Lowered lower_str_conv(capsmi_session* s, const capsmi_table* t, const capsmi_ex
     return l;
 }
 
+// toString() or a concatenation (node `at`, stack [x] or [a, b]): k_strmake.hip's passes produce the STR column and
+// grow the string store.  A NULL literal operand: NULL without a kernel or a sink call; literals are formatted here
+// and stay constants, and when every operand is one the string is folded on the host (one sink call); toString of a
+// String is its operand.
+Lowered lower_str_make(capsmi_session* s, const capsmi_table* t, const capsmi_expr* prog, int at) {
+    const bool cat = prog[at].op == CAPSMI_X_CONCAT;
+    const auto span = operand_spans(prog, at);
+    Lowered l{span[0].first, {}, {}};
+    l.ref.op = CAPSMI_X_NULL;
+    l.ref.arg = CAPSMI_STR + 1;
+    for (const auto& sp : span)
+        if (sp.first == sp.second && prog[sp.first].op == CAPSMI_X_NULL) return l;
+    MakeOperand opd[2];
+    Column col[2];
+    const int nops = (int)span.size();
+    int ncol = 0;
+    for (int q = 0; q < nops; ++q) {
+        const capsmi_expr& x = prog[span[q].first];
+        if (span[q].first == span[q].second && x.op == CAPSMI_X_LIT) {
+            if (!cat && x.type == CAPSMI_STR) {  // toString of a String literal
+                l.ref = x;
+                return l;
+            }
+            uint8_t buf[20];
+            opd[q].is_const = true;
+            if (x.type == CAPSMI_STR) opd[q].bytes = str_const_bytes(s, x.ival);
+            else if (x.type == CAPSMI_BOOL) opd[q].bytes.assign((const char*)buf, strmake::format_bool(x.ival != 0, buf));
+            else opd[q].bytes.assign((const char*)buf, strmake::format_long(x.ival, buf));
+            continue;
+        }
+        col[q] = operand_column(s, t, prog, span[q].first, span[q].second);
+        if (!cat && col[q].type == CAPSMI_STR) {  // toString of a String
+            l.res = std::move(col[q]);
+            return l;
+        }
+        opd[q].type = col[q].type;
+        opd[q].data = col[q].d();
+        opd[q].valid = col[q].v();
+        ++ncol;
+    }
+    if (ncol == 0) {
+        l.ref.op = CAPSMI_X_LIT;
+        l.ref.arg = 0;
+        l.ref.type = CAPSMI_STR;
+        l.ref.ival = str_make_fold(s, nops > 1 ? opd[0].bytes + opd[1].bytes : opd[0].bytes);
+        return l;
+    }
+    l = lowered_column(s, span[0].first, t->nrows, "__str_make", CAPSMI_STR);
+    str_make(s, nops, opd, t->nrows, P<int64_t>(l.res.data), P<uint8_t>(l.res.valid));
+    return l;
+}
+
 // evaluates prog over t's rows; returns its static type
 int32_t launch_eval(capsmi_session* s, const capsmi_table* t, int32_t nn, const capsmi_expr* prog, int64_t* out,
                     uint8_t* out_valid, uint8_t* flags) {
@@ -503,9 +560,11 @@ int32_t launch_eval(capsmi_session* s, const capsmi_table* t, int32_t nn, const 
     const int64_t n = t->nrows;
     if (n == 0) return type;
     for (int i = 0; i < nn; ++i) {  // the first node that runs as a pass of its own; the recursion lowers the rest
-        if (prog[i].op != CAPSMI_X_IN_LIST && !is_str_match(prog[i].op) && !is_str_conv(prog[i].op)) continue;
-        Lowered l = (prog[i].op == CAPSMI_X_IN_LIST ? lower_in_list
-                                                    : (is_str_conv(prog[i].op) ? lower_str_conv : lower_str_match))(s, t, prog, i);
+        const int32_t op = prog[i].op;
+        if (op != CAPSMI_X_IN_LIST && !is_str_match(op) && !is_str_conv(op) && !is_str_make(op)) continue;
+        Lowered l = (op == CAPSMI_X_IN_LIST
+                         ? lower_in_list
+                         : (is_str_conv(op) ? lower_str_conv : (is_str_make(op) ? lower_str_make : lower_str_match)))(s, t, prog, i);
         replace_span_and_eval(s, t, nn, prog, i, l, out, out_valid, flags);
         return type;
     }

@@ -247,11 +247,39 @@ enum {
                                      +-Infinity and underflow to +-0.0 included ("-0" gives -0.0), for mantissa
                                      and exponent digit strings of any length.  Any other byte gives NULL, every
                                      non-ASCII byte among them */
-    CAPSMI_X_TO_BOOLEAN = 59      /* stack [s] or [b]: BOOL.  Of a String (StringUtils.isTrueString /
+    CAPSMI_X_TO_BOOLEAN = 59,     /* stack [s] or [b]: BOOL.  Of a String (StringUtils.isTrueString /
                                      isFalseString over toLowerCase): no trimming, ASCII case folded (none of the
                                      words has a non-ASCII case partner); "t", "true", "y", "yes", "1" give TRUE,
                                      "f", "false", "n", "no", "0" FALSE, anything else NULL.  Of a BOOL: the
                                      identity */
+    /* 60..63 are unassigned. */
+    /* Functions that make a String (ToString, :233, cast(StringType); Add over a String and a String or a Number,
+       :160-181, functions.concat with the number cast to StringType).  Both yield CAPSMI_STR, which may feed any
+       opcode that takes a String in the same program.  A produced String has no code until the caller gives it
+       one: the action hands the strings it has made to the session's string sink (capsmi_session_set_string_sink
+       below), gets their codes back and merges the new entries into the registered string store, so the codes are
+       readable by every string opcode at once and by later actions.  Without a sink an action that has strings to
+       make fails with CAPSMI_ERR_ILLEGAL_ARGUMENT ("no string sink").  A NULL operand gives NULL (Spark's concat is
+       null if any input is); a NULL literal operand gives NULL in every row without a kernel and without a sink
+       call; operands that are all literals are folded on the host, with one sink call for the one string.  A STR
+       column operand reads the registered store as the string predicates do (no store, or a code that is not
+       registered: CAPSMI_ERR_ILLEGAL_ARGUMENT); TO_STRING of a Long needs no store beforehand, the merge creates
+       one.  An F64 operand is CAPSMI_ERR_NOT_IMPLEMENTED when the node is built: it would need Java's
+       Double.toString (JDK 8's FloatingDecimal, shortest-digits output with its known anomalies), which is not
+       restated here.  A list value is CAPSMI_ERR_NOT_IMPLEMENTED, a "mixed" value CAPSMI_ERR_ILLEGAL_ARGUMENT.
+       Each of these nodes runs as passes of its own before the row-wise interpreter (k_strmake.hip; the formatting
+       code is csrc/str_make.h): the distinct operand tuples are found first (a produced string is a function of
+       its operands), one string is made per tuple, load-balanced over fixed tiles of the output bytes, and the
+       rows gather their tuple's code.  a + b + c interns the intermediate a + b.  The rules are those of Spark
+       2.2.1's Cast to StringType and Concat, stated from knowledge of Spark's source, not from a run. */
+    CAPSMI_X_TO_STRING = 64,      /* stack [x]: STR.  Of a Long: Long.toString -- decimal digits, a leading '-' for a
+                                     negative value, no '+', no padding; Long.MIN_VALUE gives the 20 bytes
+                                     "-9223372036854775808".  Of a BOOL: "true" or "false".  Of a STR: the operand
+                                     itself (no kernel, no sink call) */
+    CAPSMI_X_CONCAT = 65          /* stack [a, b]: STR, the bytes of a followed by the bytes of b (UTF-8 is not
+                                     decoded).  Each operand is STR or I64, at least one of them STR or an untyped
+                                     NULL in its place; a Long is formatted as TO_STRING does.  A BOOL operand and
+                                     I64 + I64 are CAPSMI_ERR_ILLEGAL_ARGUMENT when the node is built */
 };
 
 typedef struct {
@@ -357,6 +385,13 @@ capsmi_status capsmi_session_kernel_time(capsmi_session* s, const char* name, in
  * dictionary side the whole byte array, for size one byte per slot; on the rows side of the parsers they depend on
  * the data and are not counted; "str_conv_lookup", the dictionary side's row gather: 26 B per row (size: 25 B);
  * size's lengths / scan / compaction are timed as "str_conv_starts", without bytes;
+ * toString() / string concatenation share "str_index" too; their distinct-tuple pass runs the hash kernels untimed;
+ * "str_make_lengths", one thread per distinct tuple, declares no bytes; "str_make_starts" is the write pass's plan
+ * (scan / compaction), without bytes; "str_make", the write pass: the output bytes written once + per distinct tuple
+ * two offsets (16 B) per STR operand and 8 B per Long operand; "str_store_merge", the copy into the grown store:
+ * the old store's bytes read and written once and the new entries' bytes likewise, its plan (scan / compaction) timed
+ * as "str_store_merge_starts", without bytes; "str_make_gather": 8 B read and
+ * 9 B written per row;
  * 0 otherwise; then the counter resets. */
 capsmi_status capsmi_session_kernel_bytes(capsmi_session* s, const char* name, double* bytes);
 /* fused-path routing of lazy plans: enable / disable (default on; off = operator by operator, for
@@ -388,6 +423,23 @@ capsmi_status capsmi_session_set_params(capsmi_session* s, int32_t nparams, cons
  * are CAPSMI_ERR_ILLEGAL_ARGUMENT.  On several ranks each registers its own store (the operators are row-local). */
 capsmi_status capsmi_session_set_strings(capsmi_session* s, int64_t nstrings, const int64_t* codes,
                                          const int64_t* offsets, const char* bytes);
+/* The string sink: how strings made on the device (CAPSMI_X_TO_STRING, CAPSMI_X_CONCAT) get their codes.  A code
+ * comes from a dictionary the caller owns, so the library cannot invent one: an action that has made strings calls
+ * `fn` on the thread that runs the action, once per lowered node, with host arrays that hold n >= 1 strings --
+ * string i is bytes[offsets[i] .. offsets[i+1]) -- and the sink writes one code per string into codes_out and
+ * returns 0.  The strings may repeat (two operand tuples can give equal bytes, "a" + "bc" and "ab" + "c") and may be
+ * in the caller's dictionary already.  Equal bytes must get equal codes, distinct bytes distinct codes; keeping code
+ * order equal to string order is the caller's business, as it is for capsmi_session_set_strings.  The sink must not
+ * call into the session.  After the call the library merges the entries whose codes the registered store does not
+ * hold into that store (codes stay strictly ascending; the old bytes move device to device; entries already present
+ * are dropped, so a repeated query merges nothing).  CAPSMI_ERR_ILLEGAL_ARGUMENT, with the store left as it was: a
+ * non-zero return, two different byte strings with one code, a code the store already holds for different bytes.
+ * fn NULL removes the sink.  On several ranks each rank's sink is its own (the operators are row-local). */
+typedef int32_t (*capsmi_string_sink_fn)(void* ctx, int64_t n, const int64_t* offsets, const char* bytes,
+                                         int64_t* codes_out);
+capsmi_status capsmi_session_set_string_sink(capsmi_session* s, capsmi_string_sink_fn fn, void* ctx);
+/* entries of the registered string store (0: none is registered) */
+capsmi_status capsmi_session_string_count(capsmi_session* s, int64_t* out);
 /* route "miss" counts materialisations in which a pattern over entity tables (joins of node and
  * relationship scans) matched no fused shape and ran operator by operator */
 capsmi_status capsmi_session_route_count(capsmi_session* s, const char* name, int64_t* count);

@@ -89,6 +89,9 @@ object Capsmi {
   final val X_STR_TO_INTEGER = 57  // [s]: Long holding a 32-bit Int, NULL for what UTF8String.toInt refuses
   final val X_STR_TO_FLOAT = 58    // [s]: Double, Double.parseDouble correctly rounded, NULL for what it refuses
   final val X_TO_BOOLEAN = 59      // [s] or [b]: BOOL; the ten words of StringUtils, else NULL; a Boolean stays
+  // 60..63 are unassigned.  Functions that make a String; the codes come from the session's string sink
+  final val X_TO_STRING = 64       // [x]: STR; Long.toString, true / false, a String stays
+  final val X_CONCAT = 65          // [a, b]: STR; Strings and Longs, at least one a String
 
   // capsmi_with_mask_list_column: which columns of a row pass
   final val MASK_TRUE = 0     // labels(): the Boolean flag is non-null and TRUE
@@ -193,6 +196,12 @@ trait CollectiveFn extends Callback {
   def invoke(ctx: Pointer, op: Int, send: Pointer, recv: Pointer, count: Long, dtype: Int): Int
 }
 
+/** capsmi_string_sink_fn: the n strings an action has made on the device (string i is bytes[offsets(i), offsets(i + 1)))
+  * handed to the session's dictionary, which writes one code per string and returns 0. */
+trait StringSinkFn extends Callback {
+  def invoke(ctx: Pointer, n: Long, offsets: Pointer, bytes: Pointer, codesOut: Pointer): Int
+}
+
 /** capsmi_intern_fn: strings of a CSV column handed, in row order, to the session's dictionary. */
 trait InternFn extends Callback {
   def invoke(ctx: Pointer, s: Pointer, n: Long): Long
@@ -217,6 +226,8 @@ trait CapsmiLib extends Library {
   def capsmi_session_set_fused(s: Pointer, enabled: Int): Int
   def capsmi_session_set_params(s: Pointer, nparams: Int, params: CapsmiParam): Int
   def capsmi_session_set_strings(s: Pointer, nstrings: Long, codes: Array[Long], offsets: Array[Long], bytes: Array[Byte]): Int
+  def capsmi_session_set_string_sink(s: Pointer, fn: StringSinkFn, ctx: Pointer): Int
+  def capsmi_session_string_count(s: Pointer, out: LongByReference): Int
   def capsmi_session_route_count(s: Pointer, name: String, count: LongByReference): Int
   def capsmi_session_set_unrouted_limit(s: Pointer, maxBytes: Long): Int
   def capsmi_session_set_csv_partitioning(s: Pointer, defaultParallelism: Long, maxPartitionBytes: Long,

@@ -93,10 +93,33 @@ final class GpuSession(device: Int = 0) extends RelationalCypherSession[GpuTable
 
   private var stringsAt = -1L
 
+  /** The string sink (capsmi_session_set_string_sink): the strings that toString and + make on the device get their
+    * codes from the dictionary.  The library merges the new ones into its store, so when the store was current
+    * before the call it is current after it.  The field keeps the callback reachable for the session's life. */
+  private val stringSink: StringSinkFn = new StringSinkFn {
+    override def invoke(ctx: Pointer, n: Long, offsets: Pointer, bytes: Pointer, codesOut: Pointer): Int =
+      try GpuSession.this.synchronized {
+        val synced = stringsAt == dictionary.growth
+        val off = offsets.getLongArray(0, n.toInt + 1)
+        val codes = new Array[Long](n.toInt)
+        var i = 0
+        while (i < n) {
+          val len = (off(i + 1) - off(i)).toInt
+          val raw = if (len == 0) Array.empty[Byte] else bytes.getByteArray(off(i), len)
+          codes(i) = dictionary.encode(new String(raw, java.nio.charset.StandardCharsets.UTF_8))
+          i += 1
+        }
+        codesOut.write(0, codes, 0, codes.length)
+        if (synced) stringsAt = dictionary.growth
+        0
+      } catch { case _: Throwable => 1 }
+  }
+  check(I.capsmi_session_set_string_sink(handle, stringSink, null))
+
   /** Registers the dictionary as the session's string store (capsmi_session_set_strings) when it has grown since
     * the last upload: ExprCompiler calls it for every program that reads a String's bytes (StartsWith / EndsWith /
-    * Contains, Size / ToFloat / ToInteger of a String, ToBoolean), after the
-    * program's literals are encoded.  Codes are stable, so every store is a superset of the one before. */
+    * Contains, Size / ToFloat / ToInteger of a String, ToBoolean) or makes a String (ToString, + over a String), after
+    * the program's literals are encoded.  Codes are stable, so every store is a superset of the one before. */
   def syncStrings(): Unit = synchronized {
     if (stringsAt != dictionary.growth) {
       val at = dictionary.growth

@@ -383,8 +383,10 @@ final class GpuTable private (val handle: Pointer)(implicit val session: GpuSess
   * Round / Sign (:249-260) and ToFloat / ToInteger of numbers (:229-231) are CAPSMI_X_DIV .. CAPSMI_X_TO_INTEGER,
   * E() the literal Math.E.  Size (:126-127), ToFloat and ToInteger of an operand of type CTString and ToBoolean (:235)
   * are CAPSMI_X_STR_SIZE / STR_TO_FLOAT / STR_TO_INTEGER / TO_BOOLEAN, chosen by the operand's Cypher type as the
-  * mapper's own Size chooses; they read the string store too.  Shapes the device path does not evaluate (regular
-  * expressions, other functions, maps, toString, + on strings, toBoolean of a number, rand()) raise
+  * mapper's own Size chooses; they read the string store too.  ToString (:233) and Add over an operand of type
+  * CTString (:160-181) are CAPSMI_X_TO_STRING / CAPSMI_X_CONCAT: the strings are made on the device and coded by
+  * the session's dictionary through the string sink (GpuSession).  Shapes the device path does not evaluate (regular
+  * expressions, other functions, maps, toString or + over a Double, toBoolean of a number, rand()) raise
   * NotImplementedException or, from the library, IllegalArgumentException.
   */
 final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters: CypherMap,
@@ -399,7 +401,8 @@ final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters:
     if (params.nonEmpty) bindParams()
     // the literals and parameters are encoded by now, so the store holds every string the program names
     if (out.exists(n => (n._1 >= Capsmi.X_STARTS_WITH && n._1 <= Capsmi.X_CONTAINS) ||
-        (n._1 >= Capsmi.X_STR_SIZE && n._1 <= Capsmi.X_TO_BOOLEAN))) table.session.syncStrings()
+        (n._1 >= Capsmi.X_STR_SIZE && n._1 <= Capsmi.X_TO_BOOLEAN) ||
+        n._1 == Capsmi.X_TO_STRING || n._1 == Capsmi.X_CONCAT)) table.session.syncStrings()
     out
   }
 
@@ -468,6 +471,9 @@ final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters:
     case LessThanOrEqual(l, r) => bin(Capsmi.X_LE, l, r, out)
     case GreaterThan(l, r) => bin(Capsmi.X_GT, l, r, out)
     case GreaterThanOrEqual(l, r) => bin(Capsmi.X_GE, l, r, out)
+    // functions.concat, :160-181: Add over a String and a String or a Number
+    case Add(l, r) if l.cypherType.material == CTString || r.cypherType.material == CTString =>
+      bin(Capsmi.X_CONCAT, l, r, out)
     case Add(l, r) => bin(Capsmi.X_ADD, l, r, out)
     case Subtract(l, r) => bin(Capsmi.X_SUB, l, r, out)
     case Multiply(l, r) => bin(Capsmi.X_MUL, l, r, out)
@@ -489,6 +495,8 @@ final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters:
     case ToInteger(x) => go(x, out); out += ((Capsmi.X_TO_INTEGER, 0, 0, 0L))
     // cast(BooleanType), :235: of a String or a Boolean; the library refuses numbers when the node is built
     case ToBoolean(x) => go(x, out); out += ((Capsmi.X_TO_BOOLEAN, 0, 0, 0L))
+    // cast(StringType), :233: of a Long, a Boolean or a String; the library refuses a Double when the node is built
+    case ToString(x) => go(x, out); out += ((Capsmi.X_TO_STRING, 0, 0, 0L))
     case BitwiseAnd(l, r) => bin(Capsmi.X_BITAND, l, r, out)
     case BitwiseOr(l, r) => bin(Capsmi.X_BITOR, l, r, out)
     case ShiftLeft(v, bits) => bin(Capsmi.X_SHL, v, bits, out)
