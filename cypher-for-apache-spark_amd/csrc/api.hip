@@ -542,6 +542,9 @@ bool apply(Config& c, const std::string& name, const char* v) {
     } else if (name == "CAPSMI_NARROW") {
         if (!parse_choice(v, {"auto", "off"}, k)) return false;
         c.narrow = k == 0;
+    } else if (name == "CAPSMI_PRESENCE") {
+        if (!parse_choice(v, {"auto", "off"}, k)) return false;
+        c.presence = k == 0;
     } else if (name == "CAPSMI_STR_MATCH") {
         if (!parse_choice(v, {"auto", "rows", "dict"}, k)) return false;
         c.str_match = k;
@@ -558,7 +561,8 @@ const std::pair<const char*, const char*> kKnobs[] = {
     {"CAPSMI_UND", "part"},          {"CAPSMI_VL_BITS", "8"},        {"CAPSMI_VL_SUBLOG", "-1"},
     {"CAPSMI_VL_F2", "0"},           {"CAPSMI_COLL_CHUNK", "67108864"}, {"CAPSMI_INGEST_THREADS", "0"},
     {"CAPSMI_HOP2", "auto"},         {"CAPSMI_POOL", "split"},       {"CAPSMI_STR_MATCH", "auto"},
-    {"CAPSMI_HOP2_EXCHANGE", "on"},  {"CAPSMI_NARROW", "auto"},      {"CAPSMI_TRI_UND_COUNT", "hash"}};
+    {"CAPSMI_HOP2_EXCHANGE", "on"},  {"CAPSMI_NARROW", "auto"},      {"CAPSMI_TRI_UND_COUNT", "hash"},
+    {"CAPSMI_PRESENCE", "auto"}};
 }  // namespace
 
 Config config_from_env() {
@@ -1885,15 +1889,17 @@ static void build_part(capsmi_session* s, int32_t nrels, capsmi_table* const* re
     std::vector<const int64_t*> srcs, dsts;
     std::vector<int64_t> ms;
     std::vector<NarrowRel> nar;  // pass 1 reads a table's 32-bit endpoint copies where it carries them
+    std::vector<PresenceRel> pres;  // hop 1 for a full a reads the tables' presence words where all offer them
     for (int i = 0; i < nrels; ++i) {
         need(rels[i], "rels[i]");
         M(rels[i]);
         srcs.push_back(rel_col(rels[i], src_col).d());
         dsts.push_back(rel_col(rels[i], dst_col).d());
         nar.push_back(narrow_rel(s, rel_col(rels[i], src_col), rel_col(rels[i], dst_col)));
+        pres.push_back(presence_rel(s, rel_col(rels[i], src_col), rel_col(rels[i], dst_col), rels[i]->nrows));
         ms.push_back(rels[i]->nrows);
     }
-    relpart_build(s, srcs.data(), dsts.data(), ms.data(), nrels, lo, hi, rp, h1, false, nar.data());
+    relpart_build(s, srcs.data(), dsts.data(), ms.data(), nrels, lo, hi, rp, h1, false, nar.data(), pres.data());
 }
 
 // hop 1 on a partitioned layout into X1 (= M | S1) and X2 (= M | S2); S1 scratch

@@ -73,6 +73,22 @@ struct StrStore {
 };
 inline bool is_str_match(int32_t op) { return op >= CAPSMI_X_STARTS_WITH && op <= CAPSMI_X_CONTAINS; }
 
+// Endpoint presence words of a registered relationship table (presence_endpoints, plan.hip; the rule:
+// presence_rule.h): four bitmaps over the endpoints' window [lo, hi), bit k of word 0 standing for id lo + k.
+// Facts about the immutable table which no query shapes; hop 1 of a 2-hop whose first node is unfiltered reads
+// them instead of the relationships (k_presence_hop1, k_part.hip).
+struct PresenceWords {
+    Buf in;     // ids that are the target of a relationship with source != target
+    Buf out;    // ids that are the source of one
+    Buf loop1;  // ids with at least one self-loop
+    Buf loop2;  // ids with at least two
+    int64_t lo = 0, hi = 0, nwords = 0;
+    // what they were made from: the two columns' data blocks and row offsets, and the row count
+    const DevBuf* src_of = nullptr;
+    const DevBuf* dst_of = nullptr;
+    int64_t src_off = 0, dst_off = 0, rows = 0;
+};
+
 struct Column {
     std::string name;
     int32_t type = CAPSMI_I64;
@@ -91,6 +107,10 @@ struct Column {
     Buf narrow;
     const DevBuf* narrow_of = nullptr;
     int64_t narrow_base = 0;
+    // optional presence words of the relationship table this endpoint column was registered with, shared by both
+    // endpoint columns and carried along like `narrow`; presence_rel (plan.hip) decides whether a pair of columns
+    // may still read them
+    std::shared_ptr<const PresenceWords> presence;
     const int64_t* d() const { return P<int64_t>(data) + offset; }
     const uint32_t* n32() const { return narrow && narrow_of == data.get() ? P<uint32_t>(narrow) + offset : nullptr; }
     const uint8_t* v() const { return valid ? P<uint8_t>(valid) + offset : nullptr; }
@@ -176,6 +196,11 @@ struct Config {
     bool narrow = true;           // CAPSMI_NARROW = auto | off: registering a relationship table whose endpoints span at most
                                   //   2^32 ids keeps a 32-bit copy of both endpoint columns (8 B per relationship of device
                                   //   memory), which pass 1 of the chunk partition reads instead of the int64 words; off
+                                  //   builds none and reads none
+    bool presence = true;         // CAPSMI_PRESENCE = auto | off: registering a relationship table whose endpoints span at
+                                  //   most 2^26 ids keeps four presence bitmaps over the window (non-loop targets, non-loop
+                                  //   sources, ids with one / two self-loops: 4 bits per id), from which hop 1 of a 2-hop
+                                  //   with an unfiltered first node is answered without reading the relationships; off
                                   //   builds none and reads none
     int str_match = 0;            // CAPSMI_STR_MATCH = auto | rows | dict (0..2): which side a string match with a constant
                                   //   pattern runs on -- once per row, or once per entry of the string store with a
@@ -585,6 +610,20 @@ struct NarrowRel {
 };
 // the narrow form of (source column sc, target column dc) if both carry one with one base and the knob allows
 NarrowRel narrow_rel(const capsmi_session* s, const Column& sc, const Column& dc);
+// One table's presence words as hop 1 reads them (PresenceWords): m = the to-column's side (`in` when the walk
+// follows the relationships, `out` when it runs against them), l1 / l2 = the loop words, over the window [lo, hi).
+// m == nullptr: the table offers none.
+struct PresenceRel {
+    const uint32_t* m = nullptr;
+    const uint32_t* l1 = nullptr;
+    const uint32_t* l2 = nullptr;
+    int64_t lo = 0, hi = 0, nwords = 0;
+    std::shared_ptr<const PresenceWords> keep;  // the words' owner (a handle that stores the PresenceRel keeps them alive)
+};
+// the words that the walk from column `from` to column `to` over `rows` rows may read: the to-column offers them
+// when both columns' data blocks, both row offsets and the row count are the ones they were made with, and the
+// knob allows
+PresenceRel presence_rel(const capsmi_session* s, const Column& from, const Column& to, int64_t rows);
 struct RelPart {
     PartLayout L;
     // The build has two stages.  Stage 1 (pass 1) leaves the chunk partition `cp`: pairs grouped by target
@@ -602,6 +641,9 @@ struct RelPart {
     Buf boff;   // int64 cell offsets (ncells + 1); boff[ncells] = kept
     int64_t kept = 0;  // -1: on the device only (relpart_kept reads it)
     int64_t rows = 0;  // relationships offered to the build (>= kept)
+    // the presence words of the tables with rows, when every one of them offers words usable over L's domain
+    // (else empty): relpart_hop1 with a full a reads them instead of the cells
+    std::vector<PresenceRel> pres;
 };
 int64_t relpart_kept(capsmi_session* s, RelPart& rp);
 void relpart_digest(capsmi_session* s, RelPart& rp, int64_t* counts, uint64_t* sums, int64_t* misplaced);
@@ -614,9 +656,11 @@ struct RelPartHop1 {
 };
 // unpacked: keep 8-byte pairs whatever the domain (a layout walked by kernels that read uint2 pairs only)
 // nar: per table its 32-bit endpoint form (NarrowRel; null: none has one)
+// pres: per table its presence words (PresenceRel; null: none has any).  Where every table with rows offers words
+// usable over [lo, hi), a pool hop 1 is answered from them (k_presence_hop1) and the handle keeps them.
 void relpart_build(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms, int nt,
                    int64_t lo, int64_t hi, RelPart& rp, const RelPartHop1* h1 = nullptr, bool unpacked = false,
-                   const NarrowRel* nar = nullptr);
+                   const NarrowRel* nar = nullptr, const PresenceRel* pres = nullptr);
 // stage 2 of the build on a handle that kept its pool (no-op when the cells are there)
 void relpart_cells(capsmi_session* s, RelPart& rp);
 void relpart_hop1(capsmi_session* s, RelPart& rp, const capsmi_bitmap* a, const capsmi_bitmap* b, uint32_t* M,

@@ -22,6 +22,7 @@
 #include <map>
 #include <mutex>
 #include "part_common.h"
+#include "presence_rule.h"
 
 namespace capsmi {
 
@@ -1245,6 +1246,45 @@ __global__ void __launch_bounds__(kPoolBlock) k_pool_hop1(ChunkWalk cw, BitV tma
     }
 }
 
+// Hop 1 for a full a_ok from the tables' presence words (PresenceWords, capsmi_impl.h): what k_pool_hop1 derives
+// from the pool -- M(t) = some relationship s -> t with s != t, S1 / S2 = one / two self-loops at t over all the
+// tables -- is a fact about the tables, kept since their registration.  One thread per word of the domain: the
+// tables' words are shifted to the domain (presence_word), masked with b_ok and ORed into M, S1, S2.  A second
+// loop at an id is one table's loop2 bit or the loop1 bits of two list entries (a table listed twice counts twice).
+constexpr int kPresenceMax = 8;  // tables per launch (more: hop 1 walks the pool)
+struct PresenceIn {
+    const uint32_t* m[kPresenceMax];
+    const uint32_t* l1[kPresenceMax];
+    const uint32_t* l2[kPresenceMax];
+    int64_t nwords[kPresenceMax];
+    int64_t shift[kPresenceMax];  // the table's window low end - the domain's (>= 0: presence_usable)
+    int n;
+};
+__global__ void __launch_bounds__(256) k_presence_hop1(PresenceIn in, BitV tmask, uint32_t* __restrict__ M,
+                                                       uint32_t* __restrict__ S1, uint32_t* __restrict__ S2,
+                                                       int64_t gwords) {
+    const int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (w >= gwords) return;
+    uint32_t m = 0, l1 = 0, l2 = 0;
+#pragma unroll
+    for (int i = 0; i < kPresenceMax; ++i) {  // unrolled: the argument arrays are read at constant offsets
+        if (i >= in.n) break;
+        m |= presence_word(in.m[i], in.nwords[i], in.shift[i], w);
+        const uint32_t a = presence_word(in.l1[i], in.nwords[i], in.shift[i], w);
+        l2 |= presence_word(in.l2[i], in.nwords[i], in.shift[i], w) | (l1 & a);
+        l1 |= a;
+    }
+    if (!tmask.full) {
+        const uint32_t b = tmask.w[w];
+        m &= b;
+        l1 &= b;
+        l2 &= b;
+    }
+    if (m) M[w] |= m;
+    if (l1) S1[w] |= l1;
+    if (l2) S2[w] |= l2;
+}
+
 // Hop 2: C(t) |= X1(s) for s != t, X2(s) for s == t, with the C slice in LDS.  A pair whose target bit is
 // already set needs no X read (the result is an OR, so skipping is exact in any order); targets outside c_ok
 // are preset so their pairs skip too, and the flush masks them off again.  A lane tests its step's targets
@@ -1635,10 +1675,45 @@ static bool pool_domain(const part::Layout& L) { return L.sbits == part::kSliceB
 
 static void cells_build(capsmi_session* s, RelPart& rp, const RelPartHop1* h1);
 
+// hop 1 for a full a from the presence words rp.pres (one launch over the domain's words)
+static void presence_hop1(capsmi_session* s, const RelPart& rp, const capsmi_bitmap* b, uint32_t* M, uint32_t* S1,
+                          uint32_t* S2) {
+    using namespace part;
+    PresenceIn in{};
+    in.n = (int)rp.pres.size();
+    double bytes = 16.0 * (double)b->nwords;  // b_ok read, M, S1, S2 written
+    for (int i = 0; i < in.n; ++i) {
+        const PresenceRel& p = rp.pres[i];
+        in.m[i] = p.m;
+        in.l1[i] = p.l1;
+        in.l2[i] = p.l2;
+        in.nwords[i] = p.nwords;
+        in.shift[i] = p.lo - rp.L.lo;
+        bytes += 12.0 * (double)p.nwords;
+    }
+    KernelTimer kt(s, "hop1", bytes);
+    hipLaunchKernelGGL(k_presence_hop1, dim3((unsigned)((b->nwords + 255) / 256)), dim3(256), 0, s->stream, in,
+                       BitV{P<uint32_t>(b->words), b->full ? 1 : 0}, M, S1, S2, b->nwords);
+    HIP_CHECK(hipGetLastError());
+    s->routes["hop1_presence"] += 1;
+}
+
 void relpart_build(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms, int nt,
-                   int64_t lo, int64_t hi, RelPart& rp, const RelPartHop1* h1, bool unpacked, const NarrowRel* nar) {
+                   int64_t lo, int64_t hi, RelPart& rp, const RelPartHop1* h1, bool unpacked, const NarrowRel* nar,
+                   const PresenceRel* pres) {
     REQUIRE(hi > lo && (uint64_t)(hi - lo) <= (uint64_t(1) << 30), CAPSMI_ERR_UNSUPPORTED,
             "partitioned layout needs an id domain of at most 2^30 ids");
+    // the presence words, if every table with rows offers some that the domain may read (presence_rule.h)
+    rp.pres.clear();
+    if (pres && s->cfg.presence) {
+        bool all = true;
+        for (int i = 0; i < nt && all; ++i) {
+            if (ms[i] <= 0) continue;
+            all = pres[i].m && presence_usable(pres[i].lo, pres[i].hi, lo, hi) && (int)rp.pres.size() < part::kPresenceMax;
+            if (all) rp.pres.push_back(pres[i]);
+        }
+        if (!all) rp.pres.clear();
+    }
     using namespace part;
     hipStream_t st = s->stream;
     rp.L = make_layout(lo, hi, s->cfg.pairs != 2);  // config CAPSMI_PAIRS=uint2: 8-byte pairs
@@ -1672,6 +1747,10 @@ void relpart_build(capsmi_session* s, const int64_t* const* srcs, const int64_t*
     rp.sel = -1;
     rp.kept = -1;  // known on the device (boff[ncells]); read only when asked (relpart_kept)
     rp.rows = cp.mtot;
+    if (pool_hop && !rp.pres.empty()) {
+        presence_hop1(s, rp, h1->b, h1->M, h1->S1, h1->S2);
+        return;
+    }
     if (pool_hop) {
         const size_t lds = sizeof(uint32_t) * kSliceWords;
         auto k = cp.split ? k_pool_hop1<true> : k_pool_hop1<false>;
@@ -1777,6 +1856,7 @@ void relpart_hop1(capsmi_session* s, RelPart& rp, const capsmi_bitmap* a, const 
     if (rp.rows == 0) return;
     relpart_cells(s, rp);
     const part::BitV av{P<uint32_t>(a->words), a->full ? 1 : 0}, bv{P<uint32_t>(b->words), b->full ? 1 : 0};
+    if (a->full && !rp.pres.empty() && s->cfg.presence) return presence_hop1(s, rp, b, M, S1, S2);
     KernelTimer kt(s, "hop1");
     if (a->full)
         launch_hop<true, true>(s, rp, av, nullptr, bv, M, S1, S2, b->nwords);

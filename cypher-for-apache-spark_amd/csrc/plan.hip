@@ -30,6 +30,7 @@
 
 #include "capsmi_impl.h"
 #include "narrow_rule.h"
+#include "presence_rule.h"
 
 namespace capsmi {
 
@@ -2067,6 +2068,108 @@ NarrowRel narrow_rel(const capsmi_session* s, const Column& sc, const Column& dc
     return r;
 }
 
+PresenceRel presence_rel(const capsmi_session* s, const Column& from, const Column& to, int64_t rows) {
+    PresenceRel r;
+    const std::shared_ptr<const PresenceWords>& w = to.presence;
+    if (!s->cfg.presence || !w || rows != w->rows) return r;
+    const DevBuf *f = from.data.get(), *t = to.data.get();
+    const bool with = t == w->dst_of && f == w->src_of && to.offset == w->dst_off && from.offset == w->src_off;
+    const bool against = t == w->src_of && f == w->dst_of && to.offset == w->src_off && from.offset == w->dst_off;
+    if (!with && !against) return r;
+    r.m = P<uint32_t>(with ? w->in : w->out);
+    r.l1 = P<uint32_t>(w->loop1);
+    r.l2 = P<uint32_t>(w->loop2);
+    r.lo = w->lo;
+    r.hi = w->hi;
+    r.nwords = w->nwords;
+    r.keep = w;
+    return r;
+}
+
+// The presence words of a registered relationship table's endpoints (Column::presence; the rule: presence_rule.h).
+// Like the 32-bit copies a fact about the immutable table, which no query shapes: made once, here, by the 2-hop's
+// own build -- relpart_build with hop 1 over a full bitmap of the window leaves M = `in`, S1 = `loop1`, S2 =
+// `loop2`, and the same with the columns swapped leaves `out` -- so whatever path that build takes, the words are
+// what hop 1 would have computed.  Costs two builds at registration (transient: the pass-1 pool) and 4 bits per
+// id of the window.  Two endpoint columns that already carry words valid for each other (a second registration
+// of the same columns) reuse them.  CAPSMI_PRESENCE=off: none.
+static void presence_endpoints(capsmi_table* t, const EntityInfo& e) {
+    if (e.kind != 2 || !t->sess || !t->sess->cfg.presence || t->lazy()) return;
+    Column& sc = t->cols[e.src];
+    Column& dc = t->cols[e.dst];
+    if (sc.type != CAPSMI_I64 || dc.type != CAPSMI_I64 || sc.lazy_nullable || dc.lazy_nullable) return;
+    if (!presence_eligible(sc.valid != nullptr, dc.valid != nullptr, t->nrows, e.lo, e.hi)) return;
+    if (sc.data.get() == dc.data.get()) return;  // one block on both sides: the sides could not be told apart
+    capsmi_session* s = t->sess;
+    if (presence_rel(s, sc, dc, t->nrows).m) {
+        s->routes["presence_reused"] += 1;
+        return;
+    }
+    HIP_CHECK(hipSetDevice(s->device));
+    hipStream_t st = s->stream;
+    auto w = std::make_shared<PresenceWords>();
+    w->lo = e.lo;
+    w->hi = e.hi;
+    w->nwords = (int64_t)(((uint64_t)e.hi - (uint64_t)e.lo + 31) / 32);
+    w->src_of = sc.data.get();
+    w->dst_of = dc.data.get();
+    w->src_off = sc.offset;
+    w->dst_off = dc.offset;
+    w->rows = t->nrows;
+    // the build is no routed query: its route counts and kernel timers stay out of the session's, which get one
+    // `presence_build` timer and one `presence_built` count instead
+    struct Quiet {
+        capsmi_session* s;
+        std::map<std::string, int64_t> routes;
+        bool prof;
+        ~Quiet() {
+            s->routes = std::move(routes);
+            s->prof = prof;
+        }
+    };
+    try {
+        const size_t bytes = sizeof(uint32_t) * (size_t)w->nwords;
+        w->in = dev_alloc(bytes, s);
+        w->out = dev_alloc(bytes, s);
+        w->loop1 = dev_alloc(bytes, s);
+        w->loop2 = dev_alloc(bytes, s);
+        Buf spare = dev_alloc(2 * bytes, s);  // the swapped build's loop words: the same as the first's
+        capsmi_bitmap all;
+        all.sess = s;
+        all.lo = e.lo;
+        all.hi = e.hi;
+        all.nwords = w->nwords;
+        all.words = dev_alloc(bytes, s);
+        all.set_bits = (int64_t)((uint64_t)e.hi - (uint64_t)e.lo);
+        all.full = true;
+        for (const Buf* b : {&w->in, &w->out, &w->loop1, &w->loop2}) HIP_CHECK(hipMemsetAsync(P<void>(*b), 0, bytes, st));
+        HIP_CHECK(hipMemsetAsync(P<void>(spare), 0, 2 * bytes, st));
+        HIP_CHECK(hipMemsetAsync(P<void>(all.words), 0xFF, bytes, st));
+        KernelTimer kt(s, "presence_build");
+        Quiet q{s, s->routes, s->prof};
+        s->prof = false;
+        const NarrowRel n = narrow_rel(s, sc, dc);
+        for (int side = 0; side < 2; ++side) {
+            const int64_t* from = side ? dc.d() : sc.d();
+            const int64_t* to = side ? sc.d() : dc.d();
+            NarrowRel ns = n;
+            if (side) std::swap(ns.s, ns.d);
+            const RelPartHop1 h1{&all, &all, P<uint32_t>(side ? w->out : w->in),
+                                 side ? P<uint32_t>(spare) : P<uint32_t>(w->loop1),
+                                 side ? P<uint32_t>(spare) + w->nwords : P<uint32_t>(w->loop2)};
+            RelPart rp;  // the pool goes back to the allocator at the end of each round
+            relpart_build(s, &from, &to, &t->nrows, 1, e.lo, e.hi, rp, &h1, false, &ns);
+        }
+    } catch (const Error& x) {
+        // the words are optional, as the copies are: a table that leaves no room for the transient pool is
+        // registered without (hop 1 then walks the pool, and presence_built does not count it)
+        if (x.code != CAPSMI_ERR_OUT_OF_MEMORY) throw;
+        return;
+    }
+    sc.presence = dc.presence = w;
+    s->routes["presence_built"] += 1;
+}
+
 void attach_entity(capsmi_table* t, int kind, int64_t lo, int64_t hi, bool ids_exact, bool ids_unique) {
     auto e = std::make_shared<EntityInfo>();
     e->kind = kind;
@@ -2082,6 +2185,7 @@ void attach_entity(capsmi_table* t, int kind, int64_t lo, int64_t hi, bool ids_e
     e->ids_unique = ids_exact || ids_unique;
     t->entity = e;
     narrow_endpoints(t, *e);
+    presence_endpoints(t, *e);
 }
 
 // ============================ operator-by-operator execution, pruned ========================
@@ -3205,6 +3309,7 @@ static capsmi_table* register_entity(capsmi_table* t, int kind, const std::vecto
     o->entity = e;
     try {
         narrow_endpoints(o, *e);
+        presence_endpoints(o, *e);
     } catch (...) {
         delete o;
         throw;

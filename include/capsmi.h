@@ -513,7 +513,18 @@ capsmi_status capsmi_table_column_device_ptr(const capsmi_table* t, int32_t col,
  * the result (select, rename, skip, limit, cache).  The partitioned 2-hop and var-length entry points read the
  * copies in their first pass instead of the Long columns; results are the same.  CAPSMI_NARROW=off at
  * registration keeps none; off at a query reads none.  Route counts (capsmi_session_route_count):
- * "narrow_built" per table that got copies, "pass1_narrow" per first-pass launch that read them. */
+ * "narrow_built" per table that got copies, "pass1_narrow" per first-pass launch that read them.
+ * capsmi_rel_table likewise keeps endpoint presence words when the table has rows and its endpoints span at most
+ * 2^26 ids: four bitmaps over the endpoints' window (ids that are the target / the source of a relationship that
+ * is no self-loop, ids with at least one / two self-loops).  They cost two runs of the partition's first pass and
+ * first hop at registration (about 8 ms for 2^30 relationships on MI355X, with a transient pool of 8 bytes per
+ * relationship) and 4 bits of device memory per id of the window, and are shared like the copies.  The first hop
+ * of a 2-hop whose first node is unfiltered over the query's id domain is answered from them without reading the
+ * relationships, when every table of the walk offers words for exactly the rows it is walked with (a view behind
+ * a later skip or limit, or with a replaced endpoint column, offers none) and the tables' windows lie inside the
+ * domain; results are the same.  A registration of endpoint columns that already carry words valid for each other
+ * reuses them.  CAPSMI_PRESENCE=off at registration keeps none; off at a query reads none.  Route counts:
+ * "presence_built" / "presence_reused" per registration, "hop1_presence" per first hop answered from words. */
 capsmi_status capsmi_node_table(capsmi_table* t, const char* id_col, int32_t nlabels, const char* const* label_cols,
                                 capsmi_table** out);
 capsmi_status capsmi_rel_table(capsmi_table* t, const char* id_col, const char* src_col, const char* dst_col,
