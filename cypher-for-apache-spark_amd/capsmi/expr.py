@@ -40,6 +40,9 @@ capsmi_session_set_string_sink).  ``BinOp("+")`` compiles to the concatenation w
 the tree itself -- a String literal, a ToString, a Concat, a RelType, or a ``+`` over one; over a String column the
 front end builds ``Concat``, as it picks ``StrSize`` for ``Size``.  Double operands are not implemented.
 
+MonotonicallyIncreasingId (:189) is the row's index (include/capsmi.h, CAPSMI_X_ROW_ID): the one expression the
+planner emits that is not a function of the row's values.
+
 ``compile_program`` lowers a tree to the postfix ``capsmi_expr`` program of include/capsmi.h.
 """
 from __future__ import annotations
@@ -71,6 +74,8 @@ STRING_CONV_OPS = (X_STR_SIZE, X_STR_TO_INTEGER, X_STR_TO_FLOAT, X_TO_BOOLEAN)
 # 60..63 are unassigned; the functions that make a String: their codes come from the session's string sink
 X_TO_STRING, X_CONCAT = 64, 65
 STRING_MAKE_OPS = (X_TO_STRING, X_CONCAT)
+# 66..67 are unassigned; the row's index: legal only in a withColumns program, whose plan node it pins
+X_ROW_ID = 68
 STRING_STORE_OPS = STRING_MATCH_OPS + STRING_CONV_OPS  # the opcodes that read a String's bytes
 # a program that holds one needs Session.sync_strings(): the makers read STR operands from the store and merge into it
 STRING_SYNC_OPS = STRING_STORE_OPS + STRING_MAKE_OPS
@@ -406,6 +411,15 @@ class Concat(Expr):
     right: Expr
 
 
+@dataclass(frozen=True, eq=False)
+class MonotonicallyIncreasingId(Expr):
+    """MonotonicallyIncreasingId() (SparkSQLExprMapper.scala:189, ``functions.monotonically_increasing_id()``): the
+    0-based index of the row in the table the ``withColumns`` reads, Spark's value for a single partition -- what
+    ``ConstructGraphPlanner.generateId`` builds the ids of created entities from (include/capsmi.h, CAPSMI_X_ROW_ID).
+    A Long, never NULL.  Legal only in ``withColumns``; the plan node is pinned: computed whole and once, no filter
+    pushed below it, its rows kept for every later reader."""
+
+
 def is_string_typed(e: Expr) -> bool:
     """Whether the tree itself types ``e`` as a String (a column's type is the front end's to know)."""
     if isinstance(e, Lit):
@@ -597,6 +611,8 @@ def compile_program(e: Expr, column_index: Callable[[str], int], encode_str: Cal
                 out.append((X_LIT, 0, ty, _lit_bits(x.value, ty, encode_str)))
         elif isinstance(x, Param):
             out.append((X_PARAM, x.index, 0, 0))
+        elif isinstance(x, MonotonicallyIncreasingId):
+            out.append((X_ROW_ID, 0, 0, 0))
         elif isinstance(x, BinOp):
             go(x.left)
             go(x.right)

@@ -14,6 +14,7 @@ Followed code (okapi-relational/src/main/scala/org/opencypher/okapi/relational/i
   - scans             RelationalPlanner.planScan :220-238, ScanGraph.scanOperator (impl/graph/ScanGraph.scala:61-96)
   - choice of operator okapi-logical/.../LogicalPlanner.scala:474-526 (bound target -> ExpandInto,
                       cyclic (a)--(a) -> directed ExpandInto :509-514)
+  - CONSTRUCT         ConstructGraphPlanner.scala:52-272, SingleTableGraph.scala:49-106 (capsmi/construct.py)
   - uniqueness        front-end rewrite (CypherParser.scala:64-76): NOT(r_i = r_j) for every pair of
                       single-length relationship variables of one MATCH whose type sets may overlap
 Column naming: node var v -> "v" (id), "v:Label" (Boolean), "v.key"; rel var r -> "r" (id),
@@ -319,16 +320,70 @@ class UnionGraph:
                     EntityTable(et.kind, et.labels, et.props, tab, et.id_col, et.src_col, et.dst_col))
         return nodes, rels
 
+    def to_scan_graph(self) -> ScanGraph:
+        """The graph stored: entity tables materialised, registered and compacted (capsmi.construct.to_scan_graph)."""
+        from .construct import to_scan_graph
+        return to_scan_graph(self)
+
     def _flat(self) -> ScanGraph:
         nodes, rels = self.entity_tables()
         return ScanGraph(self.backend, nodes, rels, self.tags)
 
+    def has_pattern(self) -> bool:
+        """Whether a member, at any depth, is a constructed pattern graph: such a member is scanned through its own
+        scanOperator, not through entity tables."""
+        return any(getattr(g, "has_pattern", lambda: False)() for g, _ in self.members)
+
     def node_scan(self, var: str, labels: Sequence[str]):
+        if self.has_pattern():
+            return self._member_scans(False, var, labels)
         out, header = self._flat().node_scan(var, labels)
         return out.distinct(*header), header
 
     def rel_scan(self, var: str, types: Sequence[str]):
+        if self.has_pattern():
+            return self._member_scans(True, var, types)
         out, header = self._flat().rel_scan(var, types)
+        return out.distinct(*header), header
+
+    def _member_scans(self, is_rel: bool, var: str, arg: Sequence[str]):
+        """UnionGraph.scanOperator as the reference writes it (UnionGraph.scala:63-79): every member's own scan, its id
+        columns retagged, aligned to the union of the members' headers (a label a member lacks is FALSE, a property it
+        lacks NULL), union'ed and made distinct on the scanned entity."""
+        from .construct import _aligned
+        from .tagging import expr_replace_tags
+        scans = []
+        for g, rep in self.members:
+            t, h = g.node_scan(var, arg) if not is_rel else g.rel_scan(var, arg)
+            scans.append((t, h, {f: to for f, to in rep.items() if f != to}, rep))
+        keys = [var, f"{var}.__src", f"{var}.__dst"] if is_rel else [var]
+        fixed = keys + ([f"{var}.__type"] if is_rel else [])
+        labels = sorted({c for _, h, _, _ in scans for c in h if c.startswith(f"{var}:")})
+        props: Dict[str, int] = {}
+        for t, h, _, _ in scans:
+            types = t.columnType
+            for c in h:
+                if c not in fixed and not c.startswith(f"{var}:"):
+                    if c in props and props[c] != types[c]:
+                        raise PlanningError(f"property '{c}' has conflicting types across the union's members")
+                    props[c] = types[c]
+        header = fixed + labels + sorted(props)
+        out = None
+        for t, h, moves, rep in scans:
+            cols = []
+            for c in header:
+                if c in keys and moves:
+                    cols.append((expr_replace_tags(Col(c), rep), c))
+                elif c in h:
+                    cols.append((Col(c), c))
+                elif c in labels:
+                    cols.append((Lit(False), c))
+                elif props[c] >= LIST:
+                    raise PlanningError(f"list property '{c}' is missing in a member of a union with a constructed graph")
+                else:
+                    cols.append((Lit(None, props[c]), c))
+            part = _aligned(t, cols, header)
+            out = part if out is None else out.unionAll(part)
         return out.distinct(*header), header
 
 
@@ -539,12 +594,19 @@ class _Op:
         self.node_vars = node_vars
         self.rel_vars = rel_vars      # relationship id columns in the header (incl. var-length hops)
         self.null_cols = set(null_cols)  # value columns that are a missing property (a null of no type)
+        self.graph_of: Dict[str, object] = {}  # entity variable -> the graph it was matched from (Planner.run)
 
 
 class Planner:
-    def __init__(self, graph: ScanGraph):
+    def __init__(self, graph: ScanGraph, catalog: Optional[Dict[str, object]] = None):
+        """``catalog`` names the graphs FROM GRAPH and CONSTRUCT ON may refer to; constructed graphs join it."""
         self.g = graph
         self.names = _Names()
+        self.catalog: Dict[object, object] = dict(catalog or {})
+        self.graph_name = next((k for k, v in self.catalog.items() if v is graph), "session.ambient")
+        self.catalog.setdefault(self.graph_name, graph)
+        self.tag_strategies: List[Dict[object, Dict[int, int]]] = []  # constructTagStrategy per construct clause
+        self.pattern_graphs: List[object] = []  # the PatternGraph of each construct clause
 
     # ---- query ------------------------------------------------------------------------------
     def run(self, query: dict):
@@ -553,9 +615,14 @@ class Planner:
         ``{"unwind": spec, "as": name}`` with spec ``["listlit", [...]]``, ``["param", name]`` (a list of the
         query's ``"params"`` map), ``["var", column]``, ``["prop", var, key]``, ``["range", from, to, step?]``, ``["labels", var]`` or
         ``["keys", var]``, and
-        ``{"with": {"items": ...}, "where": expr?}`` (the items of a RETURN)."""
+        ``{"with": {"items": ...}, "where": expr?}`` (the items of a RETURN),
+        ``{"from_graph": name}`` (later MATCHes scan that graph of the catalog; earlier bindings stay) and
+        ``{"construct": {...}}`` (capsmi.construct; afterwards the working graph is the constructed one and the
+        bindings start over, as the reference's ConstructGraph then Start).  ``"return": "graph"`` returns
+        (the working graph, []): RETURN GRAPH has no records."""
         cur: Optional[_Op] = None
         varlen: Dict[str, int] = {}
+        graph_of: Dict[str, object] = {}  # entity variable -> the graph it was matched from (cypherType.graph)
         if query.get("driving"):  # driving table: its columns are value variables (planStartWithDrivingTable)
             d = query["driving"]
             cols = []
@@ -570,6 +637,16 @@ class Planner:
                 cols.append(_column(name, ty, values, dictionary.encode))
             cur = _Op(self.g.backend.table(cols), list(d), set(), [])
         for clause in query["clauses"]:
+            if "from_graph" in clause:
+                if clause["from_graph"] not in self.catalog:
+                    raise PlanningError(f"unknown graph {clause['from_graph']}")
+                self.graph_name = clause["from_graph"]
+                self.g = self.catalog[self.graph_name]
+                continue
+            if "construct" in clause:
+                cur = self._construct(cur, clause["construct"], graph_of)
+                graph_of = {}
+                continue
             if "unwind" in clause:
                 cur = self._unwind(cur, clause["unwind"], clause["as"], query.get("params", {}))
             elif "with" in clause:
@@ -578,9 +655,30 @@ class Planner:
                 cur = self._optional(cur, clause["optional_match"], clause.get("where"), varlen)
             else:
                 cur = self._match(cur, clause["match"], clause.get("where"), varlen)
+            for v in list(cur.node_vars) + list(cur.rel_vars):
+                graph_of.setdefault(v, self.graph_name)
+            cur.graph_of = graph_of
+        if query["return"] == "graph":
+            return self.g, []
         if cur is None:  # no clause (RETURN sqrt(12.96)): one row; RETURN selects its items, so the helper goes
             cur = self._unit()
         return self._return(cur, query["return"], varlen)
+
+    def _construct(self, cur: Optional[_Op], spec: dict, graph_of: Dict[str, object]) -> None:
+        """CONSTRUCT (ConstructGraphPlanner.planConstructGraph, restated in capsmi.construct): over the bindings, or
+        the unit table when there are none.  The constructed graph becomes the working graph and joins the catalog; the
+        construct table is not the input of what follows."""
+        from .construct import plan_construct
+        if cur is None:
+            cur = self._unit()
+        graph, pattern, strategy = plan_construct(self.g.backend, cur.table, cur.header, cur.node_vars, cur.rel_vars, graph_of,
+                                            spec, self.catalog)
+        self.tag_strategies.append(strategy)
+        self.pattern_graphs.append(pattern)
+        self.graph_name = self.names.fresh("constructed")
+        self.catalog[self.graph_name] = graph
+        self.g = graph
+        return None
 
     def _unit(self) -> _Op:
         """The unit table: one row, one helper column."""

@@ -1733,6 +1733,7 @@ capsmi_status capsmi_bitmap_add_scan(capsmi_bitmap* b, capsmi_table* nodes, cons
         nnodes = (int32_t)bound.size();
     }
     if (nnodes > 0) {
+        refuse_row_id(nnodes, pred, "a capsmi_bitmap_add_scan predicate");
         validate_program(nodes, nnodes, pred);
         if (!compile_range_pred(nodes, nnodes, pred, rp)) {  // general predicates: a flag column first
             flags = dev_alloc(nodes->nrows > 0 ? nodes->nrows : 1, s);

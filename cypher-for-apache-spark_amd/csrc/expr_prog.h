@@ -20,7 +20,7 @@ constexpr int kMaxCols = 64;   // columns a program may address
 inline bool is_list_type(int32_t t) { return t >= CAPSMI_LIST_I64 && t <= CAPSMI_LIST_STR; }
 
 // A new opcode of include/capsmi.h gets a row in expr_pops and check_program.  The numbers are not contiguous
-// (32..39, 52..55 and 60..63 are unassigned): an opcode is unknown exactly when expr_pops has no row for it (known_expr_op
+// (32..39, 52..55, 60..63 and 66..67 are unassigned): an opcode is unknown exactly when expr_pops has no row for it (known_expr_op
 // below).
 
 // the numeric block (DIV .. TO_INTEGER): what k_expr.hip's math instantiation adds to the interpreter
@@ -42,11 +42,22 @@ constexpr int32_t str_conv_type(int32_t op) {  // the result's type
 // interpreter runs; the strings get their codes from the session's string sink
 constexpr bool is_str_make(int32_t op) { return op == CAPSMI_X_TO_STRING || op == CAPSMI_X_CONCAT; }
 
+// the row's index (ROW_ID): legal only in a program of capsmi_with_columns, whose plan node it pins (plan.hip)
+inline bool has_row_id(int32_t nn, const capsmi_expr* prog) {
+    for (int i = 0; i < nn; ++i)
+        if (prog[i].op == CAPSMI_X_ROW_ID) return true;
+    return false;
+}
+inline void refuse_row_id(int32_t nn, const capsmi_expr* prog, const char* where) {
+    REQUIRE(!has_row_id(nn, prog), CAPSMI_ERR_ILLEGAL_ARGUMENT,
+            std::string("CAPSMI_X_ROW_ID in ") + where + " (the row index is legal only in a program of capsmi_with_columns)");
+}
+
 // operands an opcode pops: the one arity table (-1: unknown opcode, CAPSMI_X_PARAM included: it is bound before
 // anything counts)
 inline int expr_pops(const capsmi_expr& x) {
     switch (x.op) {
-        case CAPSMI_X_COL: case CAPSMI_X_LIT: case CAPSMI_X_NULL: return 0;
+        case CAPSMI_X_COL: case CAPSMI_X_LIT: case CAPSMI_X_NULL: case CAPSMI_X_ROW_ID: return 0;
         case CAPSMI_X_NOT: case CAPSMI_X_ISNULL: case CAPSMI_X_ISNOTNULL: case CAPSMI_X_NEG: case CAPSMI_X_SIZE:
         case CAPSMI_X_SQRT: case CAPSMI_X_LOG: case CAPSMI_X_LOG10: case CAPSMI_X_EXP: case CAPSMI_X_ABS:
         case CAPSMI_X_CEIL: case CAPSMI_X_FLOOR: case CAPSMI_X_ROUND: case CAPSMI_X_SIGN: case CAPSMI_X_TO_FLOAT:
@@ -111,6 +122,7 @@ inline std::vector<std::pair<int, int>> operand_spans(const capsmi_expr* prog, i
 //     and a mixed entry pass (a row that holds no number yields NULL, as for ADD).
 //   - STR_SIZE, STR_TO_INTEGER, STR_TO_FLOAT and TO_BOOLEAN take a String (or an untyped NULL), TO_BOOLEAN a BOOL
 //     too: any other scalar type and a mixed entry are CAPSMI_ERR_ILLEGAL_ARGUMENT.
+//   - ROW_ID is a Long that takes no operand and no argument.
 //   - TO_STRING takes a Long, a Boolean or a String, CONCAT Strings and Longs of which at least one is a String (an
 //     untyped NULL stands for either): a Double is CAPSMI_ERR_NOT_IMPLEMENTED (Java's Double.toString is not
 //     restated), a Boolean in CONCAT, two Longs and a mixed entry are CAPSMI_ERR_ILLEGAL_ARGUMENT.
@@ -154,6 +166,10 @@ inline int32_t check_program(const int32_t* col_types, int ncols, int32_t nn, co
                 break;
             case CAPSMI_X_LIT: res.t = x.type; break;
             case CAPSMI_X_NULL: res.t = x.arg > 0 ? x.arg - 1 : -1; break;  // arg = 1 + declared type
+            case CAPSMI_X_ROW_ID:
+                REQUIRE(x.arg == 0, CAPSMI_ERR_ILLEGAL_ARGUMENT, "CAPSMI_X_ROW_ID takes no argument (arg must be 0)");
+                res.t = CAPSMI_I64;
+                break;
             case CAPSMI_X_SIZE: case CAPSMI_X_INDEX: case CAPSMI_X_IN_LIST: {
                 const int32_t l = opd[list_at].t;
                 REQUIRE(!opd[list_at].mixed && (x.op != CAPSMI_X_INDEX || !opd[1].mixed), CAPSMI_ERR_ILLEGAL_ARGUMENT, kMixed);

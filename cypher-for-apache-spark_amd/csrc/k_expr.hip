@@ -29,6 +29,8 @@
 //     Spark 2.2.1 Column calls the mapper makes (include/capsmi.h states them per opcode).  Double log and exp are
 //     library code of some size, so these cases exist only in the kMath instantiation of the interpreter, which
 //     launch_eval takes for a program that holds one of them; every other program runs the code it ran before.
+//   - MonotonicallyIncreasingId (:189): CAPSMI_X_ROW_ID pushes the row's index, which the interpreter holds anyway.
+//     Legal only under capsmi_with_columns, whose plan node it pins (plan.hip).
 #include "capsmi_impl.h"
 #include "str_make.h"
 
@@ -139,6 +141,7 @@ __device__ Val eval_row(const capsmi_expr* __restrict__ prog, int nn, const ColP
             }
             case CAPSMI_X_LIT: st[sp++] = Val{x.ival, (int8_t)x.type}; break;
             case CAPSMI_X_NULL: st[sp++] = mk_null(); break;
+            case CAPSMI_X_ROW_ID: st[sp++] = mk_i64(r); break;  // the views of replace_span_and_eval keep the rows
             case CAPSMI_X_EQ: case CAPSMI_X_NEQ: case CAPSMI_X_LT: case CAPSMI_X_LE: case CAPSMI_X_GT: case CAPSMI_X_GE: {
                 const Val b = st[--sp], a = st[--sp];
                 const int c = cmp3(a, b);
@@ -590,8 +593,14 @@ int32_t launch_eval(capsmi_session* s, const capsmi_table* t, int32_t nn, const 
     int64_t g = (n + 255) / 256;
     if (g > 8192) g = 8192;
     bool math = false;  // the instantiation with the numeric block, exactly when the program holds one of its opcodes
-    for (int i = 0; i < nn; ++i) math = math || is_math_op(prog[i].op);
-    KernelTimer kt(s, "expr_eval");  // counts interpreter launches (a scan whose predicate ran inline has none)
+    uint64_t cols_read = 0;  // the timer's algorithmic bytes: each distinct column the program names once (its 8-byte
+                             // words and its validity bytes, whatever the words stand for), the outputs once
+    for (int i = 0; i < nn; ++i) {
+        math = math || is_math_op(prog[i].op);
+        if (prog[i].op == CAPSMI_X_COL) cols_read |= 1ULL << prog[i].arg;  // arg < kMaxCols = 64 (check_program)
+    }
+    const double bytes = (double)n * (9.0 * __builtin_popcountll(cols_read) + (out ? 8 : 0) + (out_valid ? 1 : 0) + (flags ? 1 : 0));
+    KernelTimer kt(s, "expr_eval", bytes);  // counts interpreter launches (a scan whose predicate ran inline has none)
     hipLaunchKernelGGL(math ? k_eval<true> : k_eval<false>, dim3((unsigned)g), dim3(256), 0, s->stream,
                        P<capsmi_expr>(dprog), nn, cp, n, out, out_valid, flags);
     HIP_CHECK(hipGetLastError());

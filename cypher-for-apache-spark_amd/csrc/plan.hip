@@ -143,6 +143,15 @@ int arity(const capsmi_expr& x) {
     return k;
 }
 
+// A WITH_COLUMNS node with a CAPSMI_X_ROW_ID program (include/capsmi.h): Catalyst's nondeterministic expression.
+// The recogniser never takes it into a pattern, and the pruned executor computes it whole, once, in place.
+bool pinned(const capsmi_table* t) {
+    if (!t->lazy() || t->plan->kind != PlanNode::WITH_COLUMNS) return false;
+    for (const auto& prog : t->plan->progs)
+        if (has_row_id((int32_t)prog.size(), prog.data())) return true;
+    return false;
+}
+
 // ============================ operator-by-operator execution ===============================
 capsmi_table* exec_node(const PlanNode& p) {
     capsmi_table* r = nullptr;
@@ -255,7 +264,7 @@ bool as_scan(const capsmi_table* t, Scan& sc) {
     const capsmi_table* in = p.in.empty() ? nullptr : p.in[0];
     switch (p.kind) {
         case PlanNode::WITH_COLUMNS: {
-            if (!as_scan(in, sc)) return false;
+            if (pinned(t) || !as_scan(in, sc)) return false;
             std::vector<std::string> names;
             for (auto& c : in->cols) names.push_back(c.name);
             const std::vector<Member> before = sc.m;  // expressions read the input columns
@@ -484,7 +493,7 @@ bool as_paths_node(const capsmi_table* t, std::vector<Path>& out) {
             return true;
         }
         case PlanNode::WITH_COLUMNS: {
-            if (!as_paths(in, out)) return false;
+            if (pinned(t) || !as_paths(in, out)) return false;  // a row index is no column of a pattern
             for (Path& P : out) {
                 std::vector<Role> cols = P.cols;
                 std::vector<std::string> names;
@@ -2202,6 +2211,10 @@ void attach_entity(capsmi_table* t, int kind, int64_t lo, int64_t hi, bool ids_e
 // columns are matched by name, and put back in schema order where position matters (union inputs,
 // the materialised table).
 // A sub-plan with two parents in the plan DAG is materialised once in place and shared.
+// A WITH_COLUMNS node with a CAPSMI_X_ROW_ID program is pinned (Catalyst keeps a nondeterministic expression where
+// the query put it): it too is materialised in place when first reached, whole -- every column, no conjunct pushed
+// below it, its input planned as usual -- and keeps its rows, so a later reader, in this action or another, sees
+// the ids the first one saw.
 namespace {
 
 using Names = std::vector<std::string>;  // ordered, unique column names
@@ -2513,10 +2526,14 @@ bool expand_with_node_columns(capsmi_table* x, const Names& need, const Parents&
     return true;
 }
 
-Res exec(capsmi_table* t, const Names& need, std::vector<Pred> preds, const Parents& par) {
+Res exec(capsmi_table* t, const Names& need, std::vector<Pred> preds, const Parents& par, bool root = false) {
     if (t->lazy()) {
         auto it = par.find(t);
         if (it != par.end() && it->second > 1) materialize(t);  // shared sub-plan: once, in place
+        // a pinned node (CAPSMI_X_ROW_ID): whole, once, in place -- every column, no conjunct below it, and the rows
+        // stay with `t` for this action's other readers and for later actions.  (As the root of materialize it is
+        // being computed just so: `need` is every column and there are no conjuncts.)
+        else if (!root && pinned(t)) materialize(t);
     }
     if (!t->lazy()) return finish(Res(t, false), need, preds);
     capsmi_table* fr = nullptr;
@@ -2779,7 +2796,7 @@ void materialize(capsmi_table* t) {
     int64_t routed_before = 0;
     for (auto& kv : t->sess->routes) routed_before += kv.first == "miss" ? 0 : kv.second;
     {
-        Res e = exec(t, uniq, {}, par);
+        Res e = exec(t, uniq, {}, par, true);
         auto c = cstrs(all);
         check(eager_select(e.t, (int32_t)c.size(), c.data(), &r));  // schema order, an owned table
         r->partitioned = e.t->partitioned;
@@ -2877,6 +2894,7 @@ capsmi_status capsmi_filter(capsmi_table* t, int32_t nnodes, const capsmi_expr* 
             prog = bound.data();
             nnodes = (int32_t)bound.size();
         }
+        refuse_row_id(nnodes, prog, "a capsmi_filter predicate");
         validate_program(t, nnodes, prog);
         auto p = std::make_shared<PlanNode>();
         p->kind = PlanNode::FILTER;
@@ -2901,6 +2919,9 @@ capsmi_status capsmi_with_columns(capsmi_table* t, int32_t ncols, const capsmi_e
             REQUIRE(cols[i].nnodes == 0 || cols[i].prog, CAPSMI_ERR_ILLEGAL_ARGUMENT, "null program");
             std::vector<capsmi_expr> prog(cols[i].prog, cols[i].prog + cols[i].nnodes);
             if (has_params(cols[i].nnodes, cols[i].prog)) prog = bind_params(t->sess, cols[i].nnodes, cols[i].prog);
+            REQUIRE(t->sess->world <= 1 || !has_row_id((int32_t)prog.size(), prog.data()), CAPSMI_ERR_UNSUPPORTED,
+                    "CAPSMI_X_ROW_ID on a session of " + std::to_string(t->sess->world) +
+                        " ranks: distributed CONSTRUCT is not implemented");
             p->a.push_back(cols[i].name);
             Column c = schema_col(cols[i].name, validate_program(t, (int32_t)prog.size(), prog.data()), true);
             p->progs.push_back(std::move(prog));
@@ -2971,6 +2992,7 @@ capsmi_status capsmi_with_range_column(capsmi_table* t, int32_t from_nnodes, con
             REQUIRE(nn[i] > 0 ? pr[i] != nullptr : i == 2, CAPSMI_ERR_ILLEGAL_ARGUMENT, "range: null or empty operand program");
             std::vector<capsmi_expr> prog(pr[i], pr[i] + nn[i]);
             if (has_params(nn[i], pr[i])) prog = bind_params(t->sess, nn[i], pr[i]);
+            refuse_row_id((int32_t)prog.size(), prog.data(), "a capsmi_with_range_column operand");
             REQUIRE(validate_program(t, (int32_t)prog.size(), prog.data()) == CAPSMI_I64,
                     CAPSMI_ERR_ILLEGAL_ARGUMENT, "range: operands must be Long");
             p->progs.push_back(std::move(prog));

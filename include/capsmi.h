@@ -276,10 +276,32 @@ enum {
                                      negative value, no '+', no padding; Long.MIN_VALUE gives the 20 bytes
                                      "-9223372036854775808".  Of a BOOL: "true" or "false".  Of a STR: the operand
                                      itself (no kernel, no sink call) */
-    CAPSMI_X_CONCAT = 65          /* stack [a, b]: STR, the bytes of a followed by the bytes of b (UTF-8 is not
+    CAPSMI_X_CONCAT = 65,         /* stack [a, b]: STR, the bytes of a followed by the bytes of b (UTF-8 is not
                                      decoded).  Each operand is STR or I64, at least one of them STR or an untyped
                                      NULL in its place; a Long is formatted as TO_STRING does.  A BOOL operand and
                                      I64 + I64 are CAPSMI_ERR_ILLEGAL_ARGUMENT when the node is built */
+    /* 66..67 are unassigned. */
+    /* MonotonicallyIncreasingId (SparkSQLExprMapper.scala:189, functions.monotonically_increasing_id()), the
+       expression ConstructGraphPlanner.generateId builds the ids of created entities from.  The value is the
+       0-based index of the row in the table the operator reads, as that table is materialised: Spark's value for a
+       single partition.  generateId's partition offset and the tag are ordinary ADD / BITAND / BITOR / SHL around
+       it.  It is typed I64, so it may sit under any numeric or comparison opcode of its column's program; the nodes
+       that run as passes of their own (IN_LIST, the string opcodes) keep the table's rows, so a program that holds
+       one of them gives the same ids.
+       Legal only in a program of capsmi_with_columns: in capsmi_filter, capsmi_with_range_column and
+       capsmi_bitmap_add_scan it is CAPSMI_ERR_ILLEGAL_ARGUMENT when the node is built ("CAPSMI_X_ROW_ID ...").
+       Catalyst treats the expression as nondeterministic, and so does the plan executor.  A capsmi_with_columns node
+       with a ROW_ID program is pinned:
+         1. no filter conjunct is pushed below it, even one that reads none of its columns;
+         2. when first needed it is computed whole: all its columns, nothing pruned through it, its input evaluated
+            as usual (fused routes included);
+         3. it keeps its rows from then on, as capsmi_cache does, so every reader sees the same ids, in the same
+            action or a later one;
+         4. it is never matched as part of a fused pattern shape.
+       On a session with more than one rank (capsmi_session_set_ranks) the node is CAPSMI_ERR_UNSUPPORTED when built
+       ("distributed CONSTRUCT is not implemented"): Spark's (partition << 33) + row layout is not restated. */
+    CAPSMI_X_ROW_ID = 68          /* stack []: I64, the row's index, never NULL; arg must be 0
+                                     (CAPSMI_ERR_ILLEGAL_ARGUMENT when the node is built) */
 };
 
 typedef struct {

@@ -92,6 +92,8 @@ object Capsmi {
   // 60..63 are unassigned.  Functions that make a String; the codes come from the session's string sink
   final val X_TO_STRING = 64       // [x]: STR; Long.toString, true / false, a String stays
   final val X_CONCAT = 65          // [a, b]: STR; Strings and Longs, at least one a String
+  // 66..67 are unassigned.  MonotonicallyIncreasingId: legal only in withColumns, whose plan node it pins
+  final val X_ROW_ID = 68          // []: Long, the row's index in the table the operator reads; never NULL
 
   // capsmi_with_mask_list_column: which columns of a row pass
   final val MASK_TRUE = 0     // labels(): the Boolean flag is non-null and TRUE

@@ -385,7 +385,8 @@ final class GpuTable private (val handle: Pointer)(implicit val session: GpuSess
   * are CAPSMI_X_STR_SIZE / STR_TO_FLOAT / STR_TO_INTEGER / TO_BOOLEAN, chosen by the operand's Cypher type as the
   * mapper's own Size chooses; they read the string store too.  ToString (:233) and Add over an operand of type
   * CTString (:160-181) are CAPSMI_X_TO_STRING / CAPSMI_X_CONCAT: the strings are made on the device and coded by
-  * the session's dictionary through the string sink (GpuSession).  Shapes the device path does not evaluate (regular
+  * the session's dictionary through the string sink (GpuSession).  MonotonicallyIncreasingId (:189) is
+  * CAPSMI_X_ROW_ID, the row's index: all that ConstructGraphPlanner needs beyond the table operators.  Shapes the device path does not evaluate (regular
   * expressions, other functions, maps, toString or + over a Double, toBoolean of a number, rand()) raise
   * NotImplementedException or, from the library, IllegalArgumentException.
   */
@@ -497,6 +498,9 @@ final case class ExprCompiler(table: GpuTable, header: RecordHeader, parameters:
     case ToBoolean(x) => go(x, out); out += ((Capsmi.X_TO_BOOLEAN, 0, 0, 0L))
     // cast(StringType), :233: of a Long, a Boolean or a String; the library refuses a Double when the node is built
     case ToString(x) => go(x, out); out += ((Capsmi.X_TO_STRING, 0, 0, 0L))
+    // functions.monotonically_increasing_id(), :189: ConstructGraphPlanner.generateId's row index (one partition);
+    // the library takes it in withColumns only and keeps the node's rows once computed
+    case _: MonotonicallyIncreasingId => out += ((Capsmi.X_ROW_ID, 0, 0, 0L))
     case BitwiseAnd(l, r) => bin(Capsmi.X_BITAND, l, r, out)
     case BitwiseOr(l, r) => bin(Capsmi.X_BITOR, l, r, out)
     case ShiftLeft(v, bits) => bin(Capsmi.X_SHL, v, bits, out)
