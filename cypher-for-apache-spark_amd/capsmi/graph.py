@@ -185,6 +185,27 @@ def var_length_count(session: Session, rels: Sequence[GpuTable], a_ok: NodeBitma
     return GpuTable(session, out)
 
 
+def var_length_count_distinct(session: Session, rels: Sequence[GpuTable], a_ok: NodeBitmap, b_ok: NodeBitmap,
+                              lower: int, upper: int, id_name: str = "id", count_name: str = "count",
+                              src_col: str = "source", dst_col: str = "target") -> GpuTable:
+    """``MATCH (a)-[*lower..upper]->(b) WHERE a_ok(a) AND b_ok(b) RETURN id(a), count(DISTINCT b)``: lower 0 or 1,
+    any upper >= 1 (k-hop reach by bit-parallel BFS; lower >= 2 raises NotImplementedException)."""
+    out = ctypes.c_void_p()
+    _lib.call("capsmi_var_length_count_distinct", session.handle, len(rels), _handles(rels), src_col.encode(),
+              dst_col.encode(), a_ok.handle, b_ok.handle, lower, upper, id_name.encode(), count_name.encode(),
+              ctypes.byref(out))
+    return GpuTable(session, out)
+
+
+def var_length_reach_count(session: Session, rels: Sequence[GpuTable], a_ok: NodeBitmap, b_ok: NodeBitmap,
+                           lower: int, upper: int, src_col: str = "source", dst_col: str = "target") -> int:
+    """``MATCH (a)-[*lower..upper]->(b) WHERE a_ok(a) AND b_ok(b) RETURN count(DISTINCT b)`` (lower 0 or 1)."""
+    out = ctypes.c_int64()
+    _lib.call("capsmi_var_length_reach_count", session.handle, len(rels), _handles(rels), src_col.encode(),
+              dst_col.encode(), a_ok.handle, b_ok.handle, lower, upper, ctypes.byref(out))
+    return out.value
+
+
 class VarlenShard:
     """One rank's share of the var-length grouped count (multi-GPU C5; include/capsmi.h
     capsmi_varlen_shard_*).  The rank owns source ids [own_lo, own_hi); `out_rels` are the

@@ -433,7 +433,7 @@ class Session:
 
     def route_count(self, name: str) -> int:
         """Plans routed to fused entry point `name` ("expand", "expand_count", "two_hop", "triangle",
-        "triangle_grouped", "triangle_transitive", "triangle_transitive_grouped", "triangle_undirected", "triangle_undirected_grouped", "var_length") so far; "miss" counts materialisations where a pattern ran unrouted."""
+        "triangle_grouped", "triangle_transitive", "triangle_transitive_grouped", "triangle_undirected", "triangle_undirected_grouped", "var_length", "var_length_distinct") so far; "miss" counts materialisations where a pattern ran unrouted."""
         v = ctypes.c_int64()
         _lib.call("capsmi_session_route_count", self._h, name.encode(), ctypes.byref(v))
         return v.value

@@ -533,6 +533,12 @@ bool apply(Config& c, const std::string& name, const char* v) {
     } else if (name == "CAPSMI_VL_F2") {
         if (!parse_int(v, 0, 1, x)) return false;
         c.vl_f2 = x != 0;
+    } else if (name == "CAPSMI_REACH_WORDS") {
+        if (!parse_choice(v, {"auto", "1", "2", "4", "8"}, k)) return false;
+        c.reach_words = k == 0 ? 0 : 1 << (k - 1);
+    } else if (name == "CAPSMI_REACH") {
+        if (!parse_choice(v, {"sliced", "flat"}, k)) return false;
+        c.reach_flat = k == 1;
     } else if (name == "CAPSMI_COLL_CHUNK") {
         if (!parse_int(v, 1, int64_t(1) << 40, x)) return false;
         c.coll_chunk = x;
@@ -562,7 +568,7 @@ const std::pair<const char*, const char*> kKnobs[] = {
     {"CAPSMI_VL_F2", "0"},           {"CAPSMI_COLL_CHUNK", "67108864"}, {"CAPSMI_INGEST_THREADS", "0"},
     {"CAPSMI_HOP2", "auto"},         {"CAPSMI_POOL", "split"},       {"CAPSMI_STR_MATCH", "auto"},
     {"CAPSMI_HOP2_EXCHANGE", "on"},  {"CAPSMI_NARROW", "auto"},      {"CAPSMI_TRI_UND_COUNT", "hash"},
-    {"CAPSMI_PRESENCE", "auto"}};
+    {"CAPSMI_PRESENCE", "auto"},     {"CAPSMI_REACH_WORDS", "auto"}, {"CAPSMI_REACH", "sliced"}};
 }  // namespace
 
 Config config_from_env() {
@@ -2111,6 +2117,82 @@ capsmi_status capsmi_var_length_count(capsmi_session* s, int32_t nrels, capsmi_t
     o->cols.push_back(std::move(a));
     o->cols.push_back(std::move(c));
     *out = o;
+    API_END
+}
+
+namespace {
+// the argument checks and relationship views shared by the two count(DISTINCT b) entries
+struct ReachArgs {
+    std::vector<const int64_t*> srcs, dsts;
+    std::vector<int64_t> ms;
+    std::vector<NarrowRel> nar;
+};
+void reach_args(capsmi_session* s, int32_t nrels, capsmi_table* const* rels, const char* src_col, const char* dst_col,
+                const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int32_t lower, int32_t upper, ReachArgs& r) {
+    need(s, "session");
+    check_bitmap(a_ok, "a_ok");
+    check_bitmap(b_ok, "b_ok");
+    REQUIRE(nrels >= 0 && (nrels == 0 || rels), CAPSMI_ERR_ILLEGAL_ARGUMENT, "rels");
+    REQUIRE(lower >= 0 && lower <= upper && upper >= 1, CAPSMI_ERR_ILLEGAL_ARGUMENT,
+            "var-length count(DISTINCT b): 0 <= lower <= upper, upper >= 1");
+    REQUIRE(lower <= 1, CAPSMI_ERR_NOT_IMPLEMENTED,
+            "fused var-length count(DISTINCT b) supports lower 0 or 1: from lower 2 on a walk's end need not end a "
+            "relationship-distinct path (use the join plan)");
+    REQUIRE(a_ok->lo == b_ok->lo && a_ok->hi == b_ok->hi, CAPSMI_ERR_UNSUPPORTED, "a and b scans need one id domain");
+    REQUIRE(!a_ok->any_dup && !b_ok->any_dup, CAPSMI_ERR_UNSUPPORTED,
+            "fused count(DISTINCT b) needs each node id in one scanned row");
+    use_device(s);
+    for (int i = 0; i < nrels; ++i) {
+        need(rels[i], "rels[i]");
+        M(rels[i]);
+        r.srcs.push_back(rel_col(rels[i], src_col).d());
+        r.dsts.push_back(rel_col(rels[i], dst_col).d());
+        r.nar.push_back(narrow_rel(s, rel_col(rels[i], src_col), rel_col(rels[i], dst_col)));
+        r.ms.push_back(rels[i]->nrows);
+    }
+}
+}  // namespace
+
+capsmi_status capsmi_var_length_count_distinct(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                               const char* src_col, const char* dst_col, const capsmi_bitmap* a_ok,
+                                               const capsmi_bitmap* b_ok, int32_t lower, int32_t upper,
+                                               const char* id_name, const char* count_name, capsmi_table** out) {
+    API_BEGIN
+    need(s, "session");
+    need(out, "out");
+    need(id_name, "id_name");
+    need(count_name, "count_name");
+    ReachArgs r;
+    reach_args(s, nrels, rels, src_col, dst_col, a_ok, b_ok, lower, upper, r);
+    REQUIRE(std::string(id_name) != count_name, CAPSMI_ERR_ILLEGAL_ARGUMENT, "output names must differ");
+    Buf ids, cnt;
+    const int64_t rows = var_length_reach_rows(s, r.srcs.data(), r.dsts.data(), r.ms.data(), nrels, a_ok, b_ok, lower,
+                                               upper, ids, cnt, r.nar.data());
+    auto* o = new_table(s, rows);
+    Column a, c;
+    a.name = id_name;
+    a.type = CAPSMI_I64;
+    a.data = ids;
+    c.name = count_name;
+    c.type = CAPSMI_I64;
+    c.data = cnt;
+    o->cols.push_back(std::move(a));
+    o->cols.push_back(std::move(c));
+    *out = o;
+    API_END
+}
+
+capsmi_status capsmi_var_length_reach_count(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                            const char* src_col, const char* dst_col, const capsmi_bitmap* a_ok,
+                                            const capsmi_bitmap* b_ok, int32_t lower, int32_t upper,
+                                            int64_t* out_distinct) {
+    API_BEGIN
+    need(s, "session");
+    need(out_distinct, "out_distinct");
+    ReachArgs r;
+    reach_args(s, nrels, rels, src_col, dst_col, a_ok, b_ok, lower, upper, r);
+    *out_distinct = var_length_reach_count(s, r.srcs.data(), r.dsts.data(), r.ms.data(), nrels, a_ok, b_ok, lower, upper,
+                                           r.nar.data());
     API_END
 }
 

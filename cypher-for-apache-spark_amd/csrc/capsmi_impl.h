@@ -191,6 +191,10 @@ struct Config {
     int vl_bits = 8;              // CAPSMI_VL_BITS: bits per pair of the var-length reverse-pair filter
     int vl_sublog = -1;           // CAPSMI_VL_SUBLOG: filter regions per slice, log2 (-1: auto)
     bool vl_f2 = false;           // CAPSMI_VL_F2 = 1: the second-level filter in the T walk (the sharded form's)
+    int reach_words = 0;          // CAPSMI_REACH_WORDS = auto | 1 | 2 | 4 | 8 (0 = auto): 64-bit words per node of the
+                                  //   grouped var-length count(DISTINCT b), i.e. 64 sources per word and batch (k_reach.hip)
+    bool reach_flat = false;      // CAPSMI_REACH = sliced | flat: flat forces the global-OR level pass (the form of
+                                  //   domains beyond the target-sliced LDS pass)
     int64_t coll_chunk = int64_t(1) << 26;  // CAPSMI_COLL_CHUNK: elements per host collective call
     int ingest_threads = 0;       // CAPSMI_INGEST_THREADS (0: OMP_NUM_THREADS, else up to 16 hardware threads)
     bool narrow = true;           // CAPSMI_NARROW = auto | off: registering a relationship table whose endpoints span at most
@@ -758,6 +762,14 @@ int64_t var_length_count(capsmi_session* s, const int64_t* const* srcs, const in
                          int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower, int upper,
                          Buf& out_ids, Buf& out_cnt, const NarrowRel* nar = nullptr);
 
+// var-length count(DISTINCT b), lower in {0, 1}: k-hop reach by bit-parallel BFS (k_reach.hip).  Rows (a, |D(a)|)
+// of the a_ok nodes with a non-empty D(a) (returns the row count), and |U_a D(a)|.
+int64_t var_length_reach_rows(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
+                              int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower, int upper,
+                              Buf& out_ids, Buf& out_cnt, const NarrowRel* nar = nullptr);
+int64_t var_length_reach_count(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts,
+                               const int64_t* ms, int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower,
+                               int upper, const NarrowRel* nar = nullptr);
 // sharded var-length grouped count (multi-GPU C5; k_varlen.hip): begin -> caller sums od over ranks
 // -> mid -> caller sums Y -> finish (rows of owned ids)
 struct VarlenShard;

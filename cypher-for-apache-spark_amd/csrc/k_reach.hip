@@ -1,0 +1,545 @@
+// k_reach.hip -- count(DISTINCT b) over a bounded var-length expand: k-hop reach by bit-parallel BFS.
+//
+//   MATCH (a)-[r*lower..upper]->(b) WHERE a_ok(a) AND b_ok(b) RETURN id(a), count(DISTINCT b)   (grouped)
+//   MATCH (a)-[r*lower..upper]->(b) WHERE a_ok(a) AND b_ok(b) RETURN count(DISTINCT b)          (global)
+//   lower in {0, 1}, upper >= 1 (a level budget: a frontier dies after at most n levels)
+//
+// Lemma: for lower <= 1, b ends a relationship-distinct path of length in [1, k] from a iff b
+// ends a walk of length in [1, k] from a -- cut the stretch between two uses of a repeated relationship; the
+// walk stays a walk from a to b, gets shorter and keeps one relationship.  So the distinct ends are plain
+// bounded reachability, with none of the uniqueness corrections of the count(*) closed form (k_varlen.hip).
+// lower = 0 adds the zero-length path, whose b is a copy of a without b's node scan (k_final's rule): a
+// counts once whatever b_ok(a) says, and once only when a cycle also returns to it.
+//
+// Levels: R_0 = {}, F_0 = {a}; N_i = heads of the relationships whose tail is in F_(i-1), F_i = N_i \ R_(i-1),
+// R_i = R_(i-1) | N_i.  Only new nodes are expanded; an empty frontier ends the walk.
+//
+// Global form: one BFS from all of a_ok over three n-bit maps (reached, frontier, next).
+// Grouped form: multi-source BFS, 64 * NW sources per batch (NW 64-bit words per node, node-major), the
+// batches walking the set bits of a_ok in id order.  The relationships are bucketed once per query by
+// TARGET slice (the chunked partition of k_part.hip); the block that owns a slice segment ORs
+// front[source] into its slice's `next` words in LDS, and a block that holds all of a slice's chunks finishes
+// the slice from LDS (new = next & ~seen, plain stores of seen and front, per-source counts by ballot).
+// Slices shared by several blocks, and slices no relationship enters, are finished by k_rg_fix.
+#include "part_common.h"
+
+namespace capsmi {
+namespace reach {
+
+using u64 = unsigned long long;
+using part::ChunkWalk;
+
+constexpr int kBlock = 1024;
+constexpr int kLdsWords = 16384;  // 128 KiB of `next` words per block: 16384 / NW ids per slice
+constexpr int kMaxWords = 8;
+
+inline int grid(const capsmi_session* s, int64_t n) {
+    int64_t g = (n + 255) / 256;
+    const int64_t cap = (int64_t)s->num_cus * 16;
+    if (g > cap) g = cap;
+    if (g < 1) g = 1;
+    return (int)g;
+}
+
+__device__ __forceinline__ bool bit_of(const uint32_t* w, int full, uint64_t x) {
+    return full || ((w[x >> 5] >> (x & 31)) & 1u);
+}
+
+__global__ void k_zero3(u64* a, u64* b, u64* c, int64_t n) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        a[i] = 0;
+        b[i] = 0;
+        c[i] = 0;
+    }
+}
+
+// ---- global form ------------------------------------------------------------------------------------------
+// F = a_ok over the nw words of the window (bits past n clear), R = N = 0
+__global__ void k_rc_init(const uint32_t* __restrict__ aw, int a_full, int64_t n, int64_t nw, uint32_t* __restrict__ F,
+                          uint32_t* __restrict__ R, uint32_t* __restrict__ N) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nw; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t left = n - 32 * i;
+        const uint32_t in = left >= 32 ? 0xFFFFFFFFu : ((1u << left) - 1u);
+        F[i] = (a_full ? 0xFFFFFFFFu : aw[i]) & in;
+        R[i] = 0;
+        N[i] = 0;
+    }
+}
+
+// one level: the head's bit in N for every relationship whose tail is in F; heads already reached, or already
+// marked this level, cost a load and no atomic
+template <typename IdT>
+__global__ void k_rc_level(const IdT* __restrict__ src, const IdT* __restrict__ dst, int64_t m, int64_t lo, uint64_t n,
+                           const uint32_t* __restrict__ F, const uint32_t* __restrict__ R, uint32_t* __restrict__ N) {
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < m; e += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t u = part::rel_id(src[e], lo), v = part::rel_id(dst[e], lo);
+        if (u >= n || v >= n) continue;
+        if (!((F[u >> 5] >> (u & 31)) & 1u)) continue;
+        const uint32_t bit = 1u << (v & 31);
+        if ((R[v >> 5] | N[v >> 5]) & bit) continue;
+        atomicOr(&N[v >> 5], bit);
+    }
+}
+
+// per node word: new = N & ~R, R |= new, F = new, N = 0; tot[0] += new bits in b_ok, tot[1] += new bits
+// (one add per block each: the host compares tot[1] with the level before to see an empty frontier)
+__global__ void k_rc_final(int64_t nw, uint32_t* __restrict__ N, uint32_t* __restrict__ R, uint32_t* __restrict__ F,
+                           const uint32_t* __restrict__ bw, int b_full, u64* __restrict__ tot) {
+    __shared__ unsigned int cb, cn;
+    if (threadIdx.x == 0) cb = cn = 0;
+    __syncthreads();
+    unsigned int mb = 0, mn = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nw; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint32_t nx = N[i], r = R[i], nv = nx & ~r;
+        if (nx) N[i] = 0;
+        if (nv) R[i] = r | nv;
+        F[i] = nv;
+        mn += __popc(nv);
+        mb += __popc(b_full ? nv : nv & bw[i]);
+    }
+    if (mb) atomicAdd(&cb, mb);
+    if (mn) atomicAdd(&cn, mn);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (cb) atomicAdd(&tot[0], (u64)cb);
+        if (cn) atomicAdd(&tot[1], (u64)cn);
+    }
+}
+
+// lower = 0: the a_ok nodes that the reached b_ok set does not hold already
+__global__ void k_rc_zero(int64_t n, int64_t nw, const uint32_t* __restrict__ R, const uint32_t* __restrict__ aw,
+                          int a_full, const uint32_t* __restrict__ bw, int b_full, u64* __restrict__ tot) {
+    __shared__ unsigned int cb;
+    if (threadIdx.x == 0) cb = 0;
+    __syncthreads();
+    unsigned int mb = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nw; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t left = n - 32 * i;
+        const uint32_t in = left >= 32 ? 0xFFFFFFFFu : ((1u << left) - 1u);
+        const uint32_t a = (a_full ? 0xFFFFFFFFu : aw[i]) & in;
+        mb += __popc(a & ~(R[i] & (b_full ? 0xFFFFFFFFu : bw[i])));
+    }
+    if (mb) atomicAdd(&cb, mb);
+    __syncthreads();
+    if (threadIdx.x == 0 && cb) atomicAdd(&tot[0], (u64)cb);
+}
+
+// ---- grouped form -----------------------------------------------------------------------------------------
+__global__ void k_rg_flags(const uint32_t* __restrict__ aw, int a_full, int64_t n, uint8_t* __restrict__ f) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        f[i] = bit_of(aw, a_full, (uint64_t)i) ? 1 : 0;
+}
+
+// source j of the batch (node idx[j], relative) starts with its own bit in the frontier (distinct nodes: plain stores)
+__global__ void k_rg_init(const int64_t* __restrict__ idx, int bw, int nwords, u64* __restrict__ front) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < bw) front[idx[j] * nwords + (j >> 6)] = 1ULL << (j & 63);
+}
+
+// OR of a 64-bit value over the wave, the same in every lane
+__device__ __forceinline__ u64 wave_or(u64 x) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) x |= __shfl_xor(x, o, 64);
+    return x;
+}
+
+// The lanes of a wave hold 64 nodes' new bits of word w (0 for nodes outside b_ok): per set source bit j, the
+// number of lanes that hold it goes into the block's LDS counter of source 64 w + j.  All 64 lanes call.
+__device__ __forceinline__ void count_sources(u64 cm, int w, uint32_t* cl) {
+    u64 m = wave_or(cm);
+    m = ((u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)(m >> 32)) << 32) |
+        (u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m);
+    const int lane = threadIdx.x & 63;
+    while (m) {  // wave-uniform
+        const int j = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        const unsigned int c = (unsigned int)__popcll(__ballot((cm >> j) & 1ULL));
+        if (lane == 0) atomicAdd(&cl[w * 64 + j], c);
+    }
+}
+
+// one add per (block, source) and one per block for the "anything new" word
+__device__ __forceinline__ void flush_counts(const uint32_t* cl, int nwords, const uint32_t& anynew, u64* cnts, u64* tot) {
+    __syncthreads();
+    for (int t = threadIdx.x; t < nwords * 64; t += blockDim.x)
+        if (cl[t]) atomicAdd(&cnts[t], (u64)cl[t]);
+    if (threadIdx.x == 0 && anynew) atomicAdd(tot, 1ULL);
+}
+
+// One level over the target partition (pair = (source, target), bucket = slice of the target).  Slices are
+// 2^tbits ids, those of the query's width W (kLdsWords / W); a last batch narrower than W (NW < W) uses the
+// first NW * 2^tbits words of the block's LDS.
+template <int NW>
+__global__ void __launch_bounds__(kBlock) k_rg_level(ChunkWalk cw, int tbits, int64_t n, const u64* __restrict__ fin,
+                                                     u64* __restrict__ seen, u64* __restrict__ fout,
+                                                     const uint32_t* __restrict__ bw, int b_full,
+                                                     u64* __restrict__ cnts, u64* __restrict__ tot) {
+    extern __shared__ u64 rg_next[];  // kLdsWords
+    __shared__ uint32_t cl[NW * 64];
+    __shared__ uint32_t anynew;
+    const int kIds = 1 << tbits;  // >= 2048: a multiple of kBlock
+    for (int i = threadIdx.x; i < kIds * NW; i += kBlock) rg_next[i] = 0;
+    for (int i = threadIdx.x; i < NW * 64; i += kBlock) cl[i] = 0;
+    if (threadIdx.x == 0) anynew = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    part::walk_chunks_n<kBlock>(
+        cw,
+        [&](const uint2 (&pr)[part::kWalkItems], uint32_t valid, int) {
+            constexpr int G = NW >= 8 ? 2 : (NW == 4 ? 4 : 8);  // items whose front words are gathered together
+#pragma unroll
+            for (int k0 = 0; k0 < part::kWalkItems; k0 += G) {
+                u64 f[G][NW];
+#pragma unroll
+                for (int k = 0; k < G; ++k)
+#pragma unroll
+                    for (int w = 0; w < NW; ++w) f[k][w] = fin[(size_t)pr[k0 + k].x * NW + w];  // zero pairs read node 0
+#pragma unroll
+                for (int k = 0; k < G; ++k) {
+                    if (!((valid >> (k0 + k)) & 1u)) continue;
+                    const uint32_t t = pr[k0 + k].y & (uint32_t)(kIds - 1);
+#pragma unroll
+                    for (int w = 0; w < NW; ++w)
+                        if (f[k][w]) atomicOr(&rg_next[t * NW + w], f[k][w]);
+                }
+            }
+        },
+        [&](int j) {
+            const bool own = part::owns_slice(cw, j);  // block-uniform
+            const int64_t base = (int64_t)j * kIds;
+            u64 any = 0;
+            for (int i = threadIdx.x; i < kIds; i += kBlock) {  // wave-uniform trips
+                const int64_t x = base + i;
+                const bool in = x < n;
+                const bool bk = in && bit_of(bw, b_full, (uint64_t)x);
+#pragma unroll
+                for (int w = 0; w < NW; ++w) {
+                    const u64 nx = rg_next[i * NW + w];
+                    rg_next[i * NW + w] = 0;
+                    if (own) {
+                        u64 nv = 0;
+                        if (in) {
+                            const u64 sn = seen[(size_t)x * NW + w];
+                            nv = nx & ~sn;
+                            if (nv) seen[(size_t)x * NW + w] = sn | nv;
+                            fout[(size_t)x * NW + w] = nv;
+                        }
+                        any |= nv;
+                        count_sources(bk ? nv : 0ULL, w, cl);
+                    } else if (nx && in) {
+                        atomicOr(&fout[(size_t)x * NW + w], nx);  // k_rg_fix finishes the shared slices
+                    }
+                }
+            }
+            if (__any(any != 0) && lane == 0) anynew = 1;
+        });
+    flush_counts(cl, NW, anynew, cnts, tot);
+}
+
+// whether one block of the level kernel's grid holds all of slice j's chunks (part::owns_slice, seen from outside)
+__device__ __forceinline__ bool slice_owned(const int64_t* jst, int nt, int64_t blocks, int j) {
+    const int64_t c0 = jst[j], c1 = jst[j + 1];
+    if (c1 <= c0) return false;  // no relationship enters the slice: no block visits it
+    const part::SegSplit S(jst, nt, blocks);
+    const int64_t w = c0 / S.per;
+    return c1 <= min(w * S.per + S.per, S.nch);
+}
+
+// The nodes of the slices that no single block finished (shared by several blocks, or never visited; jst == null:
+// every node, the flat form): fout holds their `next` words.  new = next & ~seen, seen |= new, fout = new, and the
+// old front is cleared, since no owner overwrites it when it becomes the next level's fout.
+template <int NW>
+__global__ void __launch_bounds__(256) k_rg_fix(const int64_t* __restrict__ jst, int nt, int64_t blocks, int tbits,
+                                                int64_t n,
+                                                u64* __restrict__ fin, u64* __restrict__ seen, u64* __restrict__ fout,
+                                                const uint32_t* __restrict__ bw, int b_full, u64* __restrict__ cnts,
+                                                u64* __restrict__ tot) {
+    __shared__ uint32_t cl[NW * 64];
+    __shared__ uint32_t anynew;
+    for (int i = threadIdx.x; i < NW * 64; i += blockDim.x) cl[i] = 0;
+    if (threadIdx.x == 0) anynew = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    u64 any = 0;
+    // a wave takes 64 consecutive nodes, all of one slice (slices are multiples of 64 ids): wave-uniform trips
+    for (int64_t x0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) & ~(int64_t)63; x0 < n;
+         x0 += (int64_t)gridDim.x * blockDim.x) {
+        if (jst && slice_owned(jst, nt, blocks, (int)(x0 >> tbits))) continue;
+        const int64_t x = x0 + lane;
+        const bool in = x < n;
+        const bool bk = in && bit_of(bw, b_full, (uint64_t)x);
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            u64 nv = 0;
+            if (in) {
+                const size_t q = (size_t)x * NW + w;
+                const u64 nx = fout[q], sn = seen[q];
+                nv = nx & ~sn;
+                if (nv) seen[q] = sn | nv;
+                if (nx != nv) fout[q] = nv;
+                if (fin[q]) fin[q] = 0;
+            }
+            any |= nv;
+            count_sources(bk ? nv : 0ULL, w, cl);
+        }
+    }
+    if (__any(any != 0) && lane == 0) anynew = 1;
+    flush_counts(cl, NW, anynew, cnts, tot);
+}
+
+// The flat form of a level (domains beyond the sliced path, or CAPSMI_REACH=flat): one global OR per
+// relationship and word that brings something new; k_rg_fix (jst == null) finishes every node.
+template <int NW, typename IdT>
+__global__ void k_rg_level_flat(const IdT* __restrict__ src, const IdT* __restrict__ dst, int64_t m, int64_t lo,
+                                uint64_t n, const u64* __restrict__ fin, const u64* __restrict__ seen,
+                                u64* __restrict__ fout) {
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < m; e += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t u = part::rel_id(src[e], lo), v = part::rel_id(dst[e], lo);
+        if (u >= n || v >= n) continue;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            u64 f = fin[u * NW + w];
+            if (!f) continue;
+            f &= ~seen[v * NW + w];
+            if (f) atomicOr(&fout[v * NW + w], f);
+        }
+    }
+}
+
+// lower = 0: source j counts itself unless its own bit is in seen[a] and b_ok(a) (then a level counted it)
+__global__ void k_rg_zero(const int64_t* __restrict__ idx, int bw, int nwords, const u64* __restrict__ seen,
+                          const uint32_t* __restrict__ bwd, int b_full, u64* __restrict__ cnts) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= bw) return;
+    const int64_t a = idx[j];
+    const bool self = (seen[a * nwords + (j >> 6)] >> (j & 63)) & 1ULL;
+    if (!(self && bit_of(bwd, b_full, (uint64_t)a))) cnts[j] += 1;
+}
+
+__global__ void k_rg_rowflags(const u64* __restrict__ cnts, int64_t A, uint8_t* __restrict__ f) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < A; i += (int64_t)gridDim.x * blockDim.x)
+        f[i] = cnts[i] ? 1 : 0;
+}
+
+__global__ void k_rg_rows(const int64_t* __restrict__ sel, int64_t rows, const int64_t* __restrict__ idx, int64_t lo,
+                          const u64* __restrict__ cnts, int64_t* __restrict__ ids, int64_t* __restrict__ out) {
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t j = sel[r];
+        ids[r] = lo + idx[j];
+        out[r] = (int64_t)cnts[j];
+    }
+}
+
+// The early-exit read-back (one 8-byte copy and a stream wait per level) is skipped while it cannot pay: an
+// empty frontier saves the levels still to run, and a read-back costs about what one level costs at the
+// sizes where levels are cheap.  So no level is checked while at most kNoCheckLevels levels remain after it,
+// and a query with upper <= kNoCheckLevels + 1 never waits.
+constexpr int kNoCheckLevels = 2;
+inline bool check_after(int level, int upper) { return upper - level > kNoCheckLevels; }
+
+template <int NW>
+void run_level(capsmi_session* s, bool sliced, int tbits, const ChunkWalk& cw, const ChunkPart& cp, const int64_t* const* srcs,
+               const int64_t* const* dsts, const int64_t* ms, int nt, const NarrowRel* nar, int64_t lo, int64_t n,
+               int64_t mtot, u64* fin, u64* seen, u64* fout, const uint32_t* bw, int b_full, u64* cnts, u64* tot) {
+    hipStream_t st = s->stream;
+    const double state = 3.0 * (double)n * NW * 8;
+    if (sliced) {
+        {
+            KernelTimer kt(s, "reach_level", (double)mtot * (8 + NW * 8) + state);
+            hipLaunchKernelGGL(k_rg_level<NW>, dim3((unsigned)cp.g2), dim3(kBlock), sizeof(u64) * kLdsWords, st, cw, tbits,
+                               n, fin, seen, fout, bw, b_full, cnts, tot);
+        }
+        KernelTimer kt(s, "reach_final");
+        hipLaunchKernelGGL(k_rg_fix<NW>, dim3(grid(s, n)), dim3(256), 0, st, cp.jst, cw.nt, cp.g2, tbits, n, fin, seen, fout,
+                           bw, b_full, cnts, tot);
+    } else {
+        {
+            double rel_bytes = 0;
+            for (int i = 0; i < nt; ++i)
+                if (ms[i] > 0) rel_bytes += (double)ms[i] * (nar && nar[i].s ? 8 : 16);
+            KernelTimer kt(s, "reach_level", rel_bytes + (double)mtot * NW * 8);
+            for (int i = 0; i < nt; ++i) {
+                if (ms[i] <= 0) continue;
+                if (nar && nar[i].s)
+                    hipLaunchKernelGGL((k_rg_level_flat<NW, uint32_t>), dim3(grid(s, ms[i])), dim3(256), 0, st, nar[i].s,
+                                       nar[i].d, ms[i], lo - nar[i].base, (uint64_t)n, fin, seen, fout);
+                else
+                    hipLaunchKernelGGL((k_rg_level_flat<NW, int64_t>), dim3(grid(s, ms[i])), dim3(256), 0, st, srcs[i],
+                                       dsts[i], ms[i], lo, (uint64_t)n, fin, seen, fout);
+            }
+        }
+        KernelTimer kt(s, "reach_final", state);
+        hipLaunchKernelGGL(k_rg_fix<NW>, dim3(grid(s, n)), dim3(256), 0, st, (const int64_t*)nullptr, 0, (int64_t)0, 0,
+                           n, fin, seen, fout, bw, b_full, cnts, tot);
+    }
+}
+
+inline int tbits_of(int nwords) { return nwords == 1 ? 14 : nwords == 2 ? 13 : nwords == 4 ? 12 : 11; }
+
+// the largest domain the sliced path takes at `nwords` words: the partition's slice count, and k_varlen's 2^24
+inline int64_t sliced_max(int nwords) {
+    return std::min<int64_t>(int64_t(1) << 24, (int64_t)part::kMaxTSlices << tbits_of(nwords));
+}
+
+}  // namespace reach
+
+// |U_a D(a)|: one BFS from all of a_ok
+int64_t var_length_reach_count(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts,
+                               const int64_t* ms, int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower,
+                               int upper, const NarrowRel* nar) {
+    using namespace reach;
+    hipStream_t st = s->stream;
+    const int64_t n = b_ok->hi - b_ok->lo, lo = b_ok->lo;
+    if (n <= 0) return 0;
+    const int64_t nw = (n + 31) / 32;
+    const uint32_t* aw = P<uint32_t>(a_ok->words);
+    const uint32_t* bw = P<uint32_t>(b_ok->words);
+    const int a_full = a_ok->full ? 1 : 0, b_full = b_ok->full ? 1 : 0;
+    Buf maps = dev_alloc(sizeof(uint32_t) * 3 * (size_t)nw, s), tot = dev_alloc(2 * sizeof(u64), s);
+    uint32_t *F = P<uint32_t>(maps), *R = F + nw, *N = R + nw;
+    HIP_CHECK(hipMemsetAsync(P<void>(tot), 0, 2 * sizeof(u64), st));
+    hipLaunchKernelGGL(k_rc_init, dim3(grid(s, nw)), dim3(256), 0, st, aw, a_full, n, nw, F, R, N);
+    double rel_bytes = 0;
+    for (int i = 0; i < nt; ++i)
+        if (ms[i] > 0) rel_bytes += (double)ms[i] * (nar && nar[i].s ? 8 : 16);
+    int64_t before = 0;
+    for (int level = 1; level <= upper; ++level) {
+        {
+            KernelTimer kt(s, "reach_count_level", rel_bytes);
+            for (int i = 0; i < nt; ++i) {
+                if (ms[i] <= 0) continue;
+                if (nar && nar[i].s)
+                    hipLaunchKernelGGL(k_rc_level<uint32_t>, dim3(grid(s, ms[i])), dim3(256), 0, st, nar[i].s, nar[i].d,
+                                       ms[i], lo - nar[i].base, (uint64_t)n, F, R, N);
+                else
+                    hipLaunchKernelGGL(k_rc_level<int64_t>, dim3(grid(s, ms[i])), dim3(256), 0, st, srcs[i], dsts[i],
+                                       ms[i], lo, (uint64_t)n, F, R, N);
+            }
+        }
+        {
+            KernelTimer kt(s, "reach_count_final", 4.0 * 5 * (double)nw);
+            hipLaunchKernelGGL(k_rc_final, dim3(grid(s, nw)), dim3(256), 0, st, nw, N, R, F, bw, b_full, P<u64>(tot));
+        }
+        if (check_after(level, upper)) {
+            const int64_t now = read_scalar(s, P<int64_t>(tot) + 1);
+            if (now == before) break;  // nothing new: the frontier is empty
+            before = now;
+        }
+    }
+    if (lower == 0)
+        hipLaunchKernelGGL(k_rc_zero, dim3(grid(s, nw)), dim3(256), 0, st, n, nw, R, aw, a_full, bw, b_full, P<u64>(tot));
+    HIP_CHECK(hipGetLastError());
+    return read_scalar(s, P<int64_t>(tot));
+}
+
+// rows (a, |D(a)|) of the a_ok nodes with a non-empty D(a); returns the row count
+int64_t var_length_reach_rows(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
+                              int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower, int upper,
+                              Buf& out_ids, Buf& out_cnt, const NarrowRel* nar) {
+    using namespace reach;
+    hipStream_t st = s->stream;
+    const int64_t n = b_ok->hi - b_ok->lo, lo = b_ok->lo;
+    const uint32_t* aw = P<uint32_t>(a_ok->words);
+    const uint32_t* bw = P<uint32_t>(b_ok->words);
+    const int a_full = a_ok->full ? 1 : 0, b_full = b_ok->full ? 1 : 0;
+    // the sources in id order (relative ids): the one read-back before the levels
+    Buf idx;
+    int64_t A = 0;
+    if (n > 0) {
+        Buf fl = dev_alloc((size_t)n, s);
+        hipLaunchKernelGGL(k_rg_flags, dim3(grid(s, n)), dim3(256), 0, st, aw, a_full, n, P<uint8_t>(fl));
+        A = flags_to_indices(s, P<uint8_t>(fl), n, idx);
+    }
+    if (A == 0) {
+        out_ids = dev_alloc(8, s);
+        out_cnt = dev_alloc(8, s);
+        return 0;
+    }
+    int64_t mtot = 0;
+    for (int i = 0; i < nt; ++i) mtot += ms[i] > 0 ? ms[i] : 0;
+    // words per node: the knob, or auto: the narrowest width that takes all sources in one
+    // batch, up to kMaxWords, halved while the state (3 n W words) exceeds a quarter of the free memory or the
+    // domain is beyond the sliced path at that width
+    const int64_t need_words = (A + 63) / 64;
+    int W = s->cfg.reach_words;
+    const bool autow = W == 0;
+    if (autow) W = kMaxWords;
+    while (W > 1 && W / 2 >= need_words) W /= 2;  // never wider than the sources
+    if (autow) {
+        size_t free_b = 0, total_b = 0;
+        HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+        while (W > 1 && (3.0 * (double)n * W * 8 > (double)free_b / 4 || (n > sliced_max(W) && n <= sliced_max(1)))) W /= 2;
+    }
+    const bool sliced = !s->cfg.reach_flat && mtot > 0 && n <= sliced_max(W);
+    ChunkPart cp;
+    ChunkWalk cw{};
+    if (sliced) {
+        part::Layout L{};
+        L.lo = lo;
+        L.hi = b_ok->hi;
+        L.tbits = tbits_of(W);
+        L.nt = (int)((n + (int64_t(1) << L.tbits) - 1) >> L.tbits);
+        L.ns = 1;
+        L.sbits = 31;
+        L.ncells = L.nt;
+        {
+            KernelTimer kt(s, "reach_part");
+            chunk_partition(s, srcs, dsts, ms, nt, false, L, s->num_cus, cp, false, false, nar);
+        }
+        cw = ChunkWalk{P<uint2>(cp.pool), P<unsigned long long>(cp.meta), cp.order, cp.jst, cp.segbase, cp.ja, L.nt};
+        const size_t lds = sizeof(u64) * kLdsWords;
+        lds_attr(reinterpret_cast<const void*>(k_rg_level<1>), lds);
+        lds_attr(reinterpret_cast<const void*>(k_rg_level<2>), lds);
+        lds_attr(reinterpret_cast<const void*>(k_rg_level<4>), lds);
+        lds_attr(reinterpret_cast<const void*>(k_rg_level<8>), lds);
+    }
+    const size_t words = (size_t)n * W;
+    Buf state = dev_alloc(sizeof(u64) * 3 * words, s), cnts = dev_alloc(sizeof(u64) * (size_t)(A + 64 * kMaxWords), s),
+        tot = dev_alloc(sizeof(u64), s);
+    HIP_CHECK(hipMemsetAsync(P<void>(cnts), 0, sizeof(u64) * (size_t)(A + 64 * kMaxWords), st));
+    HIP_CHECK(hipMemsetAsync(P<void>(tot), 0, sizeof(u64), st));
+    u64 *seen = P<u64>(state), *fa = seen + words, *fb = fa + words;
+    int64_t before = 0;
+    for (int64_t base = 0; base < A; base += 64 * (int64_t)W) {
+        // no batch wider than the sources left: the last one takes the narrowest width that holds them (the
+        // slices stay those of W; a narrower batch uses part of the block's LDS)
+        const int bwid = (int)std::min<int64_t>(64 * (int64_t)W, A - base);
+        int NWb = 1;
+        while (NWb * 64 < bwid) NWb *= 2;
+        const int64_t bwords = n * NWb;
+        hipLaunchKernelGGL(k_zero3, dim3(grid(s, bwords)), dim3(256), 0, st, seen, fa, fb, bwords);
+        const int64_t* bidx = P<int64_t>(idx) + base;
+        u64* bcnt = P<u64>(cnts) + base;
+        hipLaunchKernelGGL(k_rg_init, dim3((bwid + 255) / 256), dim3(256), 0, st, bidx, bwid, NWb, fa);
+        u64 *fin = fa, *fout = fb;
+        for (int level = 1; level <= upper; ++level) {
+            switch (NWb) {
+                case 1: run_level<1>(s, sliced, tbits_of(W), cw, cp, srcs, dsts, ms, nt, nar, lo, n, mtot, fin, seen, fout, bw, b_full, bcnt, P<u64>(tot)); break;
+                case 2: run_level<2>(s, sliced, tbits_of(W), cw, cp, srcs, dsts, ms, nt, nar, lo, n, mtot, fin, seen, fout, bw, b_full, bcnt, P<u64>(tot)); break;
+                case 4: run_level<4>(s, sliced, tbits_of(W), cw, cp, srcs, dsts, ms, nt, nar, lo, n, mtot, fin, seen, fout, bw, b_full, bcnt, P<u64>(tot)); break;
+                default: run_level<8>(s, sliced, tbits_of(W), cw, cp, srcs, dsts, ms, nt, nar, lo, n, mtot, fin, seen, fout, bw, b_full, bcnt, P<u64>(tot)); break;
+            }
+            std::swap(fin, fout);
+            if (check_after(level, upper)) {
+                const int64_t now = read_scalar(s, P<int64_t>(tot));
+                if (now == before) break;  // no block saw a new bit: every frontier of the batch is empty
+                before = now;
+            }
+        }
+        if (lower == 0)
+            hipLaunchKernelGGL(k_rg_zero, dim3((bwid + 255) / 256), dim3(256), 0, st, bidx, bwid, NWb, seen, bw, b_full, bcnt);
+    }
+    HIP_CHECK(hipGetLastError());
+    Buf rf = dev_alloc((size_t)A, s), sel;
+    hipLaunchKernelGGL(k_rg_rowflags, dim3(grid(s, A)), dim3(256), 0, st, P<u64>(cnts), A, P<uint8_t>(rf));
+    const int64_t rows = flags_to_indices(s, P<uint8_t>(rf), A, sel);  // the read-back of the row count
+    out_ids = dev_alloc(sizeof(int64_t) * (size_t)(rows > 0 ? rows : 1), s);
+    out_cnt = dev_alloc(sizeof(int64_t) * (size_t)(rows > 0 ? rows : 1), s);
+    if (rows > 0)
+        hipLaunchKernelGGL(k_rg_rows, dim3(grid(s, rows)), dim3(256), 0, st, P<int64_t>(sel), rows, P<int64_t>(idx), lo,
+                           P<u64>(cnts), P<int64_t>(out_ids), P<int64_t>(out_cnt));
+    HIP_CHECK(hipGetLastError());
+    return rows;
+}
+
+}  // namespace capsmi

@@ -1867,6 +1867,108 @@ bool fused_var_length(capsmi_session* s, const capsmi_table* in, const PlanNode&
     return true;
 }
 
+// count(DISTINCT end node) over the branches of a bounded var-length expand, grouped by the start node
+// (g.a = the start's id-like column) or alone (g.a empty): k-hop reach (k_reach.hip).  Lengths lower..upper
+// contiguous with lower in {0, 1} and any upper; the branch checks are fused_var_length's.
+bool fused_var_length_distinct(capsmi_session* s, const capsmi_table* in, const PlanNode& g, const std::vector<Path>& B,
+                               capsmi_table** out) {
+    if (g.a.size() > 1 || g.aggs.size() != 1 || g_dist.on) return false;  // single device: the operator path answers
+    const bool grouped = !g.a.empty();
+    const AggSpec& ag = g.aggs[0];
+    if (ag.kind != CAPSMI_AGG_COUNT || !ag.distinct) return false;
+    const int gc = grouped ? find_col(in, g.a[0]) : -1;
+    const int ic = find_col(in, ag.input);
+    if ((grouped && gc < 0) || ic < 0) return false;
+    std::set<int> lens;
+    std::string akey, bkey, rsig;
+    int64_t lo, hi;
+    if (!id_window(B, &lo, &hi)) return false;
+    BitmapSet bs;
+    capsmi_bitmap *abm = nullptr, *bbm = nullptr;
+    RelViews views;
+    std::string zero_key;  // the zero-length branch's start scan (lower = 0)
+    bool first = true;
+    for (size_t bi = 0; bi < B.size(); ++bi) {
+        const Path& P = B[bi];
+        if (any_no_loops(P)) return false;
+        const int k = (int)P.hops.size();
+        if (grouped && (position_of(P, P.cols[gc]) != 0 || !id_like(P, P.cols[gc]))) return false;
+        if (k == 0) {
+            // lower = 0: copyEntity(source -> target) of the start scan: the counted end is the copied start column
+            if (lens.count(0) || P.pos_node.empty() || P.pos_node[0] < 0) return false;
+            if (position_of(P, P.cols[ic]) != 0 || !id_like(P, P.cols[ic])) return false;
+            Classified c;
+            if (!classify(P, c) || !c.uniq.empty()) return false;
+            for (size_t q = 0; q < P.inst.size(); ++q)
+                if (!c.pred[q].empty() && (int)q != P.pos_node[0]) return false;
+            if (!node_bitmap(s, P, c, P.pos_node[0], lo, hi, bs, &zero_key)) return false;
+            lens.insert(0);
+            continue;
+        }
+        if (!is_chain(P) || !same_orientation(P) || lens.count(k)) return false;
+        lens.insert(k);
+        for (int q = 1; q < k; ++q) if (P.pos_node[q] >= 0) return false;  // hops are not node-scanned
+        if (P.pos_node[0] < 0 || P.pos_node[k] < 0) return false;
+        if (position_of(P, P.cols[ic]) != k || !id_like(P, P.cols[ic])) return false;  // the end node's id
+        Classified c;
+        if (!classify(P, c) || !all_pairs_unique(c, k)) return false;
+        for (size_t q = 0; q < P.inst.size(); ++q)
+            if (!c.pred[q].empty() && (int)q != P.pos_node[0] && (int)q != P.pos_node[k]) return false;
+        std::string ka, kb;
+        capsmi_bitmap* a = node_bitmap(s, P, c, P.pos_node[0], lo, hi, bs, &ka);
+        capsmi_bitmap* b = node_bitmap(s, P, c, P.pos_node[k], lo, hi, bs, &kb);
+        if (!a || !b) return false;
+        for (int h = 0; h < k; ++h) {
+            RelViews v;
+            rel_views(P, P.hops[h], v);
+            if (first && h == 0) {
+                rsig = v.sig;
+                views.t.swap(v.t);
+            } else if (v.sig != rsig) {
+                return false;
+            }
+        }
+        if (first) { akey = ka; bkey = kb; abm = a; bbm = b; first = false; }
+        else if (ka != akey || kb != bkey) return false;
+    }
+    if (first || (lens.count(0) && zero_key != akey)) return false;  // a path of >= 1 hop; one start scan
+    const int l = *lens.begin(), u = *lens.rbegin();
+    if (l < 0 || l > 1 || u - l + 1 != (int)lens.size()) return false;  // lower >= 2: the join plan
+    if (abm->any_dup || bbm->any_dup) return false;
+    if (!grouped) {
+        int64_t x = 0;
+        check(capsmi_var_length_reach_count(s, (int32_t)views.t.size(), views.t.data(), "s", "t", abm, bbm, l, u, &x));
+        auto* r = result_table(s, 1);
+        Column c = i64_column(s, {x});
+        c.name = ag.output;
+        r->cols.push_back(std::move(c));
+        *out = r;
+        route(s, "var_length_distinct");
+        return true;
+    }
+    check(capsmi_var_length_count_distinct(s, (int32_t)views.t.size(), views.t.data(), "s", "t", abm, bbm, l, u,
+                                           g.a[0].c_str(), ag.output.c_str(), out));
+    if (g_dense) {  // start ids back to the graph's Long ids
+        capsmi_table* r = *out;
+        Column& c = r->cols[0];
+        Buf ids = dev_alloc(sizeof(int64_t) * (r->nrows > 0 ? r->nrows : 1), s);
+        if (g_dense->scrambled) {
+            if (r->nrows)
+                HIP_CHECK(hipMemcpyAsync(::capsmi::P<int64_t>(ids), c.d(), sizeof(int64_t) * r->nrows,
+                                         hipMemcpyDeviceToDevice, s->stream));
+            unscramble_ids(s, *g_dense, ::capsmi::P<int64_t>(ids), r->nrows);
+        } else {
+            gather_col(P<int64_t>(g_dense->orig), nullptr, c.d(), r->nrows, ::capsmi::P<int64_t>(ids), nullptr, s->stream);
+        }
+        c.data = ids;
+        c.offset = 0;
+        c.host.reset();
+        c.narrow.reset();
+    }
+    route(s, "var_length_distinct");
+    return true;
+}
+
 // Expand + node filters projected on relationship / endpoint columns (C2)
 bool fused_projection(capsmi_session* s, const capsmi_table* t, const std::vector<Path>& B, capsmi_table** out) {
     if (B.size() != 1) return false;
@@ -1996,6 +2098,7 @@ bool try_fused_shapes(capsmi_table* t, capsmi_table** out) {
         if (!as_paths(in, B) || B.empty()) return false;
         if (p.a.empty()) {
             if (B.size() != 1) {
+                if (fused_var_length_distinct(s, in, p, B, out)) return true;
                 std::vector<int64_t> vals;
                 if (!fused_undirected(s, in, p, B, vals)) return fused_undirected_triangle(s, in, p, B, out);
                 auto* r = result_table(s, 1);
@@ -2024,6 +2127,7 @@ bool try_fused_shapes(capsmi_table* t, capsmi_table** out) {
         if (fused_grouped_two_hop(s, in, p, B, out)) return true;
         if (fused_grouped_triangle(s, in, p, B, out)) return true;
         if (fused_undirected_triangle(s, in, p, B, out)) return true;
+        if (fused_var_length_distinct(s, in, p, B, out)) return true;
         return fused_var_length(s, in, p, B, out);
     }
     std::vector<Path> B;

@@ -414,11 +414,15 @@ capsmi_status capsmi_session_kernel_time(capsmi_session* s, const char* name, in
  * the old store's bytes read and written once and the new entries' bytes likewise, its plan (scan / compaction) timed
  * as "str_store_merge_starts", without bytes; "str_make_gather": 8 B read and
  * 9 B written per row;
+ * var-length count(DISTINCT b): "reach_level", one level of a batch of 64 W sources: 8 B per pooled pair + 8 W B of
+ * frontier words per relationship + the 3 n W 8 B of state (the flat form: the relationship columns instead of the
+ * pool, its state counted under "reach_final"); "reach_count_level": 8 B (narrow) or 16 B per relationship;
+ * "reach_count_final": 20 B per word of 32 ids; "reach_part", the partition by target slice, declares none;
  * 0 otherwise; then the counter resets. */
 capsmi_status capsmi_session_kernel_bytes(capsmi_session* s, const char* name, double* bytes);
 /* fused-path routing of lazy plans: enable / disable (default on; off = operator by operator, for
  * A/B checks), and the number of plans routed to fused entry point `name` ("expand", "expand_count",
- * "two_hop", "triangle", "var_length") since the session started */
+ * "two_hop", "triangle", "var_length", "var_length_distinct") since the session started */
 capsmi_status capsmi_session_set_fused(capsmi_session* s, int32_t enabled);
 /* query parameters (the CypherMap handed to asSparkSQLExpr): CAPSMI_X_PARAM `arg` = index into
  * `params`.  A scalar has count 1 (is_list 0); a list has is_list 1 and `count` values.  Values are
@@ -786,6 +790,30 @@ capsmi_status capsmi_var_length_count(capsmi_session* s, int32_t nrels, capsmi_t
                                       const char* src_col, const char* dst_col, const capsmi_bitmap* a_ok,
                                       const capsmi_bitmap* b_ok, int32_t lower, int32_t upper, const char* id_name,
                                       const char* count_name, capsmi_table** out);
+/* BoundedVarLengthExpand + count(DISTINCT b), fused: k-hop reach by bit-parallel BFS (k_reach.hip).
+ *   MATCH (a)-[r*lower..upper]->(b) WHERE a_ok(a) AND b_ok(b)
+ *   RETURN id(a) AS <id_name>, count(DISTINCT b) AS <count_name>
+ * lower 0 or 1, any upper >= 1 (a level budget: a frontier dies after at most n levels).
+ * Lemma: for lower <= 1, b ends a relationship-distinct path of length in [1, upper] from a iff b ends a walk of
+ * that length -- cutting the stretch between two uses of a repeated relationship leaves a shorter walk from a to b
+ * that keeps one relationship -- so the distinct ends are plain bounded reachability.
+ * lower >= 2 is CAPSMI_ERR_NOT_IMPLEMENTED (the lemma fails there: use the join plan).
+ * lower = 0 adds the zero-length path of every a_ok node (copyEntity, VarLengthExpandPlanner.scala:146-153,
+ * 190-210: b is a copy of a, without b's node scan), so a counts itself whatever b_ok(a) says, and once only when
+ * a cycle also returns to it.  Relationships with an endpoint outside the bitmaps' id domain are ignored.  One
+ * output row per a with a non-empty set, in no particular order.  a_ok and b_ok must share one id domain. */
+capsmi_status capsmi_var_length_count_distinct(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                               const char* src_col, const char* dst_col, const capsmi_bitmap* a_ok,
+                                               const capsmi_bitmap* b_ok, int32_t lower, int32_t upper,
+                                               const char* id_name, const char* count_name, capsmi_table** out);
+/* The ungrouped form: MATCH (a)-[r*lower..upper]->(b) WHERE a_ok(a) AND b_ok(b) RETURN count(DISTINCT b), the size
+ * of the union of the per-a sets above: one BFS from all of a_ok.  The same lemma (walks and relationship-distinct
+ * paths of length in [1, upper] end at the same nodes for lower <= 1; lower >= 2 is CAPSMI_ERR_NOT_IMPLEMENTED)
+ * and the same lower = 0 rule: every a_ok node counts, whatever b_ok says of it, once. */
+capsmi_status capsmi_var_length_reach_count(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                            const char* src_col, const char* dst_col, const capsmi_bitmap* a_ok,
+                                            const capsmi_bitmap* b_ok, int32_t lower, int32_t upper,
+                                            int64_t* out_distinct);
 /* Sharded form of capsmi_var_length_count for one rank of a multi-GPU run.  The
  * rank owns the source ids [own_lo, own_hi); `out_rels` hold the relationships whose source it
  * owns, `in_rels` those from other ranks' sources into its owned ids.  `od` and `y` are caller

@@ -340,6 +340,11 @@ trait CapsmiLib extends Library {
   def capsmi_var_length_count(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String, dstCol: String, a: Pointer,
                               b: Pointer, lower: Int, upper: Int, idName: String, countName: String,
                               out: PointerByReference): Int
+  def capsmi_var_length_count_distinct(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String, dstCol: String,
+                                       a: Pointer, b: Pointer, lower: Int, upper: Int, idName: String,
+                                       countName: String, out: PointerByReference): Int
+  def capsmi_var_length_reach_count(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String, dstCol: String,
+                                    a: Pointer, b: Pointer, lower: Int, upper: Int, out: LongByReference): Int
 
   // ingest (EdgeListDataSource / FSGraphSource CSV)
   def capsmi_read_csv(s: Pointer, nfiles: Int, paths: Array[String], delimiter: Byte, comment: Byte, ncols: Int,
