@@ -206,6 +206,33 @@ def var_length_reach_count(session: Session, rels: Sequence[GpuTable], a_ok: Nod
     return out.value
 
 
+def var_length_collect_distinct(session: Session, rels: Sequence[GpuTable], a_ok: NodeBitmap, b_ok: NodeBitmap,
+                                lower: int, upper: int, id_name: str = "id", list_name: str = "list",
+                                count_name: Optional[str] = None, src_col: str = "source",
+                                dst_col: str = "target") -> GpuTable:
+    """``MATCH (a)-[*lower..upper]->(b) WHERE a_ok(a) AND b_ok(b) RETURN id(a), collect(DISTINCT b)``: lower 0 or 1,
+    any upper >= 1.  One row per a with a non-empty list; the lists hold the absolute ids, strictly ascending
+    (``sort_array(collect_set(id(b)))``).  With `count_name` the table also carries ``count(DISTINCT b)``.  More
+    elements than ``CAPSMI_REACH_LIST_LIMIT`` raise UnsupportedOperationException."""
+    out = ctypes.c_void_p()
+    _lib.call("capsmi_var_length_collect_distinct", session.handle, len(rels), _handles(rels), src_col.encode(),
+              dst_col.encode(), a_ok.handle, b_ok.handle, lower, upper, id_name.encode(), list_name.encode(),
+              None if count_name is None else count_name.encode(), ctypes.byref(out))
+    return GpuTable(session, out)
+
+
+def var_length_reach_list(session: Session, rels: Sequence[GpuTable], a_ok: NodeBitmap, b_ok: NodeBitmap,
+                          lower: int, upper: int, src_col: str = "source", dst_col: str = "target") -> np.ndarray:
+    """``MATCH (a)-[*lower..upper]->(b) WHERE a_ok(a) AND b_ok(b) RETURN collect(DISTINCT b)`` (lower 0 or 1): the
+    ascending ids of the union of the per-a lists, as an int64 array (empty when nothing is reached)."""
+    import numpy as np
+    out = ctypes.c_void_p()
+    _lib.call("capsmi_var_length_reach_list", session.handle, len(rels), _handles(rels), src_col.encode(),
+              dst_col.encode(), a_ok.handle, b_ok.handle, lower, upper, b"list", ctypes.byref(out))
+    t = GpuTable(session, out)
+    return np.asarray(t.column("list").values[0], dtype=np.int64)
+
+
 class VarlenShard:
     """One rank's share of the var-length grouped count (multi-GPU C5; include/capsmi.h
     capsmi_varlen_shard_*).  The rank owns source ids [own_lo, own_hi); `out_rels` are the

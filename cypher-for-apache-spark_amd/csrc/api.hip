@@ -539,6 +539,10 @@ bool apply(Config& c, const std::string& name, const char* v) {
     } else if (name == "CAPSMI_REACH") {
         if (!parse_choice(v, {"sliced", "flat"}, k)) return false;
         c.reach_flat = k == 1;
+    } else if (name == "CAPSMI_REACH_LIST_LIMIT") {
+        if (v && std::string(v) == "auto") x = 0;
+        else if (!parse_int(v, 1, int64_t(1) << 62, x)) return false;
+        c.reach_list_limit = x;
     } else if (name == "CAPSMI_COLL_CHUNK") {
         if (!parse_int(v, 1, int64_t(1) << 40, x)) return false;
         c.coll_chunk = x;
@@ -568,7 +572,8 @@ const std::pair<const char*, const char*> kKnobs[] = {
     {"CAPSMI_VL_F2", "0"},           {"CAPSMI_COLL_CHUNK", "67108864"}, {"CAPSMI_INGEST_THREADS", "0"},
     {"CAPSMI_HOP2", "auto"},         {"CAPSMI_POOL", "split"},       {"CAPSMI_STR_MATCH", "auto"},
     {"CAPSMI_HOP2_EXCHANGE", "on"},  {"CAPSMI_NARROW", "auto"},      {"CAPSMI_TRI_UND_COUNT", "hash"},
-    {"CAPSMI_PRESENCE", "auto"},     {"CAPSMI_REACH_WORDS", "auto"}, {"CAPSMI_REACH", "sliced"}};
+    {"CAPSMI_PRESENCE", "auto"},     {"CAPSMI_REACH_WORDS", "auto"}, {"CAPSMI_REACH", "sliced"},
+    {"CAPSMI_REACH_LIST_LIMIT", "auto"}};
 }  // namespace
 
 Config config_from_env() {
@@ -2193,6 +2198,78 @@ capsmi_status capsmi_var_length_reach_count(capsmi_session* s, int32_t nrels, ca
     reach_args(s, nrels, rels, src_col, dst_col, a_ok, b_ok, lower, upper, r);
     *out_distinct = var_length_reach_count(s, r.srcs.data(), r.dsts.data(), r.ms.data(), nrels, a_ok, b_ok, lower, upper,
                                            r.nar.data());
+    API_END
+}
+
+capsmi_status capsmi_var_length_collect_distinct(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                                 const char* src_col, const char* dst_col, const capsmi_bitmap* a_ok,
+                                                 const capsmi_bitmap* b_ok, int32_t lower, int32_t upper,
+                                                 const char* id_name, const char* list_name, const char* count_name,
+                                                 capsmi_table** out) {
+    API_BEGIN
+    need(s, "session");
+    need(out, "out");
+    need(id_name, "id_name");
+    need(list_name, "list_name");
+    ReachArgs r;
+    reach_args(s, nrels, rels, src_col, dst_col, a_ok, b_ok, lower, upper, r);
+    const std::string idn(id_name), ln(list_name);
+    REQUIRE(idn != ln && (!count_name || (idn != count_name && ln != count_name)), CAPSMI_ERR_ILLEGAL_ARGUMENT,
+            "output names must differ");
+    Buf ids, cnt, sel;
+    std::shared_ptr<ListStore> lists;
+    const int64_t rows = var_length_reach_lists(s, r.srcs.data(), r.dsts.data(), r.ms.data(), nrels, a_ok, b_ok, lower,
+                                                upper, ids, cnt, sel, lists, r.nar.data());
+    auto* o = new_table(s, rows);
+    Column a, l;
+    a.name = idn;
+    a.type = CAPSMI_I64;
+    a.data = ids;
+    l.name = ln;
+    l.type = CAPSMI_LIST_I64;
+    l.data = sel;  // row r holds the list of its source: the row word is the source's index
+    l.list = lists;
+    o->cols.push_back(std::move(a));
+    o->cols.push_back(std::move(l));
+    if (count_name) {
+        Column c;
+        c.name = count_name;
+        c.type = CAPSMI_I64;
+        c.data = cnt;
+        o->cols.push_back(std::move(c));
+    }
+    *out = o;
+    API_END
+}
+
+capsmi_status capsmi_var_length_reach_list(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                           const char* src_col, const char* dst_col, const capsmi_bitmap* a_ok,
+                                           const capsmi_bitmap* b_ok, int32_t lower, int32_t upper,
+                                           const char* list_name, capsmi_table** out) {
+    API_BEGIN
+    need(s, "session");
+    need(out, "out");
+    need(list_name, "list_name");
+    ReachArgs r;
+    reach_args(s, nrels, rels, src_col, dst_col, a_ok, b_ok, lower, upper, r);
+    auto L = std::make_shared<ListStore>();
+    L->elem = CAPSMI_I64;
+    L->nlists = 1;
+    L->nvalues = var_length_reach_list(s, r.srcs.data(), r.dsts.data(), r.ms.data(), nrels, a_ok, b_ok, lower, upper,
+                                       L->values, r.nar.data());
+    const int64_t ends[2] = {0, L->nvalues};
+    L->offsets = dev_alloc(sizeof(ends), s);
+    HIP_CHECK(hipMemcpyAsync(P<void>(L->offsets), ends, sizeof(ends), hipMemcpyHostToDevice, s->stream));
+    HIP_CHECK(hipStreamSynchronize(s->stream));  // `ends` leaves scope
+    auto* o = new_table(s, 1);
+    Column l;
+    l.name = list_name;
+    l.type = CAPSMI_LIST_I64;
+    l.data = dev_alloc(sizeof(int64_t), s);
+    fill_i64(P<int64_t>(l.data), 0, 1, s->stream);  // the one row holds list 0
+    l.list = L;
+    o->cols.push_back(std::move(l));
+    *out = o;
     API_END
 }
 

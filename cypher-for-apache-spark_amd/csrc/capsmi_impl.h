@@ -195,6 +195,9 @@ struct Config {
                                   //   grouped var-length count(DISTINCT b), i.e. 64 sources per word and batch (k_reach.hip)
     bool reach_flat = false;      // CAPSMI_REACH = sliced | flat: flat forces the global-OR level pass (the form of
                                   //   domains beyond the target-sliced LDS pass)
+    int64_t reach_list_limit = 0; // CAPSMI_REACH_LIST_LIMIT = auto | elements (0 = auto): the most list elements a
+                                  //   var-length collect(DISTINCT b) may produce (auto: device memory / 16 B, the
+                                  //   route's peak per element); beyond it the query is CAPSMI_ERR_UNSUPPORTED
     int64_t coll_chunk = int64_t(1) << 26;  // CAPSMI_COLL_CHUNK: elements per host collective call
     int ingest_threads = 0;       // CAPSMI_INGEST_THREADS (0: OMP_NUM_THREADS, else up to 16 hardware threads)
     bool narrow = true;           // CAPSMI_NARROW = auto | off: registering a relationship table whose endpoints span at most
@@ -770,6 +773,17 @@ int64_t var_length_reach_rows(capsmi_session* s, const int64_t* const* srcs, con
 int64_t var_length_reach_count(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts,
                                const int64_t* ms, int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower,
                                int upper, const NarrowRel* nar = nullptr);
+// var-length collect(DISTINCT b) (k_reach.hip): the rows above with D(a) itself, read off each batch's bit matrix.
+// List k of `lists` is D of the k-th a_ok node in id order, strictly ascending absolute ids (empty lists included,
+// which no row names); out_sel holds the rows' list indices.  CAPSMI_REACH_LIST_LIMIT bounds the elements.
+int64_t var_length_reach_lists(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
+                               int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower, int upper,
+                               Buf& out_ids, Buf& out_cnt, Buf& out_sel, std::shared_ptr<ListStore>& lists,
+                               const NarrowRel* nar = nullptr);
+// the global form: U_a D(a) as ascending absolute ids (returns their number)
+int64_t var_length_reach_list(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
+                              int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower, int upper,
+                              Buf& out_vals, const NarrowRel* nar = nullptr);
 // sharded var-length grouped count (multi-GPU C5; k_varlen.hip): begin -> caller sums od over ranks
 // -> mid -> caller sums Y -> finish (rows of owned ids)
 struct VarlenShard;

@@ -1,4 +1,5 @@
-// k_reach.hip -- count(DISTINCT b) over a bounded var-length expand: k-hop reach by bit-parallel BFS.
+// k_reach.hip -- count(DISTINCT b) and collect(DISTINCT b) over a bounded var-length expand: k-hop reach by
+// bit-parallel BFS, and the reach lists read off its bit matrix (the last section).
 //
 //   MATCH (a)-[r*lower..upper]->(b) WHERE a_ok(a) AND b_ok(b) RETURN id(a), count(DISTINCT b)   (grouped)
 //   MATCH (a)-[r*lower..upper]->(b) WHERE a_ok(a) AND b_ok(b) RETURN count(DISTINCT b)          (global)
@@ -32,6 +33,7 @@ using part::ChunkWalk;
 constexpr int kBlock = 1024;
 constexpr int kLdsWords = 16384;  // 128 KiB of `next` words per block: 16384 / NW ids per slice
 constexpr int kMaxWords = 8;
+constexpr int kListTile = 256;  // nodes per extraction tile of the reach lists (a multiple of 64)
 
 inline int grid(const capsmi_session* s, int64_t n) {
     int64_t g = (n + 255) / 256;
@@ -383,19 +385,20 @@ inline int64_t sliced_max(int nwords) {
 
 }  // namespace reach
 
-// |U_a D(a)|: one BFS from all of a_ok
-int64_t var_length_reach_count(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts,
-                               const int64_t* ms, int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower,
-                               int upper, const NarrowRel* nar) {
-    using namespace reach;
+namespace reach {
+// The BFS of the global form from all of a_ok (n > 0): maps holds the three bitmaps F, R, N of nw words each, R the
+// nodes reached in 1..upper relationships; tot[0] counts those of them in b_ok.
+void reach_global(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms, int nt,
+                  const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int upper, const NarrowRel* nar, Buf& maps,
+                  Buf& tot) {
     hipStream_t st = s->stream;
     const int64_t n = b_ok->hi - b_ok->lo, lo = b_ok->lo;
-    if (n <= 0) return 0;
     const int64_t nw = (n + 31) / 32;
     const uint32_t* aw = P<uint32_t>(a_ok->words);
     const uint32_t* bw = P<uint32_t>(b_ok->words);
     const int a_full = a_ok->full ? 1 : 0, b_full = b_ok->full ? 1 : 0;
-    Buf maps = dev_alloc(sizeof(uint32_t) * 3 * (size_t)nw, s), tot = dev_alloc(2 * sizeof(u64), s);
+    maps = dev_alloc(sizeof(uint32_t) * 3 * (size_t)nw, s);
+    tot = dev_alloc(2 * sizeof(u64), s);
     uint32_t *F = P<uint32_t>(maps), *R = F + nw, *N = R + nw;
     HIP_CHECK(hipMemsetAsync(P<void>(tot), 0, 2 * sizeof(u64), st));
     hipLaunchKernelGGL(k_rc_init, dim3(grid(s, nw)), dim3(256), 0, st, aw, a_full, n, nw, F, R, N);
@@ -426,35 +429,60 @@ int64_t var_length_reach_count(capsmi_session* s, const int64_t* const* srcs, co
             before = now;
         }
     }
+    HIP_CHECK(hipGetLastError());
+}
+}  // namespace reach
+
+// |U_a D(a)|: one BFS from all of a_ok
+int64_t var_length_reach_count(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts,
+                               const int64_t* ms, int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower,
+                               int upper, const NarrowRel* nar) {
+    using namespace reach;
+    const int64_t n = b_ok->hi - b_ok->lo;
+    if (n <= 0) return 0;
+    const int64_t nw = (n + 31) / 32;
+    Buf maps, tot;
+    reach_global(s, srcs, dsts, ms, nt, a_ok, b_ok, upper, nar, maps, tot);
     if (lower == 0)
-        hipLaunchKernelGGL(k_rc_zero, dim3(grid(s, nw)), dim3(256), 0, st, n, nw, R, aw, a_full, bw, b_full, P<u64>(tot));
+        hipLaunchKernelGGL(k_rc_zero, dim3(grid(s, nw)), dim3(256), 0, s->stream, n, nw, P<uint32_t>(maps) + nw,
+                           P<uint32_t>(a_ok->words), a_ok->full ? 1 : 0, P<uint32_t>(b_ok->words), b_ok->full ? 1 : 0,
+                           P<u64>(tot));
     HIP_CHECK(hipGetLastError());
     return read_scalar(s, P<int64_t>(tot));
 }
 
-// rows (a, |D(a)|) of the a_ok nodes with a non-empty D(a); returns the row count
-int64_t var_length_reach_rows(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
-                              int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower, int upper,
-                              Buf& out_ids, Buf& out_cnt, const NarrowRel* nar) {
-    using namespace reach;
+namespace reach {
+
+// a finished batch of the grouped walk, handed to the caller while its bit matrix is live: the levels and the
+// zero-length rule have run, so cnts[base .. base + bwid) are final
+struct Batch {
+    int64_t base;        // the batch's first source: an index into the source list and the counts
+    int bwid, nwords;    // sources of the batch, words per node
+    const int64_t* idx;  // the batch's sources (relative ids, ascending)
+    u64* seen;           // seen[v * nwords + w]: bit j = source 64 w + j reaches v in 1..upper relationships
+    u64 *fa, *fb;        // the two frontier buffers, n * nwords words each, free from here on
+};
+
+// The front that the grouped count and the grouped collect share: the source list, the width, the target partition
+// and the batch loop.  `after(batch)` runs once per batch, after its levels and k_rg_zero.  Returns the number of
+// sources A; idx holds them, cnts their |D(a)| (plus padding).
+template <class After>
+int64_t reach_batches(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms, int nt,
+                      const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower, int upper, const NarrowRel* nar,
+                      Buf& idx, Buf& cnts, After&& after) {
     hipStream_t st = s->stream;
     const int64_t n = b_ok->hi - b_ok->lo, lo = b_ok->lo;
     const uint32_t* aw = P<uint32_t>(a_ok->words);
     const uint32_t* bw = P<uint32_t>(b_ok->words);
     const int a_full = a_ok->full ? 1 : 0, b_full = b_ok->full ? 1 : 0;
     // the sources in id order (relative ids): the one read-back before the levels
-    Buf idx;
     int64_t A = 0;
     if (n > 0) {
         Buf fl = dev_alloc((size_t)n, s);
         hipLaunchKernelGGL(k_rg_flags, dim3(grid(s, n)), dim3(256), 0, st, aw, a_full, n, P<uint8_t>(fl));
         A = flags_to_indices(s, P<uint8_t>(fl), n, idx);
     }
-    if (A == 0) {
-        out_ids = dev_alloc(8, s);
-        out_cnt = dev_alloc(8, s);
-        return 0;
-    }
+    if (A == 0) return 0;
     int64_t mtot = 0;
     for (int i = 0; i < nt; ++i) mtot += ms[i] > 0 ? ms[i] : 0;
     // words per node: the knob, or auto: the narrowest width that takes all sources in one
@@ -494,8 +522,8 @@ int64_t var_length_reach_rows(capsmi_session* s, const int64_t* const* srcs, con
         lds_attr(reinterpret_cast<const void*>(k_rg_level<8>), lds);
     }
     const size_t words = (size_t)n * W;
-    Buf state = dev_alloc(sizeof(u64) * 3 * words, s), cnts = dev_alloc(sizeof(u64) * (size_t)(A + 64 * kMaxWords), s),
-        tot = dev_alloc(sizeof(u64), s);
+    Buf state = dev_alloc(sizeof(u64) * 3 * words, s), tot = dev_alloc(sizeof(u64), s);
+    cnts = dev_alloc(sizeof(u64) * (size_t)(A + 64 * kMaxWords), s);
     HIP_CHECK(hipMemsetAsync(P<void>(cnts), 0, sizeof(u64) * (size_t)(A + 64 * kMaxWords), st));
     HIP_CHECK(hipMemsetAsync(P<void>(tot), 0, sizeof(u64), st));
     u64 *seen = P<u64>(state), *fa = seen + words, *fb = fa + words;
@@ -528,9 +556,22 @@ int64_t var_length_reach_rows(capsmi_session* s, const int64_t* const* srcs, con
         }
         if (lower == 0)
             hipLaunchKernelGGL(k_rg_zero, dim3((bwid + 255) / 256), dim3(256), 0, st, bidx, bwid, NWb, seen, bw, b_full, bcnt);
+        after(Batch{base, bwid, NWb, bidx, seen, fa, fb});
     }
     HIP_CHECK(hipGetLastError());
-    Buf rf = dev_alloc((size_t)A, s), sel;
+    return A;
+}
+
+// the rows of the sources with a non-empty D(a): their ids and counts, and (sel) their indices into the source list
+int64_t reach_rows_out(capsmi_session* s, const Buf& idx, const Buf& cnts, int64_t A, int64_t lo, Buf& out_ids,
+                       Buf& out_cnt, Buf& sel) {
+    hipStream_t st = s->stream;
+    if (A == 0) {
+        out_ids = dev_alloc(8, s);
+        out_cnt = dev_alloc(8, s);
+        return 0;
+    }
+    Buf rf = dev_alloc((size_t)A, s);
     hipLaunchKernelGGL(k_rg_rowflags, dim3(grid(s, A)), dim3(256), 0, st, P<u64>(cnts), A, P<uint8_t>(rf));
     const int64_t rows = flags_to_indices(s, P<uint8_t>(rf), A, sel);  // the read-back of the row count
     out_ids = dev_alloc(sizeof(int64_t) * (size_t)(rows > 0 ? rows : 1), s);
@@ -540,6 +581,274 @@ int64_t var_length_reach_rows(capsmi_session* s, const int64_t* const* srcs, con
                            P<u64>(cnts), P<int64_t>(out_ids), P<int64_t>(out_cnt));
     HIP_CHECK(hipGetLastError());
     return rows;
+}
+
+}  // namespace reach
+
+// rows (a, |D(a)|) of the a_ok nodes with a non-empty D(a); returns the row count
+int64_t var_length_reach_rows(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
+                              int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower, int upper,
+                              Buf& out_ids, Buf& out_cnt, const NarrowRel* nar) {
+    using namespace reach;
+    Buf idx, cnts, sel;
+    const int64_t A = reach_batches(s, srcs, dsts, ms, nt, a_ok, b_ok, lower, upper, nar, idx, cnts, [](const Batch&) {});
+    return reach_rows_out(s, idx, cnts, A, b_ok->lo, out_ids, out_cnt, sel);
+}
+
+// ---- collect(DISTINCT b): the reach lists ------------------------------------------------------------------
+// D(a) as one strictly ascending id list per source, read off a batch's bit matrix while it is live.  The hit
+// matrix hit(v, j) = (bit j of seen[v] and b_ok(v)) or (lower = 0 and v = idx[j]) is written word-major
+// (hit[w * n + v]) into a free frontier buffer, so the 64 lanes of a wave read 64 consecutive nodes' words of
+// one source word w.  A wave owns a unit: the tile of kListTile consecutive nodes, for one word w, and steps
+// through it 64 nodes at a time.  Per set bit j of the wave's OR of its 64 words, the ballot of bit j is the set
+// of lanes (nodes) that source 64 w + j reaches: its popcount is the source's count in this step (pass 1), and
+// the popcount below a lane is the lane's rank (pass 2).  Lane j keeps the running count of source 64 w + j in a
+// register (read by readlane with the wave-uniform j), so the walk needs neither LDS nor atomics, and the element
+// order falls out of it: tiles, steps and lanes all ascend in the node id.  Pass 1 leaves one count per (unit,
+// lane); a column scan over the tiles turns them into each tile's base per source and each source's length; pass
+// 2 repeats the walk from offset + base.  Lengths, offsets and positions all come from the same walk over the
+// same words, so a store cannot leave its list.
+namespace reach {
+
+constexpr int kListBlock = 256;  // 4 waves, one unit each at a time
+
+__global__ void k_rl_hit(int64_t n, int nwords, const u64* __restrict__ seen, const uint32_t* __restrict__ bw, int b_full,
+                         u64* __restrict__ hit) {
+    for (int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; v < n; v += (int64_t)gridDim.x * blockDim.x) {
+        const bool bk = bit_of(bw, b_full, (uint64_t)v);
+        for (int w = 0; w < nwords; ++w) hit[(size_t)w * n + v] = bk ? seen[(size_t)v * nwords + w] : 0ULL;
+    }
+}
+
+// lower = 0: source j holds itself (the batch's sources are distinct nodes: one thread per word touched)
+__global__ void k_rl_self(const int64_t* __restrict__ idx, int bw, int64_t n, u64* __restrict__ hit) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < bw) hit[(size_t)(j >> 6) * n + idx[j]] |= 1ULL << (j & 63);
+}
+
+__device__ __forceinline__ int64_t readlane64(int64_t x, int j) {  // j wave-uniform
+    const uint32_t l = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, j);
+    const uint32_t h = (uint32_t)__builtin_amdgcn_readlane((int)((u64)x >> 32), j);
+    return (int64_t)(((u64)h << 32) | l);
+}
+
+// WRITE = false (pass 1): tcol[unit * 64 + j] = nodes of the unit's tile that source 64 w + j holds.
+// WRITE = true (pass 2): tcol holds the tile bases; node lo + v goes to vals[offs[source] + base + rank].
+template <bool WRITE>
+__global__ void __launch_bounds__(kListBlock) k_rl_walk(int64_t n, int64_t ntiles, int nwords, int bwid,
+                                                        const u64* __restrict__ hit, uint32_t* __restrict__ tcol,
+                                                        const int64_t* __restrict__ offs, int64_t lo,
+                                                        int64_t* __restrict__ vals) {
+    const int lane = threadIdx.x & 63;
+    const int64_t units = ntiles * nwords;
+    for (int64_t u = (int64_t)blockIdx.x * (kListBlock / 64) + (threadIdx.x >> 6); u < units;
+         u += (int64_t)gridDim.x * (kListBlock / 64)) {  // wave-uniform
+        const int64_t tile = u / nwords;
+        const int w = (int)(u - tile * nwords);
+        // lane j: pass 1, the running count of source 64 w + j; pass 2, where its next element goes
+        int64_t pos = 0;
+        if (WRITE) pos = (w * 64 + lane < bwid ? offs[w * 64 + lane] : 0) + (int64_t)tcol[u * 64 + lane];
+        const u64* hw = hit + (size_t)w * n;
+        for (int step = 0; step < kListTile / 64; ++step) {
+            const int64_t v = tile * kListTile + step * 64 + lane;
+            const u64 x = v < n ? hw[v] : 0ULL;
+            if (!__any(x != 0)) continue;
+            u64 m = wave_or(x);
+            m = ((u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)(m >> 32)) << 32) |
+                (u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m);
+            while (m) {  // wave-uniform
+                const int j = __ffsll((long long)m) - 1;
+                m &= m - 1;
+                const bool on = (x >> j) & 1ULL;
+                const u64 bal = __ballot(on);
+                if (WRITE) {
+                    const int64_t p = readlane64(pos, j);
+                    const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
+                    if (on) vals[p + below] = lo + v;
+                }
+                if (lane == j) pos += __popcll(bal);
+            }
+        }
+        if (!WRITE) tcol[u * 64 + lane] = (uint32_t)pos;
+    }
+}
+
+// per source column t of the batch: tcol[tile][t] becomes the count of the tiles before, lens[t] the total
+__global__ void k_rl_colscan(int64_t ntiles, int ncols, int bwid, uint32_t* __restrict__ tcol, int64_t* __restrict__ lens) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ncols) return;
+    uint32_t acc = 0;
+    for (int64_t i = 0; i < ntiles; ++i) {
+        const uint32_t c = tcol[i * ncols + t];
+        tcol[i * ncols + t] = acc;
+        acc += c;
+    }
+    if (t < bwid) lens[t] = (int64_t)acc;
+}
+
+// global form: word i of the answer = R & b_ok, with a_ok for lower = 0; cnt[i] its bits
+__global__ void k_rc_listwords(int64_t n, int64_t nw, const uint32_t* __restrict__ R, const uint32_t* __restrict__ aw,
+                               int a_full, const uint32_t* __restrict__ bw, int b_full, int lower, uint32_t* __restrict__ out,
+                               int64_t* __restrict__ cnt) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nw; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t left = n - 32 * i;
+        const uint32_t in = left >= 32 ? 0xFFFFFFFFu : ((1u << left) - 1u);
+        uint32_t x = R[i] & (b_full ? 0xFFFFFFFFu : bw[i]);
+        if (lower == 0) x |= a_full ? 0xFFFFFFFFu : aw[i];
+        x &= in;
+        out[i] = x;
+        cnt[i] = __popc(x);
+    }
+}
+
+__global__ void k_rc_listwrite(int64_t nw, const uint32_t* __restrict__ words, const int64_t* __restrict__ offs, int64_t lo,
+                               int64_t* __restrict__ vals) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nw; i += (int64_t)gridDim.x * blockDim.x) {
+        uint32_t x = words[i];
+        int64_t o = offs[i];
+        while (x) {
+            vals[o++] = lo + 32 * i + (__ffs((int)x) - 1);
+            x &= x - 1;
+        }
+    }
+}
+
+// CAPSMI_REACH_LIST_LIMIT in elements; auto: what fits the device's memory at the 16 B per element of the peak (the
+// batches' buffers and the joined store side by side)
+inline int64_t list_limit(capsmi_session* s) {
+    if (s->cfg.reach_list_limit > 0) return s->cfg.reach_list_limit;
+    size_t free_b = 0, total_b = 0;
+    HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+    return (int64_t)(total_b / 16);
+}
+
+inline void check_list_limit(int64_t elems, int64_t limit) {
+    REQUIRE(elems <= limit, CAPSMI_ERR_UNSUPPORTED,
+            "var-length collect(DISTINCT b): the lists reach " + std::to_string(elems) +
+                " elements, above CAPSMI_REACH_LIST_LIMIT = " + std::to_string(limit));
+}
+
+}  // namespace reach
+
+// rows (a, |D(a)|, D(a)) of the a_ok nodes with a non-empty D(a): list k of the store is D of source k (empty lists
+// included, which no row names), out_sel the rows' list indices
+int64_t var_length_reach_lists(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
+                               int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower, int upper,
+                               Buf& out_ids, Buf& out_cnt, Buf& out_sel, std::shared_ptr<ListStore>& lists,
+                               const NarrowRel* nar) {
+    using namespace reach;
+    hipStream_t st = s->stream;
+    const int64_t n = b_ok->hi - b_ok->lo, lo = b_ok->lo;
+    REQUIRE(n < (int64_t(1) << 32), CAPSMI_ERR_UNSUPPORTED, "var-length collect(DISTINCT b): at most 2^32 - 1 ids");
+    const int64_t limit = list_limit(s);
+    const uint32_t* bw = P<uint32_t>(b_ok->words);
+    const int b_full = b_ok->full ? 1 : 0;
+    const int64_t ntiles = (n + kListTile - 1) / kListTile;
+    Buf tcol = dev_alloc(sizeof(uint32_t) * (size_t)std::max<int64_t>(ntiles, 1) * 64 * kMaxWords, s);
+    Buf boffs = dev_alloc(sizeof(int64_t) * (64 * kMaxWords + 1), s);
+    Buf lens;  // int64 per source, sized once the sources are known
+    std::vector<std::pair<Buf, int64_t>> parts;  // a values buffer per batch
+    int64_t total = 0;
+    Buf idx, cnts;
+    const int64_t A = reach_batches(s, srcs, dsts, ms, nt, a_ok, b_ok, lower, upper, nar, idx, cnts, [&](const Batch& b) {
+        if (!lens) lens = dev_alloc(sizeof(int64_t) * (size_t)n, s);  // at most n sources
+        const int64_t units = ntiles * b.nwords;
+        const int wgrid = (int)std::min<int64_t>((units + kListBlock / 64 - 1) / (kListBlock / 64), (int64_t)s->num_cus * 32);
+        const double hit_bytes = (double)n * b.nwords * 8, col_bytes = (double)units * 64 * 4;
+        int64_t* blen = P<int64_t>(lens) + b.base;
+        {
+            KernelTimer kt(s, "reach_list_starts");
+            hipLaunchKernelGGL(k_rl_hit, dim3(grid(s, n)), dim3(256), 0, st, n, b.nwords, b.seen, bw, b_full, b.fa);
+            if (lower == 0)
+                hipLaunchKernelGGL(k_rl_self, dim3((b.bwid + 255) / 256), dim3(256), 0, st, b.idx, b.bwid, n, b.fa);
+        }
+        {
+            KernelTimer kt(s, "reach_list_count", hit_bytes + col_bytes);
+            hipLaunchKernelGGL(k_rl_walk<false>, dim3(wgrid), dim3(kListBlock), 0, st, n, ntiles, b.nwords, b.bwid, b.fa,
+                               P<uint32_t>(tcol), (const int64_t*)nullptr, lo, (int64_t*)nullptr);
+        }
+        {
+            KernelTimer kt(s, "reach_list_starts");
+            hipLaunchKernelGGL(k_rl_colscan, dim3(b.nwords), dim3(64), 0, st, ntiles, b.nwords * 64, b.bwid,
+                               P<uint32_t>(tcol), blen);
+            exclusive_scan_i64(blen, P<int64_t>(boffs), b.bwid, s);
+        }
+        HIP_CHECK(hipGetLastError());
+        const int64_t elems = read_scalar(s, P<int64_t>(boffs) + b.bwid);  // the batch's total: 8 bytes back
+        check_list_limit(total + elems, limit);                            // before the batch is written
+        Buf vals = dev_alloc(sizeof(int64_t) * (size_t)(elems > 0 ? elems : 1), s);
+        if (elems > 0) {
+            KernelTimer kt(s, "reach_list_write", 8.0 * (double)elems + hit_bytes + col_bytes);
+            hipLaunchKernelGGL(k_rl_walk<true>, dim3(wgrid), dim3(kListBlock), 0, st, n, ntiles, b.nwords, b.bwid, b.fa,
+                               P<uint32_t>(tcol), P<int64_t>(boffs), lo, P<int64_t>(vals));
+        }
+        parts.emplace_back(vals, elems);
+        total += elems;
+    });
+    const int64_t rows = reach_rows_out(s, idx, cnts, A, lo, out_ids, out_cnt, out_sel);
+    if (!out_sel) out_sel = dev_alloc(8, s);
+    auto L = std::make_shared<ListStore>();
+    L->elem = CAPSMI_I64;
+    L->nlists = A;
+    L->nvalues = total;
+    L->offsets = dev_alloc(sizeof(int64_t) * (size_t)(A + 1), s);
+    if (A > 0) {
+        KernelTimer kt(s, "reach_list_starts");
+        exclusive_scan_i64(P<int64_t>(lens), P<int64_t>(L->offsets), A, s);
+    } else {
+        HIP_CHECK(hipMemsetAsync(P<void>(L->offsets), 0, sizeof(int64_t), st));
+    }
+    if (parts.size() == 1) {
+        L->values = parts[0].first;  // one batch: its buffer is the store
+    } else {
+        L->values = dev_alloc(sizeof(int64_t) * (size_t)(total > 0 ? total : 1), s);
+        int64_t at = 0;
+        for (auto& p : parts) {  // batch order is source order: the joined values follow the offsets
+            if (p.second)
+                HIP_CHECK(hipMemcpyAsync(P<int64_t>(L->values) + at, P<int64_t>(p.first), sizeof(int64_t) * (size_t)p.second,
+                                         hipMemcpyDeviceToDevice, st));
+            at += p.second;
+        }
+    }
+    lists = L;
+    return rows;
+}
+
+// the ascending ids of U_a D(a) (returns their number)
+int64_t var_length_reach_list(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
+                              int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower, int upper,
+                              Buf& out_vals, const NarrowRel* nar) {
+    using namespace reach;
+    hipStream_t st = s->stream;
+    const int64_t n = b_ok->hi - b_ok->lo, lo = b_ok->lo;
+    if (n <= 0) {
+        out_vals = dev_alloc(8, s);
+        return 0;
+    }
+    const int64_t limit = list_limit(s);
+    const int64_t nw = (n + 31) / 32;
+    Buf maps, tot;
+    reach_global(s, srcs, dsts, ms, nt, a_ok, b_ok, upper, nar, maps, tot);
+    uint32_t *F = P<uint32_t>(maps), *R = F + nw;  // F is free after the levels: it takes the answer's words
+    Buf cnt = dev_alloc(sizeof(int64_t) * (size_t)nw, s), offs = dev_alloc(sizeof(int64_t) * (size_t)(nw + 1), s);
+    int64_t elems = 0;
+    {
+        KernelTimer kt(s, "reach_list_starts");
+        hipLaunchKernelGGL(k_rc_listwords, dim3(grid(s, nw)), dim3(256), 0, st, n, nw, R, P<uint32_t>(a_ok->words),
+                           a_ok->full ? 1 : 0, P<uint32_t>(b_ok->words), b_ok->full ? 1 : 0, lower, F, P<int64_t>(cnt));
+        exclusive_scan_i64(P<int64_t>(cnt), P<int64_t>(offs), nw, s);
+    }
+    HIP_CHECK(hipGetLastError());
+    elems = read_scalar(s, P<int64_t>(offs) + nw);
+    check_list_limit(elems, limit);
+    out_vals = dev_alloc(sizeof(int64_t) * (size_t)(elems > 0 ? elems : 1), s);
+    if (elems > 0) {
+        KernelTimer kt(s, "reach_list_write", 8.0 * (double)elems + 12.0 * (double)nw);
+        hipLaunchKernelGGL(k_rc_listwrite, dim3(grid(s, nw)), dim3(256), 0, st, nw, F, P<int64_t>(offs), lo,
+                           P<int64_t>(out_vals));
+    }
+    HIP_CHECK(hipGetLastError());
+    return elems;
 }
 
 }  // namespace capsmi

@@ -1867,22 +1867,34 @@ bool fused_var_length(capsmi_session* s, const capsmi_table* in, const PlanNode&
     return true;
 }
 
-// count(DISTINCT end node) over the branches of a bounded var-length expand, grouped by the start node
-// (g.a = the start's id-like column) or alone (g.a empty): k-hop reach (k_reach.hip).  Lengths lower..upper
-// contiguous with lower in {0, 1} and any upper; the branch checks are fused_var_length's.
+// count(DISTINCT end node) and / or collect(DISTINCT end node), at most one of each, over the branches of a bounded
+// var-length expand, grouped by the start node (g.a = the start's id-like column) or alone (g.a empty): k-hop reach
+// (k_reach.hip).  Lengths lower..upper contiguous with lower in {0, 1} and any upper; the branch checks are
+// fused_var_length's.
 bool fused_var_length_distinct(capsmi_session* s, const capsmi_table* in, const PlanNode& g, const std::vector<Path>& B,
                                capsmi_table** out) {
-    if (g.a.size() > 1 || g.aggs.size() != 1 || g_dist.on) return false;  // single device: the operator path answers
+    if (g.a.size() > 1 || g.aggs.empty() || g.aggs.size() > 2 || g_dist.on) return false;  // single device: the operator path answers
     const bool grouped = !g.a.empty();
-    const AggSpec& ag = g.aggs[0];
-    if (ag.kind != CAPSMI_AGG_COUNT || !ag.distinct) return false;
+    const AggSpec *cag = nullptr, *lag = nullptr;  // the count, the collect
+    std::vector<int> ics;
+    for (const AggSpec& ag : g.aggs) {
+        if (!ag.distinct) return false;
+        if (ag.kind == CAPSMI_AGG_COUNT && !cag) cag = &ag;
+        else if (ag.kind == CAPSMI_AGG_COLLECT && !lag) lag = &ag;
+        else return false;
+        ics.push_back(find_col(in, ag.input));
+        if (ics.back() < 0) return false;
+    }
     const int gc = grouped ? find_col(in, g.a[0]) : -1;
-    const int ic = find_col(in, ag.input);
-    if ((grouped && gc < 0) || ic < 0) return false;
+    if (grouped && gc < 0) return false;
     std::set<int> lens;
     std::string akey, bkey, rsig;
     int64_t lo, hi;
     if (!id_window(B, &lo, &hi)) return false;
+    // The lists ascend in the ids the walk runs on.  A compacted graph's dense ids are hash group numbers
+    // (graph_compact: orig[] is not monotonic, the scrambled form neither), so mapping them back element-wise would
+    // leave the lists unsorted: collect on such a graph stays on the operator path, which sorts the original ids.
+    if (lag && g_dense) return false;
     BitmapSet bs;
     capsmi_bitmap *abm = nullptr, *bbm = nullptr;
     RelViews views;
@@ -1896,7 +1908,8 @@ bool fused_var_length_distinct(capsmi_session* s, const capsmi_table* in, const 
         if (k == 0) {
             // lower = 0: copyEntity(source -> target) of the start scan: the counted end is the copied start column
             if (lens.count(0) || P.pos_node.empty() || P.pos_node[0] < 0) return false;
-            if (position_of(P, P.cols[ic]) != 0 || !id_like(P, P.cols[ic])) return false;
+            for (int ic : ics)
+                if (position_of(P, P.cols[ic]) != 0 || !id_like(P, P.cols[ic])) return false;
             Classified c;
             if (!classify(P, c) || !c.uniq.empty()) return false;
             for (size_t q = 0; q < P.inst.size(); ++q)
@@ -1909,7 +1922,8 @@ bool fused_var_length_distinct(capsmi_session* s, const capsmi_table* in, const 
         lens.insert(k);
         for (int q = 1; q < k; ++q) if (P.pos_node[q] >= 0) return false;  // hops are not node-scanned
         if (P.pos_node[0] < 0 || P.pos_node[k] < 0) return false;
-        if (position_of(P, P.cols[ic]) != k || !id_like(P, P.cols[ic])) return false;  // the end node's id
+        for (int ic : ics)
+            if (position_of(P, P.cols[ic]) != k || !id_like(P, P.cols[ic])) return false;  // the end node's id
         Classified c;
         if (!classify(P, c) || !all_pairs_unique(c, k)) return false;
         for (size_t q = 0; q < P.inst.size(); ++q)
@@ -1935,19 +1949,46 @@ bool fused_var_length_distinct(capsmi_session* s, const capsmi_table* in, const 
     const int l = *lens.begin(), u = *lens.rbegin();
     if (l < 0 || l > 1 || u - l + 1 != (int)lens.size()) return false;  // lower >= 2: the join plan
     if (abm->any_dup || bbm->any_dup) return false;
+    if (!grouped && lag) {  // one row: the union's list, and its length as the count
+        capsmi_table* lt = nullptr;
+        check(capsmi_var_length_reach_list(s, (int32_t)views.t.size(), views.t.data(), "s", "t", abm, bbm, l, u,
+                                           lag->output.c_str(), &lt));
+        std::unique_ptr<capsmi_table, void (*)(capsmi_table*)> hold(lt, [](capsmi_table* t) { capsmi_table_release(t); });
+        auto* r = result_table(s, 1);
+        for (const AggSpec& ag : g.aggs) {
+            if (&ag == lag) {
+                r->cols.push_back(lt->cols[0]);
+            } else {
+                Column c = i64_column(s, {lt->cols[0].list->nvalues});
+                c.name = ag.output;
+                r->cols.push_back(std::move(c));
+            }
+        }
+        *out = r;
+        route(s, "var_length_distinct");
+        return true;
+    }
     if (!grouped) {
         int64_t x = 0;
         check(capsmi_var_length_reach_count(s, (int32_t)views.t.size(), views.t.data(), "s", "t", abm, bbm, l, u, &x));
         auto* r = result_table(s, 1);
         Column c = i64_column(s, {x});
-        c.name = ag.output;
+        c.name = cag->output;
         r->cols.push_back(std::move(c));
         *out = r;
         route(s, "var_length_distinct");
         return true;
     }
+    if (lag) {  // (id, list[, count]) in the order of the aggregates; no dense ids here (above)
+        check(capsmi_var_length_collect_distinct(s, (int32_t)views.t.size(), views.t.data(), "s", "t", abm, bbm, l, u,
+                                                 g.a[0].c_str(), lag->output.c_str(), cag ? cag->output.c_str() : nullptr,
+                                                 out));
+        if (cag && cag == &g.aggs[0]) std::swap((*out)->cols[1], (*out)->cols[2]);
+        route(s, "var_length_distinct");
+        return true;
+    }
     check(capsmi_var_length_count_distinct(s, (int32_t)views.t.size(), views.t.data(), "s", "t", abm, bbm, l, u,
-                                           g.a[0].c_str(), ag.output.c_str(), out));
+                                           g.a[0].c_str(), cag->output.c_str(), out));
     if (g_dense) {  // start ids back to the graph's Long ids
         capsmi_table* r = *out;
         Column& c = r->cols[0];

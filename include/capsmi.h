@@ -418,6 +418,10 @@ capsmi_status capsmi_session_kernel_time(capsmi_session* s, const char* name, in
  * frontier words per relationship + the 3 n W 8 B of state (the flat form: the relationship columns instead of the
  * pool, its state counted under "reach_final"); "reach_count_level": 8 B (narrow) or 16 B per relationship;
  * "reach_count_final": 20 B per word of 32 ids; "reach_part", the partition by target slice, declares none;
+ * var-length collect(DISTINCT b): "reach_list_count", pass 1 of a batch's extraction: the n W 8 B of hit words read
+ * + 4 B per (tile, source) count written; "reach_list_write", pass 2: 8 B per element written + the n W 8 B of hit
+ * words + 4 B per (tile, source) base read (the global form: 8 B per element + 12 B per word of 32 ids);
+ * "reach_list_starts", the hit words, scans and compaction, declares none;
  * 0 otherwise; then the counter resets. */
 capsmi_status capsmi_session_kernel_bytes(capsmi_session* s, const char* name, double* bytes);
 /* fused-path routing of lazy plans: enable / disable (default on; off = operator by operator, for
@@ -814,6 +818,33 @@ capsmi_status capsmi_var_length_reach_count(capsmi_session* s, int32_t nrels, ca
                                             const char* src_col, const char* dst_col, const capsmi_bitmap* a_ok,
                                             const capsmi_bitmap* b_ok, int32_t lower, int32_t upper,
                                             int64_t* out_distinct);
+/* BoundedVarLengthExpand + collect(DISTINCT b), fused: the sets that capsmi_var_length_count_distinct counts, as lists,
+ * read off the same bit-parallel BFS (k_reach.hip).
+ *   MATCH (a)-[r*lower..upper]->(b) WHERE a_ok(a) AND b_ok(b)
+ *   RETURN id(a) AS <id_name>, collect(DISTINCT b) AS <list_name> [, count(DISTINCT b) AS <count_name>]
+ * The same lemma (for lower <= 1 the ends of the relationship-distinct paths are the ends of the walks of length in
+ * [1, upper]: DESIGN.md section 4), so lower >= 2 is CAPSMI_ERR_NOT_IMPLEMENTED (use the join plan), and the same
+ * lower = 0 rule: a's list holds a itself whatever b_ok(a) says, once, also when a cycle returns to it.  The list
+ * column is CAPSMI_LIST_I64 and is sort_array(collect_set(id(b))) (SparkTable.scala:169-177): the absolute ids,
+ * strictly ascending, no duplicates, no nulls.  One row per a with a non-empty list, in no particular order.
+ * count_name may be NULL; otherwise the table also carries count(DISTINCT b), which the walk has anyway.
+ * Guard: the lists may hold up to |a_ok| n elements; beyond CAPSMI_REACH_LIST_LIMIT (elements, or auto = device
+ * memory / 16 B) the call is CAPSMI_ERR_UNSUPPORTED, raised before the batch that crosses the limit is written; the
+ * session stays usable.  a_ok and b_ok must share one id domain (fewer than 2^32 ids). */
+capsmi_status capsmi_var_length_collect_distinct(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                                 const char* src_col, const char* dst_col, const capsmi_bitmap* a_ok,
+                                                 const capsmi_bitmap* b_ok, int32_t lower, int32_t upper,
+                                                 const char* id_name, const char* list_name, const char* count_name,
+                                                 capsmi_table** out);
+/* The ungrouped form: MATCH (a)-[r*lower..upper]->(b) WHERE a_ok(a) AND b_ok(b) RETURN collect(DISTINCT b) AS
+ * <list_name>: exactly one row holding the union of the per-a lists above, strictly ascending absolute ids in a
+ * CAPSMI_LIST_I64 column, the empty list when nothing is reached (collect_set over no rows).  One BFS from all of
+ * a_ok; the same lemma (lower >= 2 is CAPSMI_ERR_NOT_IMPLEMENTED: use the join plan), the same lower = 0 rule (every
+ * a_ok node is in the list, whatever b_ok says of it, once) and the same CAPSMI_REACH_LIST_LIMIT guard. */
+capsmi_status capsmi_var_length_reach_list(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                           const char* src_col, const char* dst_col, const capsmi_bitmap* a_ok,
+                                           const capsmi_bitmap* b_ok, int32_t lower, int32_t upper, const char* list_name,
+                                           capsmi_table** out);
 /* Sharded form of capsmi_var_length_count for one rank of a multi-GPU run.  The
  * rank owns the source ids [own_lo, own_hi); `out_rels` hold the relationships whose source it
  * owns, `in_rels` those from other ranks' sources into its owned ids.  `od` and `y` are caller

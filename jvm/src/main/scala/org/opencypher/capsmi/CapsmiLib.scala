@@ -345,6 +345,12 @@ trait CapsmiLib extends Library {
                                        countName: String, out: PointerByReference): Int
   def capsmi_var_length_reach_count(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String, dstCol: String,
                                     a: Pointer, b: Pointer, lower: Int, upper: Int, out: LongByReference): Int
+  def capsmi_var_length_collect_distinct(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String, dstCol: String,
+                                         a: Pointer, b: Pointer, lower: Int, upper: Int, idName: String,
+                                         listName: String, countName: String, out: PointerByReference): Int
+  def capsmi_var_length_reach_list(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String, dstCol: String,
+                                   a: Pointer, b: Pointer, lower: Int, upper: Int, listName: String,
+                                   out: PointerByReference): Int
 
   // ingest (EdgeListDataSource / FSGraphSource CSV)
   def capsmi_read_csv(s: Pointer, nfiles: Int, paths: Array[String], delimiter: Byte, comment: Byte, ncols: Int,
