@@ -205,6 +205,10 @@ _SIGS = {
                                                      c_char_p, c_char_p, c_char_p, PP]),
     "capsmi_var_length_reach_list": (c_int32, [P, c_int32, PP, c_char_p, c_char_p, P, P, c_int32, c_int32, c_char_p,
                                                PP]),
+    "capsmi_var_length_collect_distinct_mapped": (c_int32, [P, c_int32, PP, c_char_p, c_char_p, P, P, c_int32, c_int32,
+                                                            c_void_p, c_int64, c_char_p, c_char_p, c_char_p, PP]),
+    "capsmi_var_length_reach_list_mapped": (c_int32, [P, c_int32, PP, c_char_p, c_char_p, P, P, c_int32, c_int32,
+                                                      c_void_p, c_int64, c_char_p, PP]),
     "capsmi_varlen_shard_begin": (c_int32, [P, c_int32, PP, c_int32, PP, c_char_p, c_char_p, P, P, c_int32, c_int32,
                                             c_int64, c_int64, c_void_p, PP]),
     "capsmi_varlen_shard_mid": (c_int32, [P, c_void_p]),

@@ -206,29 +206,68 @@ def var_length_reach_count(session: Session, rels: Sequence[GpuTable], a_ok: Nod
     return out.value
 
 
+def _orig_device(session: Session, a_ok: NodeBitmap, orig):
+    """`orig` (dense index -> original id) as (holder, device pointer, length): an int64 array is copied to the
+    device, a ``(device_ptr, length)`` pair (e.g. a torch tensor's ``data_ptr()`` and ``numel()``) is passed on."""
+    import numpy as np
+    from .expr import I64
+    from .table import ColumnData
+    if isinstance(orig, tuple):
+        return None, ctypes.c_void_p(int(orig[0])), int(orig[1])
+    arr = np.ascontiguousarray(np.asarray(orig), dtype=np.int64)
+    if arr.ndim != 1:
+        raise ValueError("orig must be one-dimensional")
+    if len(arr) == 0:
+        return None, ctypes.c_void_p(), 0
+    holder = session.table([ColumnData("orig", I64, arr)])
+    data, valid = ctypes.c_void_p(), ctypes.c_void_p()
+    _lib.call("capsmi_table_column_device_ptr", holder.handle, 0, ctypes.byref(data), ctypes.byref(valid))
+    return holder, data, len(arr)
+
+
 def var_length_collect_distinct(session: Session, rels: Sequence[GpuTable], a_ok: NodeBitmap, b_ok: NodeBitmap,
                                 lower: int, upper: int, id_name: str = "id", list_name: str = "list",
                                 count_name: Optional[str] = None, src_col: str = "source",
-                                dst_col: str = "target") -> GpuTable:
+                                dst_col: str = "target", orig=None) -> GpuTable:
     """``MATCH (a)-[*lower..upper]->(b) WHERE a_ok(a) AND b_ok(b) RETURN id(a), collect(DISTINCT b)``: lower 0 or 1,
     any upper >= 1.  One row per a with a non-empty list; the lists hold the absolute ids, strictly ascending
     (``sort_array(collect_set(id(b)))``).  With `count_name` the table also carries ``count(DISTINCT b)``.  More
-    elements than ``CAPSMI_REACH_LIST_LIMIT`` raise UnsupportedOperationException."""
+    elements than ``CAPSMI_REACH_LIST_LIMIT`` raise UnsupportedOperationException.
+
+    `orig` (remapped ids): the bitmaps and relationships hold dense ids, and ``orig[d]`` is the original id of dense
+    id ``a_ok.lo + d`` -- an int64 array of ``hi - lo`` distinct ids, or a ``(device_ptr, length)`` pair.  The ids
+    and lists then hold original ids, the lists ascending by signed value; a wrong length or a repeated id raises
+    IllegalArgumentException."""
     out = ctypes.c_void_p()
-    _lib.call("capsmi_var_length_collect_distinct", session.handle, len(rels), _handles(rels), src_col.encode(),
-              dst_col.encode(), a_ok.handle, b_ok.handle, lower, upper, id_name.encode(), list_name.encode(),
-              None if count_name is None else count_name.encode(), ctypes.byref(out))
+    if orig is None:
+        _lib.call("capsmi_var_length_collect_distinct", session.handle, len(rels), _handles(rels), src_col.encode(),
+                  dst_col.encode(), a_ok.handle, b_ok.handle, lower, upper, id_name.encode(), list_name.encode(),
+                  None if count_name is None else count_name.encode(), ctypes.byref(out))
+        return GpuTable(session, out)
+    holder, ptr, length = _orig_device(session, a_ok, orig)
+    _lib.call("capsmi_var_length_collect_distinct_mapped", session.handle, len(rels), _handles(rels), src_col.encode(),
+              dst_col.encode(), a_ok.handle, b_ok.handle, lower, upper, ptr, length, id_name.encode(),
+              list_name.encode(), None if count_name is None else count_name.encode(), ctypes.byref(out))
+    del holder  # the call has read it (stream-ordered)
     return GpuTable(session, out)
 
 
 def var_length_reach_list(session: Session, rels: Sequence[GpuTable], a_ok: NodeBitmap, b_ok: NodeBitmap,
-                          lower: int, upper: int, src_col: str = "source", dst_col: str = "target") -> np.ndarray:
+                          lower: int, upper: int, src_col: str = "source", dst_col: str = "target",
+                          orig=None) -> np.ndarray:
     """``MATCH (a)-[*lower..upper]->(b) WHERE a_ok(a) AND b_ok(b) RETURN collect(DISTINCT b)`` (lower 0 or 1): the
-    ascending ids of the union of the per-a lists, as an int64 array (empty when nothing is reached)."""
+    ascending ids of the union of the per-a lists, as an int64 array (empty when nothing is reached).  `orig`: as
+    in `var_length_collect_distinct` -- the original ids, ascending by signed value."""
     import numpy as np
     out = ctypes.c_void_p()
-    _lib.call("capsmi_var_length_reach_list", session.handle, len(rels), _handles(rels), src_col.encode(),
-              dst_col.encode(), a_ok.handle, b_ok.handle, lower, upper, b"list", ctypes.byref(out))
+    if orig is None:
+        _lib.call("capsmi_var_length_reach_list", session.handle, len(rels), _handles(rels), src_col.encode(),
+                  dst_col.encode(), a_ok.handle, b_ok.handle, lower, upper, b"list", ctypes.byref(out))
+    else:
+        holder, ptr, length = _orig_device(session, a_ok, orig)
+        _lib.call("capsmi_var_length_reach_list_mapped", session.handle, len(rels), _handles(rels), src_col.encode(),
+                  dst_col.encode(), a_ok.handle, b_ok.handle, lower, upper, ptr, length, b"list", ctypes.byref(out))
+        del holder
     t = GpuTable(session, out)
     return np.asarray(t.column("list").values[0], dtype=np.int64)
 

@@ -2201,16 +2201,13 @@ capsmi_status capsmi_var_length_reach_count(capsmi_session* s, int32_t nrels, ca
     API_END
 }
 
-capsmi_status capsmi_var_length_collect_distinct(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
-                                                 const char* src_col, const char* dst_col, const capsmi_bitmap* a_ok,
-                                                 const capsmi_bitmap* b_ok, int32_t lower, int32_t upper,
-                                                 const char* id_name, const char* list_name, const char* count_name,
-                                                 capsmi_table** out) {
-    API_BEGIN
-    need(s, "session");
-    need(out, "out");
-    need(id_name, "id_name");
-    need(list_name, "list_name");
+}  // extern "C"
+
+namespace capsmi {
+void var_length_collect_table(capsmi_session* s, int32_t nrels, capsmi_table* const* rels, const char* src_col,
+                              const char* dst_col, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int32_t lower,
+                              int32_t upper, const char* id_name, const char* list_name, const char* count_name,
+                              const int64_t* orig, const IdOrder* ord, capsmi_table** out) {
     ReachArgs r;
     reach_args(s, nrels, rels, src_col, dst_col, a_ok, b_ok, lower, upper, r);
     const std::string idn(id_name), ln(list_name);
@@ -2219,7 +2216,7 @@ capsmi_status capsmi_var_length_collect_distinct(capsmi_session* s, int32_t nrel
     Buf ids, cnt, sel;
     std::shared_ptr<ListStore> lists;
     const int64_t rows = var_length_reach_lists(s, r.srcs.data(), r.dsts.data(), r.ms.data(), nrels, a_ok, b_ok, lower,
-                                                upper, ids, cnt, sel, lists, r.nar.data());
+                                                upper, ids, cnt, sel, lists, r.nar.data(), orig, ord);
     auto* o = new_table(s, rows);
     Column a, l;
     a.name = idn;
@@ -2239,24 +2236,18 @@ capsmi_status capsmi_var_length_collect_distinct(capsmi_session* s, int32_t nrel
         o->cols.push_back(std::move(c));
     }
     *out = o;
-    API_END
 }
 
-capsmi_status capsmi_var_length_reach_list(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
-                                           const char* src_col, const char* dst_col, const capsmi_bitmap* a_ok,
-                                           const capsmi_bitmap* b_ok, int32_t lower, int32_t upper,
-                                           const char* list_name, capsmi_table** out) {
-    API_BEGIN
-    need(s, "session");
-    need(out, "out");
-    need(list_name, "list_name");
+void var_length_reach_list_table(capsmi_session* s, int32_t nrels, capsmi_table* const* rels, const char* src_col,
+                                 const char* dst_col, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int32_t lower,
+                                 int32_t upper, const char* list_name, const IdOrder* ord, capsmi_table** out) {
     ReachArgs r;
     reach_args(s, nrels, rels, src_col, dst_col, a_ok, b_ok, lower, upper, r);
     auto L = std::make_shared<ListStore>();
     L->elem = CAPSMI_I64;
     L->nlists = 1;
     L->nvalues = var_length_reach_list(s, r.srcs.data(), r.dsts.data(), r.ms.data(), nrels, a_ok, b_ok, lower, upper,
-                                       L->values, r.nar.data());
+                                       L->values, r.nar.data(), ord);
     const int64_t ends[2] = {0, L->nvalues};
     L->offsets = dev_alloc(sizeof(ends), s);
     HIP_CHECK(hipMemcpyAsync(P<void>(L->offsets), ends, sizeof(ends), hipMemcpyHostToDevice, s->stream));
@@ -2270,6 +2261,91 @@ capsmi_status capsmi_var_length_reach_list(capsmi_session* s, int32_t nrels, cap
     l.list = L;
     o->cols.push_back(std::move(l));
     *out = o;
+}
+
+namespace {
+// the per-call order of a mapped entry: the argument checks that need no device work first, then the sort, whose
+// neighbours show a repeated id
+std::shared_ptr<const IdOrder> mapped_order(capsmi_session* s, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok,
+                                            int32_t lower, int32_t upper, const int64_t* orig, int64_t orig_len) {
+    need(s, "session");
+    check_bitmap(a_ok, "a_ok");
+    check_bitmap(b_ok, "b_ok");
+    REQUIRE(lower >= 0 && lower <= upper && upper >= 1, CAPSMI_ERR_ILLEGAL_ARGUMENT,
+            "var-length count(DISTINCT b): 0 <= lower <= upper, upper >= 1");
+    REQUIRE(lower <= 1, CAPSMI_ERR_NOT_IMPLEMENTED,
+            "fused var-length collect(DISTINCT b) supports lower 0 or 1 (use the join plan)");
+    REQUIRE(a_ok->lo == b_ok->lo && a_ok->hi == b_ok->hi, CAPSMI_ERR_UNSUPPORTED, "a and b scans need one id domain");
+    const int64_t n = a_ok->hi - a_ok->lo;
+    REQUIRE(orig_len == n && (orig || n == 0), CAPSMI_ERR_ILLEGAL_ARGUMENT,
+            "orig must hold one original id per id of the bitmaps' domain (" + std::to_string(n) + ")");
+    REQUIRE(n < (int64_t(1) << 32), CAPSMI_ERR_UNSUPPORTED, "var-length collect(DISTINCT b): at most 2^32 - 1 ids");
+    use_device(s);
+    bool dup = false;
+    auto ord = id_order_build(s, orig, n, &dup);
+    REQUIRE(!dup, CAPSMI_ERR_ILLEGAL_ARGUMENT, "orig holds an id twice: the original ids must be distinct");
+    return ord;
+}
+}  // namespace
+}  // namespace capsmi
+
+extern "C" {
+
+capsmi_status capsmi_var_length_collect_distinct(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                                 const char* src_col, const char* dst_col, const capsmi_bitmap* a_ok,
+                                                 const capsmi_bitmap* b_ok, int32_t lower, int32_t upper,
+                                                 const char* id_name, const char* list_name, const char* count_name,
+                                                 capsmi_table** out) {
+    API_BEGIN
+    need(s, "session");
+    need(out, "out");
+    need(id_name, "id_name");
+    need(list_name, "list_name");
+    var_length_collect_table(s, nrels, rels, src_col, dst_col, a_ok, b_ok, lower, upper, id_name, list_name, count_name,
+                             nullptr, nullptr, out);
+    API_END
+}
+
+capsmi_status capsmi_var_length_reach_list(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                           const char* src_col, const char* dst_col, const capsmi_bitmap* a_ok,
+                                           const capsmi_bitmap* b_ok, int32_t lower, int32_t upper,
+                                           const char* list_name, capsmi_table** out) {
+    API_BEGIN
+    need(s, "session");
+    need(out, "out");
+    need(list_name, "list_name");
+    var_length_reach_list_table(s, nrels, rels, src_col, dst_col, a_ok, b_ok, lower, upper, list_name, nullptr, out);
+    API_END
+}
+
+capsmi_status capsmi_var_length_collect_distinct_mapped(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                                        const char* src_col, const char* dst_col,
+                                                        const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok,
+                                                        int32_t lower, int32_t upper, const int64_t* orig,
+                                                        int64_t orig_len, const char* id_name, const char* list_name,
+                                                        const char* count_name, capsmi_table** out) {
+    API_BEGIN
+    need(s, "session");
+    need(out, "out");
+    need(id_name, "id_name");
+    need(list_name, "list_name");
+    auto ord = mapped_order(s, a_ok, b_ok, lower, upper, orig, orig_len);
+    var_length_collect_table(s, nrels, rels, src_col, dst_col, a_ok, b_ok, lower, upper, id_name, list_name, count_name,
+                             orig, ord.get(), out);
+    API_END
+}
+
+capsmi_status capsmi_var_length_reach_list_mapped(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                                  const char* src_col, const char* dst_col, const capsmi_bitmap* a_ok,
+                                                  const capsmi_bitmap* b_ok, int32_t lower, int32_t upper,
+                                                  const int64_t* orig, int64_t orig_len, const char* list_name,
+                                                  capsmi_table** out) {
+    API_BEGIN
+    need(s, "session");
+    need(out, "out");
+    need(list_name, "list_name");
+    auto ord = mapped_order(s, a_ok, b_ok, lower, upper, orig, orig_len);
+    var_length_reach_list_table(s, nrels, rels, src_col, dst_col, a_ok, b_ok, lower, upper, list_name, ord.get(), out);
     API_END
 }
 

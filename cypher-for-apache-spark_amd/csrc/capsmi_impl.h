@@ -13,6 +13,7 @@
 #include <map>
 #include <set>
 #include <memory>
+#include <mutex>
 #include <stdexcept>
 #include <string>
 #include <functional>
@@ -132,9 +133,20 @@ struct PlanNode;  // lazy Table[T] operator (plan.hip)
 // Dense id space of one graph (capsmi_graph_compact): every node id and relationship endpoint of
 // the graph's entity tables numbered 0..n-1; orig[d] is the Long id of dense id d.  The fused
 // routes run on dense ids when the Long ids do not fit one window of 2^30 ids.
+// The signed order of a dense domain's original ids (id_order_build, k_reach.hip): sorted_orig[p] is the p-th
+// smallest original id and by_rank[p] the dense id that holds it, so orig[by_rank[p]] == sorted_orig[p].
+struct IdOrder {
+    int64_t n = 0;
+    Buf sorted_orig, by_rank;  // int64 x n each
+};
+
 struct DenseIds {
     int64_t n = 0;
     Buf orig;
+    // built at the first var-length collect(DISTINCT b) routed on this domain and kept with it: 16 B per id
+    // (the orig-table form only); guarded by order_mu
+    mutable std::shared_ptr<const IdOrder> order;
+    mutable std::mutex order_mu;
     // a distributed graph's domain (capsmi_graph_distribute): dense = h(x) = ((x - lo) * mul) mod 2^kbits,
     // x = (dense * mul_inv mod 2^kbits) + lo; no orig table
     bool scrambled = false;
@@ -776,14 +788,27 @@ int64_t var_length_reach_count(capsmi_session* s, const int64_t* const* srcs, co
 // var-length collect(DISTINCT b) (k_reach.hip): the rows above with D(a) itself, read off each batch's bit matrix.
 // List k of `lists` is D of the k-th a_ok node in id order, strictly ascending absolute ids (empty lists included,
 // which no row names); out_sel holds the rows' list indices.  CAPSMI_REACH_LIST_LIMIT bounds the elements.
+// Remapped ids (orig != null: orig[d] is the original id of dense id lo + d, all distinct; ord their order): the
+// lists hold original ids, ascending by signed value, and out_ids the sources' original ids; rows and lists stay
+// in dense order of the sources.
 int64_t var_length_reach_lists(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
                                int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower, int upper,
                                Buf& out_ids, Buf& out_cnt, Buf& out_sel, std::shared_ptr<ListStore>& lists,
-                               const NarrowRel* nar = nullptr);
-// the global form: U_a D(a) as ascending absolute ids (returns their number)
+                               const NarrowRel* nar = nullptr, const int64_t* orig = nullptr, const IdOrder* ord = nullptr);
+// the global form: U_a D(a) as ascending absolute ids (returns their number); ord: as ascending original ids
 int64_t var_length_reach_list(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
                               int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower, int upper,
-                              Buf& out_vals, const NarrowRel* nar = nullptr);
+                              Buf& out_vals, const NarrowRel* nar = nullptr, const IdOrder* ord = nullptr);
+// the order of n original ids (signed, ORDER BY's key image and radix sort); *dup (if given): two ids are equal
+std::shared_ptr<const IdOrder> id_order_build(capsmi_session* s, const int64_t* orig, int64_t n, bool* dup = nullptr);
+// the two collect entries behind the C interface and the route: orig / ord null for plain ids
+void var_length_collect_table(capsmi_session* s, int32_t nrels, capsmi_table* const* rels, const char* src_col,
+                              const char* dst_col, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int32_t lower,
+                              int32_t upper, const char* id_name, const char* list_name, const char* count_name,
+                              const int64_t* orig, const IdOrder* ord, capsmi_table** out);
+void var_length_reach_list_table(capsmi_session* s, int32_t nrels, capsmi_table* const* rels, const char* src_col,
+                                 const char* dst_col, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int32_t lower,
+                                 int32_t upper, const char* list_name, const IdOrder* ord, capsmi_table** out);
 // sharded var-length grouped count (multi-GPU C5; k_varlen.hip): begin -> caller sums od over ranks
 // -> mid -> caller sums Y -> finish (rows of owned ids)
 struct VarlenShard;

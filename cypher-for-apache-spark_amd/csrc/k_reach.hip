@@ -626,6 +626,42 @@ __global__ void k_rl_self(const int64_t* __restrict__ idx, int bw, int64_t n, u6
     if (j < bw) hit[(size_t)(j >> 6) * n + idx[j]] |= 1ULL << (j & 63);
 }
 
+// Remapped ids (a compacted graph: dense id d holds the original id orig[d], and orig is not monotonic).  The lists
+// must ascend in the original ids, and no list element is ever sorted: position p of the hit matrix is taken from
+// the node of rank p, by_rank[p], so the walk's ascending positions are ascending original ids and pass 2 stores
+// sorted_orig[p].  seen is node-major, so a node's NW words are one stretch of NW * 8 bytes (a 64-byte line at
+// NW = 8): a lane reads it whole, at random, and the stores stay coalesced as in k_rl_hit.
+template <int NW>
+__global__ void k_rl_hit_rank(int64_t n, const u64* __restrict__ seen, const int64_t* __restrict__ by_rank,
+                              const uint32_t* __restrict__ bw, int b_full, u64* __restrict__ hit) {
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
+        const uint64_t d = (uint64_t)by_rank[p];  // a permutation of [0, n): the payload of the order's sort
+        const bool bk = bit_of(bw, b_full, d);
+        u64 x[NW];
+#pragma unroll
+        for (int w = 0; w < NW; ++w) x[w] = seen[(size_t)d * NW + w];
+#pragma unroll
+        for (int w = 0; w < NW; ++w) hit[(size_t)w * n + p] = bk ? x[w] : 0ULL;
+    }
+}
+
+// lower = 0, remapped: source j's own bit goes to the position of its original id, found by bisection of sorted_orig
+// (at most 64 * NW sources per batch, log2 n steps each: no inverse of by_rank is kept).  The sources are distinct
+// nodes, so their positions differ: one thread per word touched.
+__global__ void k_rl_self_rank(const int64_t* __restrict__ idx, int bw, int64_t n, const int64_t* __restrict__ orig,
+                               const int64_t* __restrict__ sorted, u64* __restrict__ hit) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= bw) return;
+    const int64_t key = orig[idx[j]];
+    int64_t a = 0, b = n;  // the first position whose id is >= key
+    while (a < b) {
+        const int64_t mid = a + ((b - a) >> 1);
+        if (sorted[mid] < key) a = mid + 1;
+        else b = mid;
+    }
+    if (a < n && sorted[a] == key) hit[(size_t)(j >> 6) * n + a] |= 1ULL << (j & 63);
+}
+
 __device__ __forceinline__ int64_t readlane64(int64_t x, int j) {  // j wave-uniform
     const uint32_t l = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)x, j);
     const uint32_t h = (uint32_t)__builtin_amdgcn_readlane((int)((u64)x >> 32), j);
@@ -634,11 +670,13 @@ __device__ __forceinline__ int64_t readlane64(int64_t x, int j) {  // j wave-uni
 
 // WRITE = false (pass 1): tcol[unit * 64 + j] = nodes of the unit's tile that source 64 w + j holds.
 // WRITE = true (pass 2): tcol holds the tile bases; node lo + v goes to vals[offs[source] + base + rank].
-template <bool WRITE>
+// MAP (pass 2 over a rank-ordered hit matrix): position v stands for the original id sorted[v], stored in its place.
+template <bool WRITE, bool MAP = false>
 __global__ void __launch_bounds__(kListBlock) k_rl_walk(int64_t n, int64_t ntiles, int nwords, int bwid,
                                                         const u64* __restrict__ hit, uint32_t* __restrict__ tcol,
                                                         const int64_t* __restrict__ offs, int64_t lo,
-                                                        int64_t* __restrict__ vals) {
+                                                        int64_t* __restrict__ vals,
+                                                        const int64_t* __restrict__ sorted = nullptr) {
     const int lane = threadIdx.x & 63;
     const int64_t units = ntiles * nwords;
     for (int64_t u = (int64_t)blockIdx.x * (kListBlock / 64) + (threadIdx.x >> 6); u < units;
@@ -653,6 +691,8 @@ __global__ void __launch_bounds__(kListBlock) k_rl_walk(int64_t n, int64_t ntile
             const int64_t v = tile * kListTile + step * 64 + lane;
             const u64 x = v < n ? hw[v] : 0ULL;
             if (!__any(x != 0)) continue;
+            int64_t val = lo + v;
+            if (MAP) val = x ? sorted[v] : 0;  // x != 0 only below n
             u64 m = wave_or(x);
             m = ((u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)(m >> 32)) << 32) |
                 (u64)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)m);
@@ -664,7 +704,7 @@ __global__ void __launch_bounds__(kListBlock) k_rl_walk(int64_t n, int64_t ntile
                 if (WRITE) {
                     const int64_t p = readlane64(pos, j);
                     const int below = __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0));
-                    if (on) vals[p + below] = lo + v;
+                    if (on) vals[p + below] = val;
                 }
                 if (lane == j) pos += __popcll(bal);
             }
@@ -701,16 +741,53 @@ __global__ void k_rc_listwords(int64_t n, int64_t nw, const uint32_t* __restrict
     }
 }
 
+// MAP: the words are in rank order (k_rc_rank) and bit p stands for the original id sorted[p]
+template <bool MAP>
 __global__ void k_rc_listwrite(int64_t nw, const uint32_t* __restrict__ words, const int64_t* __restrict__ offs, int64_t lo,
-                               int64_t* __restrict__ vals) {
+                               int64_t* __restrict__ vals, const int64_t* __restrict__ sorted) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nw; i += (int64_t)gridDim.x * blockDim.x) {
         uint32_t x = words[i];
         int64_t o = offs[i];
         while (x) {
-            vals[o++] = lo + 32 * i + (__ffs((int)x) - 1);
+            const int64_t p = 32 * i + (__ffs((int)x) - 1);
+            vals[o++] = MAP ? sorted[p] : lo + p;
             x &= x - 1;
         }
     }
+}
+
+// global form, remapped ids: the answer's bitmap from dense order into rank order, bit p of the output = bit
+// by_rank[p] of the input.  A wave takes 64 consecutive positions: one ballot, and lane 0 stores the 64-bit word
+// (two of the 32-bit words that the count, scan and write passes walk) and lanes 0 and 1 its halves' bit counts.
+// out has 2 * ceil(n / 64) 32-bit words; cnt has nw = ceil(n / 32), so the last odd half has no count to store.
+__global__ void __launch_bounds__(256) k_rc_rank(int64_t n, int64_t nw, const uint32_t* __restrict__ words,
+                                                 const int64_t* __restrict__ by_rank, u64* __restrict__ out,
+                                                 int64_t* __restrict__ cnt) {
+    const int lane = threadIdx.x & 63;
+    const int64_t nw64 = (n + 63) >> 6;
+    for (int64_t i = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; i < nw64;
+         i += ((int64_t)gridDim.x * blockDim.x) >> 6) {  // wave-uniform
+        const int64_t p = i * 64 + lane;
+        bool on = false;
+        if (p < n) {
+            const uint64_t d = (uint64_t)by_rank[p];
+            on = (words[d >> 5] >> (d & 31)) & 1u;
+        }
+        const u64 bal = __ballot(on);
+        if (lane == 0) out[i] = bal;
+        if (lane < 2 && 2 * i + lane < nw) cnt[2 * i + lane] = __popc((uint32_t)(bal >> (32 * lane)));
+    }
+}
+
+// sorted keys (the order-preserving image of the ids) back to ids
+__global__ void k_ro_unkey(int64_t n, uint64_t* __restrict__ key) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        key[i] ^= 0x8000000000000000ULL;
+}
+
+__global__ void k_ro_dup(int64_t n, const uint64_t* __restrict__ key, int64_t* __restrict__ flag) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x + 1; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        if (key[i] == key[i - 1]) *flag = 1;  // every writer stores the same word
 }
 
 // CAPSMI_REACH_LIST_LIMIT in elements; auto: what fits the device's memory at the 16 B per element of the peak (the
@@ -735,11 +812,14 @@ inline void check_list_limit(int64_t elems, int64_t limit) {
 int64_t var_length_reach_lists(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
                                int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower, int upper,
                                Buf& out_ids, Buf& out_cnt, Buf& out_sel, std::shared_ptr<ListStore>& lists,
-                               const NarrowRel* nar) {
+                               const NarrowRel* nar, const int64_t* orig, const IdOrder* ord) {
     using namespace reach;
     hipStream_t st = s->stream;
     const int64_t n = b_ok->hi - b_ok->lo, lo = b_ok->lo;
     REQUIRE(n < (int64_t(1) << 32), CAPSMI_ERR_UNSUPPORTED, "var-length collect(DISTINCT b): at most 2^32 - 1 ids");
+    REQUIRE(!ord || (orig && ord->n == n), CAPSMI_ERR_INTERNAL, "var-length collect(DISTINCT b): the id order is not the domain's");
+    const int64_t* by_rank = ord ? P<int64_t>(ord->by_rank) : nullptr;
+    const int64_t* sorted = ord ? P<int64_t>(ord->sorted_orig) : nullptr;
     const int64_t limit = list_limit(s);
     const uint32_t* bw = P<uint32_t>(b_ok->words);
     const int b_full = b_ok->full ? 1 : 0;
@@ -756,7 +836,23 @@ int64_t var_length_reach_lists(capsmi_session* s, const int64_t* const* srcs, co
         const int wgrid = (int)std::min<int64_t>((units + kListBlock / 64 - 1) / (kListBlock / 64), (int64_t)s->num_cus * 32);
         const double hit_bytes = (double)n * b.nwords * 8, col_bytes = (double)units * 64 * 4;
         int64_t* blen = P<int64_t>(lens) + b.base;
-        {
+        if (ord) {  // the hit matrix in rank order: n ranks and n * W words read (by node lines), n * W words written
+            {
+                KernelTimer kt(s, "reach_list_gather", 2.0 * hit_bytes + 8.0 * (double)n);
+                const dim3 g(grid(s, n)), t(256);
+                switch (b.nwords) {
+                    case 1: hipLaunchKernelGGL(k_rl_hit_rank<1>, g, t, 0, st, n, b.seen, by_rank, bw, b_full, b.fa); break;
+                    case 2: hipLaunchKernelGGL(k_rl_hit_rank<2>, g, t, 0, st, n, b.seen, by_rank, bw, b_full, b.fa); break;
+                    case 4: hipLaunchKernelGGL(k_rl_hit_rank<4>, g, t, 0, st, n, b.seen, by_rank, bw, b_full, b.fa); break;
+                    default: hipLaunchKernelGGL(k_rl_hit_rank<8>, g, t, 0, st, n, b.seen, by_rank, bw, b_full, b.fa); break;
+                }
+            }
+            if (lower == 0) {
+                KernelTimer kt(s, "reach_list_starts");
+                hipLaunchKernelGGL(k_rl_self_rank, dim3((b.bwid + 255) / 256), dim3(256), 0, st, b.idx, b.bwid, n, orig,
+                                   sorted, b.fa);
+            }
+        } else {
             KernelTimer kt(s, "reach_list_starts");
             hipLaunchKernelGGL(k_rl_hit, dim3(grid(s, n)), dim3(256), 0, st, n, b.nwords, b.seen, bw, b_full, b.fa);
             if (lower == 0)
@@ -765,7 +861,7 @@ int64_t var_length_reach_lists(capsmi_session* s, const int64_t* const* srcs, co
         {
             KernelTimer kt(s, "reach_list_count", hit_bytes + col_bytes);
             hipLaunchKernelGGL(k_rl_walk<false>, dim3(wgrid), dim3(kListBlock), 0, st, n, ntiles, b.nwords, b.bwid, b.fa,
-                               P<uint32_t>(tcol), (const int64_t*)nullptr, lo, (int64_t*)nullptr);
+                               P<uint32_t>(tcol), (const int64_t*)nullptr, lo, (int64_t*)nullptr, (const int64_t*)nullptr);
         }
         {
             KernelTimer kt(s, "reach_list_starts");
@@ -778,14 +874,26 @@ int64_t var_length_reach_lists(capsmi_session* s, const int64_t* const* srcs, co
         check_list_limit(total + elems, limit);                            // before the batch is written
         Buf vals = dev_alloc(sizeof(int64_t) * (size_t)(elems > 0 ? elems : 1), s);
         if (elems > 0) {
-            KernelTimer kt(s, "reach_list_write", 8.0 * (double)elems + hit_bytes + col_bytes);
-            hipLaunchKernelGGL(k_rl_walk<true>, dim3(wgrid), dim3(kListBlock), 0, st, n, ntiles, b.nwords, b.bwid, b.fa,
-                               P<uint32_t>(tcol), P<int64_t>(boffs), lo, P<int64_t>(vals));
+            KernelTimer kt(s, "reach_list_write", 8.0 * (double)elems + hit_bytes + col_bytes + (ord ? 8.0 * (double)n : 0));
+            if (ord)
+                hipLaunchKernelGGL((k_rl_walk<true, true>), dim3(wgrid), dim3(kListBlock), 0, st, n, ntiles, b.nwords, b.bwid,
+                                   b.fa, P<uint32_t>(tcol), P<int64_t>(boffs), lo, P<int64_t>(vals), sorted);
+            else
+                hipLaunchKernelGGL(k_rl_walk<true>, dim3(wgrid), dim3(kListBlock), 0, st, n, ntiles, b.nwords, b.bwid, b.fa,
+                                   P<uint32_t>(tcol), P<int64_t>(boffs), lo, P<int64_t>(vals), (const int64_t*)nullptr);
         }
         parts.emplace_back(vals, elems);
         total += elems;
     });
-    const int64_t rows = reach_rows_out(s, idx, cnts, A, lo, out_ids, out_cnt, out_sel);
+    int64_t rows = 0;
+    if (ord) {  // the sources' dense indices, then their original ids
+        Buf dense_ids;
+        rows = reach_rows_out(s, idx, cnts, A, 0, dense_ids, out_cnt, out_sel);
+        out_ids = dev_alloc(sizeof(int64_t) * (size_t)(rows > 0 ? rows : 1), s);
+        if (rows > 0) gather_col(orig, nullptr, P<int64_t>(dense_ids), rows, P<int64_t>(out_ids), nullptr, st);
+    } else {
+        rows = reach_rows_out(s, idx, cnts, A, lo, out_ids, out_cnt, out_sel);
+    }
     if (!out_sel) out_sel = dev_alloc(8, s);
     auto L = std::make_shared<ListStore>();
     L->elem = CAPSMI_I64;
@@ -817,7 +925,7 @@ int64_t var_length_reach_lists(capsmi_session* s, const int64_t* const* srcs, co
 // the ascending ids of U_a D(a) (returns their number)
 int64_t var_length_reach_list(capsmi_session* s, const int64_t* const* srcs, const int64_t* const* dsts, const int64_t* ms,
                               int nt, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int lower, int upper,
-                              Buf& out_vals, const NarrowRel* nar) {
+                              Buf& out_vals, const NarrowRel* nar, const IdOrder* ord) {
     using namespace reach;
     hipStream_t st = s->stream;
     const int64_t n = b_ok->hi - b_ok->lo, lo = b_ok->lo;
@@ -829,13 +937,26 @@ int64_t var_length_reach_list(capsmi_session* s, const int64_t* const* srcs, con
     const int64_t nw = (n + 31) / 32;
     Buf maps, tot;
     reach_global(s, srcs, dsts, ms, nt, a_ok, b_ok, upper, nar, maps, tot);
+    REQUIRE(!ord || ord->n == n, CAPSMI_ERR_INTERNAL, "var-length collect(DISTINCT b): the id order is not the domain's");
     uint32_t *F = P<uint32_t>(maps), *R = F + nw;  // F is free after the levels: it takes the answer's words
     Buf cnt = dev_alloc(sizeof(int64_t) * (size_t)nw, s), offs = dev_alloc(sizeof(int64_t) * (size_t)(nw + 1), s);
     int64_t elems = 0;
+    Buf ranked;  // remapped ids: the answer's words in rank order
     {
         KernelTimer kt(s, "reach_list_starts");
         hipLaunchKernelGGL(k_rc_listwords, dim3(grid(s, nw)), dim3(256), 0, st, n, nw, R, P<uint32_t>(a_ok->words),
                            a_ok->full ? 1 : 0, P<uint32_t>(b_ok->words), b_ok->full ? 1 : 0, lower, F, P<int64_t>(cnt));
+        if (!ord) exclusive_scan_i64(P<int64_t>(cnt), P<int64_t>(offs), nw, s);
+    }
+    if (ord) {
+        const int64_t nw64 = (n + 63) / 64;
+        ranked = dev_alloc(sizeof(u64) * (size_t)nw64, s);
+        {
+            KernelTimer kt(s, "reach_list_gather", 8.0 * (double)n + 4.0 * (double)nw + 8.0 * (double)nw64 + 8.0 * (double)nw);
+            hipLaunchKernelGGL(k_rc_rank, dim3(grid(s, n)), dim3(256), 0, st, n, nw, F, P<int64_t>(ord->by_rank),
+                               P<u64>(ranked), P<int64_t>(cnt));
+        }
+        KernelTimer kt(s, "reach_list_starts");
         exclusive_scan_i64(P<int64_t>(cnt), P<int64_t>(offs), nw, s);
     }
     HIP_CHECK(hipGetLastError());
@@ -844,11 +965,45 @@ int64_t var_length_reach_list(capsmi_session* s, const int64_t* const* srcs, con
     out_vals = dev_alloc(sizeof(int64_t) * (size_t)(elems > 0 ? elems : 1), s);
     if (elems > 0) {
         KernelTimer kt(s, "reach_list_write", 8.0 * (double)elems + 12.0 * (double)nw);
-        hipLaunchKernelGGL(k_rc_listwrite, dim3(grid(s, nw)), dim3(256), 0, st, nw, F, P<int64_t>(offs), lo,
-                           P<int64_t>(out_vals));
+        if (ord)
+            hipLaunchKernelGGL(k_rc_listwrite<true>, dim3(grid(s, nw)), dim3(256), 0, st, nw, P<uint32_t>(ranked),
+                               P<int64_t>(offs), lo, P<int64_t>(out_vals), P<int64_t>(ord->sorted_orig));
+        else
+            hipLaunchKernelGGL(k_rc_listwrite<false>, dim3(grid(s, nw)), dim3(256), 0, st, nw, F, P<int64_t>(offs), lo,
+                               P<int64_t>(out_vals), (const int64_t*)nullptr);
     }
     HIP_CHECK(hipGetLastError());
     return elems;
+}
+
+// The signed order of n original ids: ORDER BY's key image of a Long (the sign bit flipped) under the 64-bit radix
+// sort, the dense index as the payload.
+std::shared_ptr<const IdOrder> id_order_build(capsmi_session* s, const int64_t* orig, int64_t n, bool* dup) {
+    using namespace reach;
+    hipStream_t st = s->stream;
+    auto o = std::make_shared<IdOrder>();
+    o->n = n;
+    o->sorted_orig = dev_alloc(sizeof(int64_t) * (size_t)(n > 0 ? n : 1), s);
+    o->by_rank = dev_alloc(sizeof(int64_t) * (size_t)(n > 0 ? n : 1), s);
+    if (dup) *dup = false;
+    if (n <= 0) return o;
+    uint64_t* key = P<uint64_t>(o->sorted_orig);
+    Buf flag;
+    {
+        KernelTimer kt(s, "reach_list_order", 16.0 * (double)n);
+        iota_i64(P<int64_t>(o->by_rank), 0, n, st);
+        order_keys(s, orig, nullptr, CAPSMI_I64, false, false, P<int64_t>(o->by_rank), n, key);
+        radix_sort_pairs(s, key, P<int64_t>(o->by_rank), n, 0, 64);
+        if (dup) {
+            flag = dev_alloc(sizeof(int64_t), s);
+            HIP_CHECK(hipMemsetAsync(P<void>(flag), 0, sizeof(int64_t), st));
+            hipLaunchKernelGGL(k_ro_dup, dim3(grid(s, n)), dim3(256), 0, st, n, key, P<int64_t>(flag));
+        }
+        hipLaunchKernelGGL(k_ro_unkey, dim3(grid(s, n)), dim3(256), 0, st, n, key);
+    }
+    HIP_CHECK(hipGetLastError());
+    if (dup) *dup = read_scalar(s, P<int64_t>(flag)) != 0;
+    return o;
 }
 
 }  // namespace capsmi

@@ -1892,9 +1892,20 @@ bool fused_var_length_distinct(capsmi_session* s, const capsmi_table* in, const 
     int64_t lo, hi;
     if (!id_window(B, &lo, &hi)) return false;
     // The lists ascend in the ids the walk runs on.  A compacted graph's dense ids are hash group numbers
-    // (graph_compact: orig[] is not monotonic, the scrambled form neither), so mapping them back element-wise would
-    // leave the lists unsorted: collect on such a graph stays on the operator path, which sorts the original ids.
-    if (lag && g_dense) return false;
+    // (graph_compact: orig[] is not monotonic), so the extraction walks the domain in the order of the original ids
+    // (DenseIds::order, built at the first collect and kept; k_reach.hip "Remapped ids") and stores those.  The
+    // scrambled form of a distributed graph has no orig table: collect there stays on the operator path, which sorts
+    // the original ids (distributed sessions were declined above).
+    if (lag && g_dense && g_dense->scrambled) return false;
+    std::shared_ptr<const IdOrder> ord;
+    const int64_t* orig = nullptr;
+    if (lag && g_dense) {
+        if (hi - lo != g_dense->n) return false;
+        std::lock_guard<std::mutex> lk(g_dense->order_mu);
+        if (!g_dense->order) g_dense->order = id_order_build(s, P<int64_t>(g_dense->orig), g_dense->n);
+        ord = g_dense->order;
+        orig = P<int64_t>(g_dense->orig);
+    }
     BitmapSet bs;
     capsmi_bitmap *abm = nullptr, *bbm = nullptr;
     RelViews views;
@@ -1951,8 +1962,8 @@ bool fused_var_length_distinct(capsmi_session* s, const capsmi_table* in, const 
     if (abm->any_dup || bbm->any_dup) return false;
     if (!grouped && lag) {  // one row: the union's list, and its length as the count
         capsmi_table* lt = nullptr;
-        check(capsmi_var_length_reach_list(s, (int32_t)views.t.size(), views.t.data(), "s", "t", abm, bbm, l, u,
-                                           lag->output.c_str(), &lt));
+        var_length_reach_list_table(s, (int32_t)views.t.size(), views.t.data(), "s", "t", abm, bbm, l, u,
+                                    lag->output.c_str(), ord.get(), &lt);
         std::unique_ptr<capsmi_table, void (*)(capsmi_table*)> hold(lt, [](capsmi_table* t) { capsmi_table_release(t); });
         auto* r = result_table(s, 1);
         for (const AggSpec& ag : g.aggs) {
@@ -1979,10 +1990,9 @@ bool fused_var_length_distinct(capsmi_session* s, const capsmi_table* in, const 
         route(s, "var_length_distinct");
         return true;
     }
-    if (lag) {  // (id, list[, count]) in the order of the aggregates; no dense ids here (above)
-        check(capsmi_var_length_collect_distinct(s, (int32_t)views.t.size(), views.t.data(), "s", "t", abm, bbm, l, u,
-                                                 g.a[0].c_str(), lag->output.c_str(), cag ? cag->output.c_str() : nullptr,
-                                                 out));
+    if (lag) {  // (id, list[, count]) in the order of the aggregates; on dense ids, original ids throughout
+        var_length_collect_table(s, (int32_t)views.t.size(), views.t.data(), "s", "t", abm, bbm, l, u, g.a[0].c_str(),
+                                 lag->output.c_str(), cag ? cag->output.c_str() : nullptr, orig, ord.get(), out);
         if (cag && cag == &g.aggs[0]) std::swap((*out)->cols[1], (*out)->cols[2]);
         route(s, "var_length_distinct");
         return true;

@@ -845,6 +845,39 @@ capsmi_status capsmi_var_length_reach_list(capsmi_session* s, int32_t nrels, cap
                                            const char* src_col, const char* dst_col, const capsmi_bitmap* a_ok,
                                            const capsmi_bitmap* b_ok, int32_t lower, int32_t upper, const char* list_name,
                                            capsmi_table** out);
+/* capsmi_var_length_collect_distinct over remapped ids: the bitmaps and the relationship columns hold dense ids (the
+ * domain [a_ok->lo, a_ok->hi) of n ids, as capsmi_graph_compact numbers a graph), and `orig`, a device array of
+ * orig_len = n int64, gives the original id of dense id a_ok->lo + d at orig[d].
+ *   RETURN id(a) AS <id_name>, collect(DISTINCT b) AS <list_name> [, count(DISTINCT b) AS <count_name>]
+ * with id(a) and the list elements in ORIGINAL ids: every list is sort_array(collect_set(id(b))), strictly ascending
+ * by signed value (Long order: negative ids first), whatever order orig has.  No list element is sorted: the n
+ * original ids are sorted once per call (ORDER BY's radix sort), and the walk of capsmi_var_length_collect_distinct
+ * runs over the domain in that order.  The same lemma (for lower <= 1 the ends of the relationship-distinct paths are
+ * the ends of the walks of length in [1, upper]: DESIGN.md section 4), so lower >= 2 is CAPSMI_ERR_NOT_IMPLEMENTED
+ * (use the join plan); the same lower = 0 rule (a's list holds a itself whatever b_ok(a) says, once); the same
+ * CAPSMI_REACH_LIST_LIMIT guard (CAPSMI_ERR_UNSUPPORTED, the session stays usable).  One row per a with a non-empty
+ * list, in no particular order; with orig[d] = a_ok->lo + d the table equals capsmi_var_length_collect_distinct's.
+ * orig must hold distinct ids: orig_len != n, or an id that occurs twice (seen in the sorted ids, one pass and an
+ * 8-byte read-back), is CAPSMI_ERR_ILLEGAL_ARGUMENT.  The call reads orig on the session's stream and keeps no
+ * reference to it.  The planner's route on a compacted graph keeps the order with the graph instead of sorting per
+ * call. */
+capsmi_status capsmi_var_length_collect_distinct_mapped(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                                        const char* src_col, const char* dst_col,
+                                                        const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok,
+                                                        int32_t lower, int32_t upper, const int64_t* orig,
+                                                        int64_t orig_len, const char* id_name, const char* list_name,
+                                                        const char* count_name, capsmi_table** out);
+/* The ungrouped form over remapped ids: RETURN collect(DISTINCT b) AS <list_name>, exactly one row holding the union
+ * of the per-a lists above in ORIGINAL ids, strictly ascending by signed value (Long order), the empty list when
+ * nothing is reached.  One BFS from all of a_ok on the dense ids; the answer's bitmap is permuted into the order of
+ * the original ids before it is written out.  The same lemma (lower >= 2 is CAPSMI_ERR_NOT_IMPLEMENTED: use the join
+ * plan), the same lower = 0 rule, the same CAPSMI_REACH_LIST_LIMIT guard, and the same contract for orig (orig_len
+ * ids, distinct, else CAPSMI_ERR_ILLEGAL_ARGUMENT). */
+capsmi_status capsmi_var_length_reach_list_mapped(capsmi_session* s, int32_t nrels, capsmi_table* const* rels,
+                                                  const char* src_col, const char* dst_col, const capsmi_bitmap* a_ok,
+                                                  const capsmi_bitmap* b_ok, int32_t lower, int32_t upper,
+                                                  const int64_t* orig, int64_t orig_len, const char* list_name,
+                                                  capsmi_table** out);
 /* Sharded form of capsmi_var_length_count for one rank of a multi-GPU run.  The
  * rank owns the source ids [own_lo, own_hi); `out_rels` hold the relationships whose source it
  * owns, `in_rels` those from other ranks' sources into its owned ids.  `od` and `y` are caller

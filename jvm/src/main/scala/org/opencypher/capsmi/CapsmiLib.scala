@@ -351,6 +351,13 @@ trait CapsmiLib extends Library {
   def capsmi_var_length_reach_list(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String, dstCol: String,
                                    a: Pointer, b: Pointer, lower: Int, upper: Int, listName: String,
                                    out: PointerByReference): Int
+  def capsmi_var_length_collect_distinct_mapped(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String,
+                                                dstCol: String, a: Pointer, b: Pointer, lower: Int, upper: Int,
+                                                orig: Pointer, origLen: Long, idName: String, listName: String,
+                                                countName: String, out: PointerByReference): Int
+  def capsmi_var_length_reach_list_mapped(s: Pointer, nrels: Int, rels: Array[Pointer], srcCol: String, dstCol: String,
+                                          a: Pointer, b: Pointer, lower: Int, upper: Int, orig: Pointer, origLen: Long,
+                                          listName: String, out: PointerByReference): Int
 
   // ingest (EdgeListDataSource / FSGraphSource CSV)
   def capsmi_read_csv(s: Pointer, nfiles: Int, paths: Array[String], delimiter: Byte, comment: Byte, ncols: Int,
