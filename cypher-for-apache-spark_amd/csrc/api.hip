@@ -450,6 +450,33 @@ const Column& rel_col(const capsmi_table* t, const char* name) {
     return c;
 }
 
+// The relationship tables of a fused entry point as the kernels take them.  Per table, in order: the null check
+// (under the name `what`), its materialisation, the lookup of its source column, then of its target column; with
+// REL_NARROW / REL_PRESENCE also the columns' 32-bit copies / presence words, where the table carries them.
+struct RelArgs {
+    std::vector<const int64_t*> srcs, dsts;
+    std::vector<int64_t> ms;
+    std::vector<NarrowRel> nar;
+    std::vector<PresenceRel> pres;
+};
+enum { REL_NARROW = 1, REL_PRESENCE = 2 };
+RelArgs rel_args(const capsmi_session* s, int32_t nrels, capsmi_table* const* rels, const char* src_col,
+                 const char* dst_col, int with = 0, const char* what = "rels[i]") {
+    RelArgs r;
+    for (int i = 0; i < nrels; ++i) {
+        need(rels[i], what);
+        M(rels[i]);
+        const Column& sc = rel_col(rels[i], src_col);
+        const Column& dc = rel_col(rels[i], dst_col);
+        r.srcs.push_back(sc.d());
+        r.dsts.push_back(dc.d());
+        if (with & REL_NARROW) r.nar.push_back(narrow_rel(s, sc, dc));
+        if (with & REL_PRESENCE) r.pres.push_back(presence_rel(s, sc, dc, rels[i]->nrows));
+        r.ms.push_back(rels[i]->nrows);
+    }
+    return r;
+}
+
 void check_bitmap(const capsmi_bitmap* b, const char* what) {
     need(b, what);
 }
@@ -1898,20 +1925,10 @@ static bool same_domain(const capsmi_bitmap* a, const capsmi_bitmap* b, const ca
 
 static void build_part(capsmi_session* s, int32_t nrels, capsmi_table* const* rels, const char* src_col,
                        const char* dst_col, int64_t lo, int64_t hi, RelPart& rp, const RelPartHop1* h1 = nullptr) {
-    std::vector<const int64_t*> srcs, dsts;
-    std::vector<int64_t> ms;
-    std::vector<NarrowRel> nar;  // pass 1 reads a table's 32-bit endpoint copies where it carries them
-    std::vector<PresenceRel> pres;  // hop 1 for a full a reads the tables' presence words where all offer them
-    for (int i = 0; i < nrels; ++i) {
-        need(rels[i], "rels[i]");
-        M(rels[i]);
-        srcs.push_back(rel_col(rels[i], src_col).d());
-        dsts.push_back(rel_col(rels[i], dst_col).d());
-        nar.push_back(narrow_rel(s, rel_col(rels[i], src_col), rel_col(rels[i], dst_col)));
-        pres.push_back(presence_rel(s, rel_col(rels[i], src_col), rel_col(rels[i], dst_col), rels[i]->nrows));
-        ms.push_back(rels[i]->nrows);
-    }
-    relpart_build(s, srcs.data(), dsts.data(), ms.data(), nrels, lo, hi, rp, h1, false, nar.data(), pres.data());
+    // pass 1 reads a table's 32-bit endpoint copies where it carries them; hop 1 for a full a reads the tables'
+    // presence words where all offer them
+    const RelArgs r = rel_args(s, nrels, rels, src_col, dst_col, REL_NARROW | REL_PRESENCE);
+    relpart_build(s, r.srcs.data(), r.dsts.data(), r.ms.data(), nrels, lo, hi, rp, h1, false, r.nar.data(), r.pres.data());
 }
 
 // hop 1 on a partitioned layout into X1 (= M | S1) and X2 (= M | S2); S1 scratch
@@ -2063,16 +2080,9 @@ capsmi_status capsmi_undirected_count(capsmi_session* s, int32_t nrels, capsmi_t
     REQUIRE(kind >= 0 && kind <= 2, CAPSMI_ERR_ILLEGAL_ARGUMENT, "undirected patterns: kind");
     if (hops == 2) check_bitmap(c_ok, "c_ok");
     use_device(s);
-    std::vector<const int64_t*> srcs, dsts;
-    std::vector<int64_t> ms;
-    for (int i = 0; i < nrels; ++i) {
-        need(rels[i], "rels[i]");
-        M(rels[i]);
-        srcs.push_back(rel_col(rels[i], src_col).d());
-        dsts.push_back(rel_col(rels[i], dst_col).d());
-        ms.push_back(rels[i]->nrows);
-    }
-    *out = undirected_count(s, srcs.data(), dsts.data(), ms.data(), nrels, hops, a_ok, b_ok, hops == 2 ? c_ok : b_ok, kind);
+    const RelArgs r = rel_args(s, nrels, rels, src_col, dst_col);
+    *out = undirected_count(s, r.srcs.data(), r.dsts.data(), r.ms.data(), nrels, hops, a_ok, b_ok,
+                            hops == 2 ? c_ok : b_ok, kind);
     API_END
 }
 
@@ -2097,20 +2107,11 @@ capsmi_status capsmi_var_length_count(capsmi_session* s, int32_t nrels, capsmi_t
             "fused var-length upper 4: at most 2^24 - 2 ids");
     REQUIRE(std::string(id_name) != count_name, CAPSMI_ERR_ILLEGAL_ARGUMENT, "output names must differ");
     use_device(s);
-    std::vector<const int64_t*> srcs, dsts;
-    std::vector<int64_t> ms;
-    std::vector<NarrowRel> nar;  // for the two partitions' pass 1 (the other passes read the int64 words)
-    for (int i = 0; i < nrels; ++i) {
-        need(rels[i], "rels[i]");
-        M(rels[i]);
-        srcs.push_back(rel_col(rels[i], src_col).d());
-        dsts.push_back(rel_col(rels[i], dst_col).d());
-        nar.push_back(narrow_rel(s, rel_col(rels[i], src_col), rel_col(rels[i], dst_col)));
-        ms.push_back(rels[i]->nrows);
-    }
+    // the 32-bit copies: for the two partitions' pass 1 (the other passes read the int64 words)
+    const RelArgs r = rel_args(s, nrels, rels, src_col, dst_col, REL_NARROW);
     Buf ids, cnt;
-    const int64_t rows = var_length_count(s, srcs.data(), dsts.data(), ms.data(), nrels, a_ok, b_ok, lower, upper, ids,
-                                          cnt, nar.data());
+    const int64_t rows = var_length_count(s, r.srcs.data(), r.dsts.data(), r.ms.data(), nrels, a_ok, b_ok, lower, upper,
+                                          ids, cnt, r.nar.data());
     auto* o = new_table(s, rows);
     Column a, c;
     a.name = id_name;
@@ -2126,14 +2127,9 @@ capsmi_status capsmi_var_length_count(capsmi_session* s, int32_t nrels, capsmi_t
 }
 
 namespace {
-// the argument checks and relationship views shared by the two count(DISTINCT b) entries
-struct ReachArgs {
-    std::vector<const int64_t*> srcs, dsts;
-    std::vector<int64_t> ms;
-    std::vector<NarrowRel> nar;
-};
+// the argument checks and relationship views shared by the count / collect(DISTINCT b) entries
 void reach_args(capsmi_session* s, int32_t nrels, capsmi_table* const* rels, const char* src_col, const char* dst_col,
-                const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int32_t lower, int32_t upper, ReachArgs& r) {
+                const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int32_t lower, int32_t upper, RelArgs& r) {
     need(s, "session");
     check_bitmap(a_ok, "a_ok");
     check_bitmap(b_ok, "b_ok");
@@ -2147,14 +2143,7 @@ void reach_args(capsmi_session* s, int32_t nrels, capsmi_table* const* rels, con
     REQUIRE(!a_ok->any_dup && !b_ok->any_dup, CAPSMI_ERR_UNSUPPORTED,
             "fused count(DISTINCT b) needs each node id in one scanned row");
     use_device(s);
-    for (int i = 0; i < nrels; ++i) {
-        need(rels[i], "rels[i]");
-        M(rels[i]);
-        r.srcs.push_back(rel_col(rels[i], src_col).d());
-        r.dsts.push_back(rel_col(rels[i], dst_col).d());
-        r.nar.push_back(narrow_rel(s, rel_col(rels[i], src_col), rel_col(rels[i], dst_col)));
-        r.ms.push_back(rels[i]->nrows);
-    }
+    r = rel_args(s, nrels, rels, src_col, dst_col, REL_NARROW);
 }
 }  // namespace
 
@@ -2167,7 +2156,7 @@ capsmi_status capsmi_var_length_count_distinct(capsmi_session* s, int32_t nrels,
     need(out, "out");
     need(id_name, "id_name");
     need(count_name, "count_name");
-    ReachArgs r;
+    RelArgs r;
     reach_args(s, nrels, rels, src_col, dst_col, a_ok, b_ok, lower, upper, r);
     REQUIRE(std::string(id_name) != count_name, CAPSMI_ERR_ILLEGAL_ARGUMENT, "output names must differ");
     Buf ids, cnt;
@@ -2194,7 +2183,7 @@ capsmi_status capsmi_var_length_reach_count(capsmi_session* s, int32_t nrels, ca
     API_BEGIN
     need(s, "session");
     need(out_distinct, "out_distinct");
-    ReachArgs r;
+    RelArgs r;
     reach_args(s, nrels, rels, src_col, dst_col, a_ok, b_ok, lower, upper, r);
     *out_distinct = var_length_reach_count(s, r.srcs.data(), r.dsts.data(), r.ms.data(), nrels, a_ok, b_ok, lower, upper,
                                            r.nar.data());
@@ -2208,7 +2197,7 @@ void var_length_collect_table(capsmi_session* s, int32_t nrels, capsmi_table* co
                               const char* dst_col, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int32_t lower,
                               int32_t upper, const char* id_name, const char* list_name, const char* count_name,
                               const int64_t* orig, const IdOrder* ord, capsmi_table** out) {
-    ReachArgs r;
+    RelArgs r;
     reach_args(s, nrels, rels, src_col, dst_col, a_ok, b_ok, lower, upper, r);
     const std::string idn(id_name), ln(list_name);
     REQUIRE(idn != ln && (!count_name || (idn != count_name && ln != count_name)), CAPSMI_ERR_ILLEGAL_ARGUMENT,
@@ -2241,7 +2230,7 @@ void var_length_collect_table(capsmi_session* s, int32_t nrels, capsmi_table* co
 void var_length_reach_list_table(capsmi_session* s, int32_t nrels, capsmi_table* const* rels, const char* src_col,
                                  const char* dst_col, const capsmi_bitmap* a_ok, const capsmi_bitmap* b_ok, int32_t lower,
                                  int32_t upper, const char* list_name, const IdOrder* ord, capsmi_table** out) {
-    ReachArgs r;
+    RelArgs r;
     reach_args(s, nrels, rels, src_col, dst_col, a_ok, b_ok, lower, upper, r);
     auto L = std::make_shared<ListStore>();
     L->elem = CAPSMI_I64;
@@ -2374,26 +2363,12 @@ capsmi_status capsmi_varlen_shard_begin(capsmi_session* s, int32_t nout, capsmi_
     REQUIRE(!a_ok->any_dup && !b_ok->any_dup, CAPSMI_ERR_UNSUPPORTED,
             "fused count(*) needs each node id in one scanned row");
     use_device(s);
-    std::vector<const int64_t*> srcs, dsts, isrcs, idsts;
-    std::vector<int64_t> ms, ims;
-    for (int i = 0; i < nout; ++i) {
-        need(out_rels[i], "out_rels[i]");
-        M(out_rels[i]);
-        srcs.push_back(rel_col(out_rels[i], src_col).d());
-        dsts.push_back(rel_col(out_rels[i], dst_col).d());
-        ms.push_back(out_rels[i]->nrows);
-    }
-    for (int i = 0; i < nin; ++i) {
-        need(in_rels[i], "in_rels[i]");
-        M(in_rels[i]);
-        isrcs.push_back(rel_col(in_rels[i], src_col).d());
-        idsts.push_back(rel_col(in_rels[i], dst_col).d());
-        ims.push_back(in_rels[i]->nrows);
-    }
+    const RelArgs o = rel_args(s, nout, out_rels, src_col, dst_col, 0, "out_rels[i]");
+    const RelArgs i = rel_args(s, nin, in_rels, src_col, dst_col, 0, "in_rels[i]");
     auto h = std::make_unique<capsmi_varlen_shard>();
     h->sess = s;
-    h->v = varlen_shard_begin(s, srcs.data(), dsts.data(), ms.data(), nout, isrcs.data(), idsts.data(), ims.data(),
-                              nin, a_ok, b_ok, lower, upper, own_lo, own_hi, od);
+    h->v = varlen_shard_begin(s, o.srcs.data(), o.dsts.data(), o.ms.data(), nout, i.srcs.data(), i.dsts.data(),
+                              i.ms.data(), nin, a_ok, b_ok, lower, upper, own_lo, own_hi, od);
     *out = h.release();
     API_END
 }
@@ -2447,17 +2422,6 @@ struct capsmi_trigraph {
     capsmi_session* sess = nullptr;
     capsmi::TriGraph g;
 };
-
-static void rel_cols(int32_t nrels, capsmi_table* const* rels, const char* src_col, const char* dst_col,
-                     std::vector<const int64_t*>& srcs, std::vector<const int64_t*>& dsts, std::vector<int64_t>& ms) {
-    for (int i = 0; i < nrels; ++i) {
-        need(rels[i], "rels[i]");
-        M(rels[i]);
-        srcs.push_back(rel_col(rels[i], src_col).d());
-        dsts.push_back(rel_col(rels[i], dst_col).d());
-        ms.push_back(rels[i]->nrows);
-    }
-}
 
 // f over a temporary trigraph of the relationships: the first failing status of build and f
 template <class F>
@@ -2524,13 +2488,11 @@ capsmi_status capsmi_trigraph_build(capsmi_session* s, int32_t nrels, capsmi_tab
     REQUIRE(!n_ok->any_dup, CAPSMI_ERR_UNSUPPORTED, "fused count(*) needs each node id in one scanned row");
     REQUIRE(nrels >= 0 && (nrels == 0 || rels), CAPSMI_ERR_ILLEGAL_ARGUMENT, "rels");
     use_device(s);
-    std::vector<const int64_t*> srcs, dsts;
-    std::vector<int64_t> ms;
-    rel_cols(nrels, rels, src_col, dst_col, srcs, dsts, ms);
+    const RelArgs r = rel_args(s, nrels, rels, src_col, dst_col);
     auto* g = new capsmi_trigraph();
     std::unique_ptr<capsmi_trigraph> guard(g);
     g->sess = s;
-    tri_build(s, srcs.data(), dsts.data(), ms.data(), nrels, n_ok, g->g);
+    tri_build(s, r.srcs.data(), r.dsts.data(), r.ms.data(), nrels, n_ok, g->g);
     *out = guard.release();
     API_END
 }
@@ -2808,18 +2770,10 @@ capsmi_status capsmi_count_shard_begin(capsmi_session* s, int32_t nrels, capsmi_
     REQUIRE(0 <= own_lo && own_lo <= own_hi && own_hi <= n, CAPSMI_ERR_ILLEGAL_ARGUMENT, "count shard: owned range");
     REQUIRE(own_hi == own_lo || owned_in, CAPSMI_ERR_ILLEGAL_ARGUMENT, "null argument: owned_in");
     use_device(s);
-    std::vector<const int64_t*> srcs, dsts;
-    std::vector<int64_t> ms;
-    for (int i = 0; i < nrels; ++i) {
-        need(rels[i], "rels[i]");
-        M(rels[i]);
-        srcs.push_back(rel_col(rels[i], src_col).d());
-        dsts.push_back(rel_col(rels[i], dst_col).d());
-        ms.push_back(rels[i]->nrows);
-    }
+    const RelArgs r = rel_args(s, nrels, rels, src_col, dst_col);
     auto h = std::make_unique<capsmi_count_shard>();
     h->b_words = b_ok->words;
-    count_rec_begin(s, srcs.data(), dsts.data(), ms.data(), nrels, a_ok, b_ok, c_ok, h->cr);
+    count_rec_begin(s, r.srcs.data(), r.dsts.data(), r.ms.data(), nrels, a_ok, b_ok, c_ok, h->cr);
     count_rec_fold(h->cr, own_lo, own_hi, owned_in);
     *out = h.release();
     API_END
@@ -2861,16 +2815,8 @@ capsmi_status capsmi_two_hop_count(capsmi_session* s, int32_t nrels, capsmi_tabl
     const bool same_domain = a_ok->lo == b_ok->lo && a_ok->hi == b_ok->hi && c_ok->lo == b_ok->lo && c_ok->hi == b_ok->hi;
     // (config CAPSMI_COUNT=atomic forces the per-relationship atomic form below, the one above 2^26 ids)
     if (same_domain && n > 0 && n <= (int64_t(1) << 26) && !s->cfg.count_atomic) {
-        std::vector<const int64_t*> srcs, dsts;
-        std::vector<int64_t> ms;
-        for (int i = 0; i < nrels; ++i) {
-            need(rels[i], "rels[i]");
-            M(rels[i]);
-            srcs.push_back(rel_col(rels[i], src_col).d());
-            dsts.push_back(rel_col(rels[i], dst_col).d());
-            ms.push_back(rels[i]->nrows);
-        }
-        *out_rows = two_hop_count_rec(s, srcs.data(), dsts.data(), ms.data(), nrels, a_ok, b_ok, c_ok);
+        const RelArgs r = rel_args(s, nrels, rels, src_col, dst_col);
+        *out_rows = two_hop_count_rec(s, r.srcs.data(), r.dsts.data(), r.ms.data(), nrels, a_ok, b_ok, c_ok);
         return CAPSMI_OK;
     }
     Buf inA = dev_alloc(sizeof(uint32_t) * (n > 0 ? n : 1), s);

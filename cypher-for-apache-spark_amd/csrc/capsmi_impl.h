@@ -74,7 +74,7 @@ struct StrStore {
 };
 inline bool is_str_match(int32_t op) { return op >= CAPSMI_X_STARTS_WITH && op <= CAPSMI_X_CONTAINS; }
 
-// Endpoint presence words of a registered relationship table (presence_endpoints, plan.hip; the rule:
+// Endpoint presence words of a registered relationship table (presence_endpoints, plan_entity.hip; the rule:
 // presence_rule.h): four bitmaps over the endpoints' window [lo, hi), bit k of word 0 standing for id lo + k.
 // Facts about the immutable table which no query shapes; hop 1 of a 2-hop whose first node is unfiltered reads
 // them instead of the relationships (k_presence_hop1, k_part.hip).
@@ -101,7 +101,7 @@ struct Column {
     // host copy of the words of a column built from host values (the fused routes' count rows):
     // exports read it without a device round trip
     std::shared_ptr<const std::vector<int64_t>> host;
-    // optional 32-bit copy of `data`, made when a relationship table is registered (narrow_endpoints, plan.hip):
+    // optional 32-bit copy of `data`, made when a relationship table is registered (narrow_endpoints, plan_entity.hip):
     // narrow[i] = data[i] - narrow_base over the rows the table had then, under the same row `offset`.  The
     // words are immutable and shared, so a copy of the Column carries them along; `narrow_of` names the words
     // they were made from, so a Column whose `data` was replaced since no longer offers them (n32).
@@ -109,7 +109,7 @@ struct Column {
     const DevBuf* narrow_of = nullptr;
     int64_t narrow_base = 0;
     // optional presence words of the relationship table this endpoint column was registered with, shared by both
-    // endpoint columns and carried along like `narrow`; presence_rel (plan.hip) decides whether a pair of columns
+    // endpoint columns and carried along like `narrow`; presence_rel (plan_entity.hip) decides whether a pair of columns
     // may still read them
     std::shared_ptr<const PresenceWords> presence;
     const int64_t* d() const { return P<int64_t>(data) + offset; }
@@ -128,7 +128,7 @@ struct EntityInfo {
     bool ids_exact = false;       // node: the ids are exactly [lo, hi), each once (checked at registration)
     bool ids_unique = false;      // node: no id occurs twice and none is null (checked at registration)
 };
-struct PlanNode;  // lazy Table[T] operator (plan.hip)
+struct PlanNode;  // lazy Table[T] operator (plan_impl.h)
 
 // Dense id space of one graph (capsmi_graph_compact): every node id and relationship endpoint of
 // the graph's entity tables numbered 0..n-1; orig[d] is the Long id of dense id d.  The fused
@@ -274,7 +274,7 @@ struct capsmi_session {
     }
     std::map<std::string, std::pair<int64_t, double>> totals;
     std::map<std::string, double> alg_bytes;  // algorithmic bytes of the timed launches, per name
-    // fused-path routing of lazy plans (plan.hip): enabled flag and per-route counters
+    // fused-path routing of lazy plans (plan_routes.hip): enabled flag and per-route counters
     bool fused = true;
     std::map<std::string, int64_t> routes;
     // multi-GPU rank view (capsmi_session_set_ranks): the host's collective on this session's stream

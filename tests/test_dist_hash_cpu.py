@@ -1,5 +1,5 @@
 """Hash ownership of a distributed graph (include/capsmi.h capsmi_graph_distribute) and the exchanges of
-the distributed two-hop routes (csrc/plan.hip dist_two_hop_distinct / dist_two_hop_count), restated
+the distributed two-hop routes (csrc/plan_dist.hip dist_two_hop_distinct / dist_two_hop_count), restated
 with numpy and rehearsed on CPU with gloo ranks (world size 2 and 4).
 
 Ownership: h(x) = ((x - lo) * 0x9E3779B97F4A7C15) mod 2^k, rank r owns h in [r*32*S, (r+1)*32*S),

@@ -1,5 +1,5 @@
 """Endpoint presence words (CAPSMI_PRESENCE=auto, the default: four bitmaps kept with a registered relationship
-table -- non-loop targets, non-loop sources, ids with one / two self-loops; plan.hip presence_endpoints) and hop 1
+table -- non-loop targets, non-loop sources, ids with one / two self-loops; plan_entity.hip presence_endpoints) and hop 1
 answered from them (k_part.hip k_presence_hop1) in place of k_pool_hop1 / k_hop_2d<HOP1>.
 
 Every 2-hop case registers its tables and runs the cold 2-hop (RelPartition.build_mark_mid + mark_dst) under
