@@ -123,6 +123,18 @@ def two_hop_count(session: Session, rels: Sequence[GpuTable], a_ok: NodeBitmap, 
     return v.value
 
 
+def undirected_count(session: Session, rels: Sequence[GpuTable], hops: int, a_ok: NodeBitmap, b_ok: NodeBitmap,
+                     c_ok: Optional[NodeBitmap] = None, kind: int = 0, src_col: str = "source",
+                     dst_col: str = "target") -> int:
+    """``MATCH (a)-[r]-(b)`` (hops 1) or ``MATCH (a)-[r1]-(b)-[r2]-(c)`` (hops 2, r1 <> r2 implied) with the node
+    filters, ``RETURN count(*)`` (kind 0), ``count(DISTINCT the last node)`` (kind 1) or ``count(DISTINCT a)``
+    (kind 2).  c_ok is ignored for one hop; the bitmaps share one id domain."""
+    v = ctypes.c_int64()
+    _lib.call("capsmi_undirected_count", session.handle, len(rels), _handles(rels), src_col.encode(), dst_col.encode(),
+              hops, a_ok.handle, b_ok.handle, None if c_ok is None else c_ok.handle, kind, ctypes.byref(v))
+    return v.value
+
+
 class CountShard:
     """count(*) of the 2-hop chain on one rank of an owner(target) partition (capsmi_count_shard_*).
 
